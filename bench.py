@@ -1,6 +1,13 @@
 """Benchmark: batched truck-trailer NMPC solves on MI355X (BASELINE.json metric).
 
     python bench.py --gpus N --steps K --warmup W [--config c2|c3|c5|c4|c4all|c4replan|cobs|sim] [--batch B] [--horizon H]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line; everything beyond the headline figure that takes
+work of its own (the CPU baseline, the B = 1 latency, kernel-only launches after the timed loop, the committed
+rocprofv3 traffic passes, the oracle census of the C4 batch) is measured only with --full.  --dump-outputs DIR writes
+what the last timed step left in the output buffers of the timed path as DIR/<name>.npy (float64): the inputs are
+seeded, so the files of two builds run with the same arguments can be compared array by array.
 
 c5 is the sharded path: one global batch on rank 0, RCCL scatter -> solve -> gather (ttmpc/sharded.py).
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py launches the N ranks itself (one process
@@ -14,7 +21,7 @@ per rank -> each rank owns its shard, no data-path collective: weak scaling).
 Prints ONE JSON line on rank 0.  `value` = solves/s of the whole job (sum over ranks / max time).
 `roofline` uses the algorithmic FP64 flop formula of SURVEY.md §8(d) over the per-instance Newton
 iteration counts the kernel returns, divided by the kernel time measured with HIP events on the
-stream the kernel is launched on.  `cpu_baseline` times the CPU oracle (oracle/, the same NLP and
+stream the kernel is launched on.  With --full, `cpu_baseline` times the CPU oracle (oracle/, the same NLP and
 interior-point constants, banded-LU KKT, OpenMP over instances) on a bounded sample on rank 0, with
 as many threads as the host grants this process (OMP_NUM_THREADS, which the GPU pool sets to the
 per-GPU CPU share, else every core in os.sched_getaffinity) and on one core.
@@ -165,6 +172,31 @@ def reduce_over_ranks(dist, wall, ok, B):
     return float(tmax[0]), int(tsum[1]), int(tsum[2])
 
 
+DUMP_CAP_BYTES = 60 * 10 ** 6   # --dump-outputs writes at most this much array data (the limit is 64 MB in all)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: `arrays` maps a name to one output buffer of the timed path (torch or numpy, first axis =
+    instance), as the last timed step left it.  Each goes to DIR/<name>.npy as float64 (the integer status / iteration
+    outputs are converted).  Above DUMP_CAP_BYTES the same fixed sample of instances (rows drawn once with seed 0,
+    ascending) is kept of every array and its indices go to DIR/sample_index.npy."""
+    import numpy as np
+    out = Path(dirname)
+    out.mkdir(parents=True, exist_ok=True)
+    host = {k: np.ascontiguousarray((v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)), dtype=np.float64)
+            for k, v in arrays.items()}
+    B = next(iter(host.values())).shape[0]
+    assert all(a.shape[0] == B for a in host.values())
+    row_bytes = sum(a.nbytes // B for a in host.values())
+    if row_bytes * B > DUMP_CAP_BYTES:
+        keep = DUMP_CAP_BYTES // (row_bytes + 8)
+        idx = np.sort(np.random.default_rng(0).choice(B, size=keep, replace=False))
+        host = {k: a[idx] for k, a in host.items()}
+        host["sample_index"] = idx.astype(np.float64)
+    for k, a in host.items():
+        np.save(out / f"{k}.npy", a)
+
+
 def p50_latency(solver, x0, xr, ur, reps=200):
     """Host wall clock around one B=1 solve incl. H2D/D2H (mirrors simulation.py:519-522)."""
     import numpy as np
@@ -188,8 +220,14 @@ def main():
                          "c4replan: OBCA re-plans around the committed plan; cobs: MPC+OBCA (mpc_control_obs.py)")
     ap.add_argument("--batch", type=int, default=0, help="instances per GPU (default by config)")
     ap.add_argument("--horizon", type=int, default=0)
-    ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU-baseline work (0 = skip)")
-    ap.add_argument("--no-latency", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is not the headline figure: CPU baseline, B = 1 latency, kernel-only launches "
+                         "after the timed loop, committed traffic passes, the C4 oracle census")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the outputs of the last timed step as DIR/<name>.npy (float64; a "
+                         "fixed seeded sample of instances above 60 MB)")
+    ap.add_argument("--cpu-budget", type=float, default=12.0, help="--full: seconds of CPU-baseline work (0 = skip)")
+    ap.add_argument("--no-latency", action="store_true", help="--full: skip the B = 1 latency")
     ap.add_argument("--traffic-csv", default="",
                     help="comma-separated rocprofv3 --pmc CSVs (FETCH_SIZE, WRITE_SIZE) of this config; "
                          "default: the committed profiles/ pair when the config is the default C2")
@@ -199,6 +237,8 @@ def main():
                          "0 = auto: 1 (one launch per rank shard, the measured fastest shape)")
     ap.add_argument("--graph", action="store_true", help="sim: replay one captured closed-loop step (hipGraph)")
     args = ap.parse_args()
+    if not args.full:   # a plain run: the timed steps only
+        args.cpu_budget, args.no_latency = 0.0, True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
     if args.config == "selftest":
@@ -271,6 +311,8 @@ def main():
     if rank != 0:
         dist.destroy_process_group()
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"x_out": X, "u_out": U, "status": status, "iters": iters, "kkt": kkt})
     ms_per_step = wall_max / args.steps * 1e3
     value = B_total * args.steps / wall_max
     F = float(np.sum(flops_per_solve(N, iters.astype(np.float64))))
@@ -278,9 +320,9 @@ def main():
     io = io_bytes_per_solve(N) * B
     traffic = None
     traffic_src = None
-    csvs = [p for p in args.traffic_csv.split(",") if p]
+    csvs = [p for p in args.traffic_csv.split(",") if p] if args.full else []
     src_note = ""
-    if not csvs and (args.config, B, N) in (("c2", 1024, 20), ("c3", 8192, 40)):
+    if args.full and not csvs and (args.config, B, N) in (("c2", 1024, 20), ("c3", 8192, 40)):
         d = REPO / TRACK_PMC[args.config]
         csvs = [str(d / pas / f"{pas}_counter_collection.csv") for pas in ("fetch", "write")]
         src_note = f" (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes of this bench config; HBM bytes per " \
@@ -411,17 +453,21 @@ def main_c5(args):
     if rank != 0:
         dist.destroy_process_group()
         return
-    # kernel-only time of this rank's shard: one more solve on the same stream, HIP events around it
-    k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    with torch.cuda.stream(stream):
-        k0.record(stream)
-        sb.solve_local()
-        k1.record(stream)
-    torch.cuda.synchronize(dev)
-    kernel_ms = k0.elapsed_time(k1)
     X, U, st, it, kk = sb.results()
-    F_shard = float(np.sum(flops_per_solve(N, sb.iters()[: sb.valid].cpu().numpy().astype(np.float64))))
-    achieved = F_shard / (kernel_ms * 1e-3) / 1e12
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"x_out": X, "u_out": U, "status": st, "iters": it, "kkt": kk})
+    kernel_ms = achieved = None
+    if args.full:
+        # kernel-only time of this rank's shard: one more solve on the same stream, HIP events around it
+        k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        with torch.cuda.stream(stream):
+            k0.record(stream)
+            sb.solve_local()
+            k1.record(stream)
+        torch.cuda.synchronize(dev)
+        kernel_ms = k0.elapsed_time(k1)
+        F_shard = float(np.sum(flops_per_solve(N, sb.iters()[: sb.valid].cpu().numpy().astype(np.float64))))
+        achieved = F_shard / (kernel_ms * 1e-3) / 1e12
     out = {
         "metric": "MPC solves/sec (N=20, nx=6, nu=2; BASELINE label says nx=5, the reference model has 6 states)"
         if N == 20 else f"MPC solves/sec (N={N}, nx=6, nu=2)",
@@ -446,11 +492,12 @@ def main_c5(args):
         "solver": {"converged_or_acceptable": stats["converged"], "instances": stats["instances"],
                    "iters_mean": float(it.mean()), "iters_max": stats["iters_max"], "kkt_max": stats["kkt_max"],
                    "step_ms_rank0_hip_events": round(step_ms_local, 4),
-                   "kernel_ms_per_launch": round(kernel_ms, 4)},
-        "roofline": {"bound": "valu_fp64", "achieved": round(achieved, 4), "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": round(achieved / FP64_PEAK_TFLOPS, 6), "traffic": None,
-                     "note": "rank-0 shard kernel (track_kernel) only; SURVEY §8(d) flop formula x per-instance "
-                             "iterations"},
+                   "kernel_ms_per_launch": None if kernel_ms is None else round(kernel_ms, 4)},
+        "roofline": {"bound": "valu_fp64", "achieved": None if achieved is None else round(achieved, 4),
+                     "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
+                     "frac": None if achieved is None else round(achieved / FP64_PEAK_TFLOPS, 6), "traffic": None,
+                     "note": "rank-0 shard kernel (track_kernel) only, timed in a launch of its own (--full); SURVEY "
+                             "§8(d) flop formula x per-instance iterations"},
     }
     if args.cpu_budget > 0 and world == 1:
         out["cpu_baseline"] = cpu_baseline("c5", min(B_total, 8192), N, rank_seed(0), args.cpu_budget)
@@ -535,17 +582,23 @@ def main_sim(args):
     if rank != 0:
         dist.destroy_process_group()
         return
-    # one more solve alone: the track_kernel share of a closed-loop step
-    k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    k0.record(cl.stream)
-    solver.solve_device(B, cl.x_meas.data_ptr(), cl.xref.data_ptr(), cl.uref.data_ptr(), cl.X.data_ptr(),
-                        cl.U.data_ptr(), cl.st.data_ptr(), cl.it.data_ptr(), cl.kkt.data_ptr(),
-                        stream=cl.stream.cuda_stream)
-    k1.record(cl.stream)
-    torch.cuda.synchronize(dev)
-    kernel_ms = k0.elapsed_time(k1)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"state": cl.state, "x_out": cl.X, "u_out": cl.U, "u_applied": cl.u_applied,
+                                         "status": cl.st, "iters": cl.it, "kkt": cl.kkt, "collision_flag": cl.flag})
+    kernel_ms = achieved = None
+    if args.full:
+        # one more solve alone: the track_kernel share of a closed-loop step
+        k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        k0.record(cl.stream)
+        solver.solve_device(B, cl.x_meas.data_ptr(), cl.xref.data_ptr(), cl.uref.data_ptr(), cl.X.data_ptr(),
+                            cl.U.data_ptr(), cl.st.data_ptr(), cl.it.data_ptr(), cl.kkt.data_ptr(),
+                            stream=cl.stream.cuda_stream)
+        k1.record(cl.stream)
+        torch.cuda.synchronize(dev)
+        kernel_ms = k0.elapsed_time(k1)
     iters = cl.it.cpu().numpy()
-    F = float(np.sum(flops_per_solve(N, iters.astype(np.float64))))
+    if kernel_ms is not None:
+        achieved = float(np.sum(flops_per_solve(N, iters.astype(np.float64)))) / (kernel_ms * 1e-3) / 1e12
     out = {
         "metric": f"closed-loop MPC steps/sec (simulation.py loop, N={N}, disturbed plant)",
         "value": round(B_total * args.steps / wall_max, 1),
@@ -567,10 +620,13 @@ def main_sim(args):
         "solver": {"converged_or_acceptable_last_step": ok_total, "instances": B_total,
                    "status_counts_last_step": {str(k): int(v) for k, v in zip(*np.unique(st, return_counts=True))},
                    "iters_mean_last_step": float(iters.mean()), "step_ms_hip_events": round(
-                       e0.elapsed_time(e1) / args.steps, 4), "kernel_ms_per_solve": round(kernel_ms, 4)},
-        "roofline": {"bound": "valu_fp64", "achieved": round(F / (kernel_ms * 1e-3) / 1e12, 4), "peak": FP64_PEAK_TFLOPS,
-                     "unit": "TFLOP/s", "frac": round(F / (kernel_ms * 1e-3) / 1e12 / FP64_PEAK_TFLOPS, 6),
-                     "traffic": None, "note": "track_kernel of one closed-loop step; SURVEY §8(d) flop formula"},
+                       e0.elapsed_time(e1) / args.steps, 4),
+                   "kernel_ms_per_solve": None if kernel_ms is None else round(kernel_ms, 4)},
+        "roofline": {"bound": "valu_fp64", "achieved": None if achieved is None else round(achieved, 4),
+                     "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
+                     "frac": None if achieved is None else round(achieved / FP64_PEAK_TFLOPS, 6),
+                     "traffic": None, "note": "track_kernel of one closed-loop step, timed in a launch of its own (--full); "
+                                              "SURVEY §8(d) flop formula"},
     }
     if args.cpu_budget > 0 and world == 1:
         out["cpu_baseline"] = sim_cpu_baseline(S, U, g["obstacles"], x0, N, params, args.cpu_budget)
@@ -712,6 +768,8 @@ def main_obca(args):
     if rank != 0:
         dist.destroy_process_group()
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"x_out": X, "u_out": U, "status": status, "iters": iters, "kkt": kk})
     F = float(np.sum(obca_flops(N, M, iters.astype(np.float64))))
     achieved = F / (kernel_ms * 1e-3) / 1e12
     name = {"c4": "c4: TrajectoryOptimization OBCA plans of the 4 collision-free test_cases.json cases x start "
@@ -728,7 +786,7 @@ def main_obca(args):
         solver_rec["infeasible_by_construction"] = int(blocked.sum())
         solver_rec["converged_of_feasible"] = f"{int(np.sum((status <= 1) & ~blocked))}/{int(np.sum(~blocked))}"
     census = REPO / "tests" / "golden" / "c4_census.json"
-    if args.config == "c4" and (B, N, M, rank_seed(rank)) == (256, 200, 6, 7) and census.exists():
+    if args.full and args.config == "c4" and (B, N, M, rank_seed(rank)) == (256, 200, 6, 7) and census.exists():
         # instance-by-instance agreement with the oracle census of this exact batch (tests/golden/make_c4_census.py): which
         # failures the restated IPOPT shares (its behaviour) and which are the kernel's alone (drift)
         cen = json.loads(census.read_text()).get("bench")
@@ -749,7 +807,7 @@ def main_obca(args):
                 solver_rec["oracle_census"]["oracle_rounding_sensitive"] = int(sens.sum())
                 solver_rec["oracle_census"]["status_mismatch_not_oracle_sensitive"] = \
                     np.flatnonzero((status != stc) & ~sens).tolist()
-    traffic, traffic_src, traffic_est = obca_traffic(args.config, float(iters.sum()))
+    traffic, traffic_src, traffic_est = obca_traffic(args.config, float(iters.sum())) if args.full else (None, None, None)
     out = {
         "metric": f"OBCA {'plan' if args.config != 'cobs' else 'MPC+OBCA'} solves/sec (N={N}, M={M} obstacles, "
                   f"n={n} variables; converged or acceptable solves only)",

@@ -6,7 +6,7 @@ OUT=${1:-gpurun_out/configs}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 for c in c3 c5; do
-  timeout -k 10 300 python bench.py --config $c --steps 10 --warmup 2 --cpu-budget 10 > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err" || { echo BENCH_FAILED $c; tail -20 "$OUT/bench_$c.err"; exit 1; }
+  timeout -k 10 300 python bench.py --full --config $c --steps 10 --warmup 2 --cpu-budget 10 > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err" || { echo BENCH_FAILED $c; tail -20 "$OUT/bench_$c.err"; exit 1; }
   cat "$OUT/bench_$c.json"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_$c" -o run --output-format csv \
     -- python3 bench.py --config $c --steps 10 --warmup 2 --cpu-budget 0 --no-latency > "$OUT/prof_$c.log" 2>&1 || { echo PROF_FAILED $c; tail -20 "$OUT/prof_$c.log"; exit 1; }

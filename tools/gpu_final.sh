@@ -9,7 +9,7 @@ timeout -k 10 500 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout
 tail -2 "$OUT/gpu_tests.log"
 bench() {
   local name=$1; shift
-  timeout -k 10 400 python bench.py "$@" > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err" || { echo "BENCH_FAILED $name"; tail -20 "$OUT/bench_$name.err"; exit 1; }
+  timeout -k 10 400 python bench.py --full "$@" >"$OUT/bench_$name.json" 2> "$OUT/bench_$name.err" || { echo "BENCH_FAILED $name"; tail -20 "$OUT/bench_$name.err"; exit 1; }
   head -c 300 "$OUT/bench_$name.json"; echo
   timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/prof_$name" -o run --output-format csv \
     -- python3 bench.py "$@" --cpu-budget 0 --no-latency > "$OUT/prof_$name.log" 2>&1 || { echo "PROF_FAILED $name"; tail -20 "$OUT/prof_$name.log"; exit 1; }

@@ -11,7 +11,7 @@ tail -2 "$OUT/gpu_tests.log"; grep -E "FAILED|ERROR" "$OUT/gpu_tests.log" | head
 [ $rc -le 1 ] || exit 1
 bench() {
   local name=$1; shift
-  timeout -k 10 300 python bench.py "$@" > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err" || { echo "BENCH_FAILED $name"; tail -20 "$OUT/bench_$name.err"; exit 1; }
+  timeout -k 10 300 python bench.py --full "$@" >"$OUT/bench_$name.json" 2> "$OUT/bench_$name.err" || { echo "BENCH_FAILED $name"; tail -20 "$OUT/bench_$name.err"; exit 1; }
   head -c 400 "$OUT/bench_$name.json"; echo
 }
 kstats() {

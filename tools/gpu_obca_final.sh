@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 bash tools/obca_pmc.sh "$OUT/pmc_c4" c4 300 hbm || exit 1
 bash tools/obca_pmc.sh "$OUT/pmc_cobs" cobs 300 hbm || exit 1
 for cfg in c4 cobs c4all; do
-  timeout -k 10 400 python -u bench.py --config $cfg --steps 1 --warmup 1 > "$OUT/bench_$cfg.json" 2> "$OUT/bench_$cfg.err" || { echo BENCH_FAILED $cfg; tail -5 "$OUT/bench_$cfg.err"; exit 1; }
+  timeout -k 10 400 python -u bench.py --full --config $cfg --steps 1 --warmup 1 > "$OUT/bench_$cfg.json" 2> "$OUT/bench_$cfg.err" || { echo BENCH_FAILED $cfg; tail -5 "$OUT/bench_$cfg.err"; exit 1; }
   echo "done $cfg"; cat "$OUT/bench_$cfg.json"
 done
 echo OBCA_FINAL_DONE

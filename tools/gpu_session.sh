@@ -7,7 +7,7 @@
 # steps:
 #   tests[:K]                pytest -m gpu (optionally -k K), log OUT/tests.log
 #   smoke                    __graft_entry__.smoke()
-#   bench:CFG[:ARGS]         python bench.py --config CFG ARGS (ARGS: comma-separated, e.g. --steps,5) -> OUT/bench_CFG.json
+#   bench:CFG[:ARGS]         python bench.py --full --config CFG ARGS (ARGS: comma-separated, e.g. --steps,5) -> OUT/bench_CFG.json
 #   ab:CFG:ROUNDS:N1=SO1,..[:ARGS]  alternating rounds of bench CFG over builds (TTMPC_LIB=SO; empty SO = in-tree)
 #   prof:CFG[:ARGS]          rocprofv3 --kernel-trace --stats of bench CFG -> OUT/prof_CFG/
 #   pmc:CFG:NAME:CTR[,CTR]   one rocprofv3 --pmc pass of bench CFG (one counter group per pass) -> OUT/pmc_CFG/NAME/
@@ -41,7 +41,7 @@ for step in "$@"; do
     bench)
       j="$OUT/bench_$a1.json"
       n=2; while [ -e "$j" ]; do j="$OUT/bench_${a1}_$n.json"; n=$((n + 1)); done
-      timeout -k 10 600 python -u bench.py --config "$a1" $(args "$a2") > "$j" 2> "${j%.json}.err" || fail "$step" "${j%.json}.err"
+      timeout -k 10 600 python -u bench.py --full --config "$a1" $(args "$a2") > "$j" 2> "${j%.json}.err" || fail "$step" "${j%.json}.err"
       cat "$j" ;;
     ab)
       for r in $(seq 1 "$a2"); do
