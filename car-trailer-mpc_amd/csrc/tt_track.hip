@@ -33,6 +33,9 @@
 // a second life (their first owner is dead over that span of the iteration):
 //   linearise .. Riccati   30-36 curvature W (7 nnz)          [dX is produced by the forward sweep]
 //   linearise .. ric_prep  82-89 Sigma = zL/sL + zU/sU, 90-97 dB = 1/sU - 1/sL   [P_k: Riccati]
+//                          (not in the register-carried builds -- one wave per SIMD, N = 20, 30, 40 and the all-LDS
+//                          N = 50 -- which hand Sigma and dB to phase_ric_tail in registers, see struct Carry; they
+//                          do not use the Y+ rows either: y+ goes from phase_step to phase_update in registers)
 //   ric_prep .. Riccati    110-115 diag(Sigma) + diag(W), 116-117 Sigma_u      [dX_soc: SOC]
 //                          38-43 b^ = -c_{k+1}                                  [Y+: step]
 //   trial .. SOC forward   110-115 c(trial) / c_soc                             [dX_soc: SOC forward]
@@ -84,7 +87,9 @@ constexpr int rKF = 80, rPS = 82, rPV = 104, rDXS = 110;
 static_assert(rDXS + 8 == kRowsPerStage, "stage record");
 static_assert(rDXS - rPS == kGlobalRows, "the HBM band of the kPG builds: P, spare, p (overlay Sigma, dB)");
 // second lives (see the LDS map): curvature, Sigma, dB from the linearisation to the Riccati sweep; the
-// Riccati operands diag(Sigma) + diag(W), Sigma_u and b^ = -c_{k+1} (stage k); the trial residual c
+// Riccati operands diag(Sigma) + diag(W), Sigma_u and b^ = -c_{k+1} (stage k); the trial residual c.
+// The Sigma / dB overlay (rSG, rDB) is used by the generic builds (NS = 0), the two-wave builds and the N = 50 HBM-band
+// build (where it lies in HBM); the register-carried builds (struct Carry) neither write nor read it.
 constexpr int rWC = rDX, rSG = rPS, rDB = rPS + 8, rHD = rDXS, rSGU = rDXS + 6, rBH = rYP, rCT = rDXS;
 // the shifted input gradient g_u' of the Newton sweep (ric_prep .. Riccati) in the b^4, b^5 rows (see gu_shift)
 constexpr int rGU = rBH + 4;
@@ -213,6 +218,27 @@ __device__ __forceinline__ double psel(bool p, double a, double b) {
     asm("" : "+v"(a), "+v"(b));
     return p ? b : a;
 }
+
+// a value the compiler cannot look through: a product made opaque here is not contracted into a later add, so a value
+// that used to reach its consumer through LDS keeps the rounding it had there
+__device__ __forceinline__ double opq(double a) {
+    asm("" : "+v"(a));
+    return a;
+}
+
+// Register-carried stage state (the stage-unrolled one-wave builds: Ctx::kLF, 0 < NS < W).  There a lane owns the same
+// variables of the same stage for the whole solve -- slot t is variable 2t + part in the lane-pair builds (t = 0..3),
+// variable t in the one-stage-per-lane builds (t = 0..7) -- so the stage-parallel passes hand them on in registers
+// instead of through LDS: the point x, z_L, z_U, the slacks x - lb, ub - x and their reciprocals (primed once after the
+// load, then left by phase_update at the new point), the step d and the lane's y+ rows (phase_step -> phase_update), and
+// the Riccati operands of phase_linearize (-> phase_ric_tail).  The values are the ones the LDS rows held (the same
+// expressions on the same operands), so these builds stay bitwise the two-wave builds, which keep the round trips.
+// Every index is a compile-time constant after unrolling (a run-time index would send the arrays to scratch).
+struct Carry {
+    double x[8], zl[8], zu[8], sl[8], su[8], rl[8], ru[8];
+    double d[8], yp[6];
+    double gf[8], sg[8], db[8], wd[6], cn[6];  // grad F, Sigma, dB, diag of the curvature, c_{k+1}
+};
 
 // sum of logs as log(prod of mantissas) + (sum of exponents) ln 2: one log per stage instead of 16
 struct LogSum {
@@ -428,8 +454,8 @@ struct Lin {
 
 // ============ linearise at the current point (stage-parallel) ============
 // f, dt*J, curvature, constraint residual c, grad F, Sigma, dB, and the optimality / merit pieces.
-template <int BM>
-__device__ __forceinline__ Lin phase_linearize(const Ctx<BM>& c) {
+template <int BM, bool CR>
+__device__ __forceinline__ Lin phase_linearize(const Ctx<BM>& c, Carry& cy) {
     const int N = c.N;
     double dinf = 0.0, pinf = 0.0, zmx = -INFINITY, zmn = INFINITY, sy = 0.0, sz = 0.0, cost = 0.0, th = 0.0,
            logs = 0.0;
@@ -445,17 +471,11 @@ __device__ __forceinline__ Lin phase_linearize(const Ctx<BM>& c) {
             // Every LDS read of the stage is issued before the pass's first store: a read queued behind a store waits
             // for it, and the per-variable load -> compute -> store order made the variable loop a chain of twelve LDS
             // round trips (SUBSTAMP census, profiles/r05/track_ab/).  The arithmetic is unchanged (bitwise).
-            double zl[4] = {0, 0, 0, 0}, zu[4] = {0, 0, 0, 0}, lbv[4] = {0, 0, 0, 0}, ubv[4] = {0, 0, 0, 0};
+            // The lane's own variables, multipliers, slacks and slack reciprocals come from the carried state (a lane-pair
+            // build is always a carried build); LDS serves what the partner and the next stage own.
             double qw[3], xi0[3] = {0, 0, 0}, xn[3] = {0, 0, 0};
 #pragma unroll
             for (int i = 0; i < 6; ++i) { x[i] = c.r(rX + i, k); yk[i] = c.r(rY + i, k); }
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const int vb = 2 * t, v = vb + p;
-                if (vb >= 6 && k == N) break;
-                if (c.hl(vb)) { zl[t] = c.r(rZL + v, k); lbv[t] = c.lb(v); }
-                if (c.hu(vb)) { zu[t] = c.r(rZU + v, k); ubv[t] = c.ub(v); }
-            }
 #pragma unroll
             for (int t = 0; t < 3; ++t) qw[t] = c.h(hQW + (2 * t + p) * 7);
             const double rw = c.h(hRW + p * 3);
@@ -476,7 +496,7 @@ __device__ __forceinline__ Lin phase_linearize(const Ctx<BM>& c) {
             if (k == 0) {
 #pragma unroll
                 for (int q = 0; q < 3; ++q) {
-                    const double cc = psel(p, x[2 * q], x[2 * q + 1]) - xi0[q];
+                    const double cc = cy.x[q] - xi0[q];
                     cc0[q] = cc;
                     pinf = fmax(pinf, fabs(cc));
                     th += fabs(cc);
@@ -488,7 +508,7 @@ __device__ __forceinline__ Lin phase_linearize(const Ctx<BM>& c) {
                 SUBSTAMP(c, 5);
 #pragma unroll
                 for (int q = 0; q < 3; ++q) {
-                    const double cc = xn[q] - (psel(p, x[2 * q], x[2 * q + 1]) + c.dt * psel(p, fo[2 * q], fo[2 * q + 1]));
+                    const double cc = xn[q] - (cy.x[q] + c.dt * psel(p, fo[2 * q], fo[2 * q + 1]));
                     cc1[q] = cc;
                     pinf = fmax(pinf, fabs(cc));
                     th += fabs(cc);
@@ -500,42 +520,41 @@ __device__ __forceinline__ Lin phase_linearize(const Ctx<BM>& c) {
             for (int t = 0; t < 4; ++t) {
                 const int vb = 2 * t, v = vb + p;
                 if (vb >= 6 && k == N) break;
-                double gf, g, xv;
+                double gf, g;
+                const double xv = cy.x[t];
                 if (vb < 6) {
-                    const double dxr = psel(p, x[vb], x[vb + 1]) - c.xr(v, k);
+                    const double dxr = xv - c.xr(v, k);
                     gf = qw[t] * dxr;
                     cost += dxr * gf;
                     gf *= 2.0;
                     g = gf + psel(p, yk[vb], yk[vb + 1]);
                     if (k < N) g -= psel(p, y1[vb], y1[vb + 1]) + (p ? colJ(aj, vb + 1, y1, 1) : colJ(aj, vb, y1, 1));
-                    xv = psel(p, x[vb], x[vb + 1]);
                 } else {
-                    const double du = psel(p, u[0], u[1]) - c.ur(p, k);
+                    const double du = xv - c.ur(p, k);
                     gf = rw * du;
                     cost += du * gf;
                     gf *= 2.0;
                     g = gf - c.dt * psel(p, y1[5], y1[4]);
-                    xv = psel(p, u[0], u[1]);
                 }
                 gfv[t] = gf;
                 double sg = 0.0, db = 0.0;
                 if (c.hl(vb)) {
-                    const double sl = xv - lbv[t], rs = frcp(sl);
-                    g -= zl[t];
-                    zmx = fmax(zmx, zl[t] * sl);
-                    zmn = fmin(zmn, zl[t] * sl);
-                    sz += zl[t];
-                    sg += zl[t] * rs;
+                    const double zl = cy.zl[t], sl = cy.sl[t], rs = cy.rl[t];  // sl = xv - lb, rs = frcp(sl)
+                    g -= zl;
+                    zmx = fmax(zmx, zl * sl);
+                    zmn = fmin(zmn, zl * sl);
+                    sz += zl;
+                    sg += zl * rs;
                     db -= rs;
                     if (sl <= 0.0) bad = true; else ls.add(sl);
                 }
                 if (c.hu(vb)) {
-                    const double su = ubv[t] - xv, rs = frcp(su);
-                    g += zu[t];
-                    zmx = fmax(zmx, zu[t] * su);
-                    zmn = fmin(zmn, zu[t] * su);
-                    sz += zu[t];
-                    sg += zu[t] * rs;
+                    const double zu = cy.zu[t], su = cy.su[t], rs = cy.ru[t];  // su = ub - xv, rs = frcp(su)
+                    g += zu;
+                    zmx = fmax(zmx, zu * su);
+                    zmn = fmin(zmn, zu * su);
+                    sz += zu;
+                    sg += zu * rs;
                     db += rs;
                     if (su <= 0.0) bad = true; else ls.add(su);
                 }
@@ -562,20 +581,23 @@ __device__ __forceinline__ Lin phase_linearize(const Ctx<BM>& c) {
 #pragma unroll
                 for (int q = 0; q < 3; ++q) c.r(rCC + 2 * q + p, k + 1) = cc1[q];
             }
+            // grad F, Sigma, dB, the curvature diagonal and c_{k+1} stay in registers for phase_ric_tail (no Sigma / dB rows)
 #pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const int v = 2 * t + p;
-                if (2 * t >= 6 && k == N) break;
-                c.r(rGF + v, k) = gfv[t];
-                c.g(rSG + v, k) = sgv[t];
-                c.g(rDB + v, k) = dbv[t];
-            }
+            for (int t = 0; t < 4; ++t) { cy.gf[t] = gfv[t]; cy.sg[t] = sgv[t]; cy.db[t] = dbv[t]; }
+#pragma unroll
+            for (int q = 0; q < 3; ++q) cy.cn[q] = cc1[q];
+            cy.wd[0] = 0.0;
+            cy.wd[1] = st ? psel(p, wc[w_idx(2, 2)], wc[w_idx(3, 3)]) : 0.0;
+            cy.wd[2] = st ? wc[w_idx(4, 4)] : 0.0;
             SUBSTAMP(c, 6);
             logs += ls.value();
         }
     } else
     for (int k = c.lane; k <= N; k += W) {
-        // as in the lane-pair path: every LDS read of the stage, then the arithmetic, then the stores
+        // as in the lane-pair path: every LDS read of the stage, then the arithmetic, then the stores.  Carried builds:
+        // z, the slacks and the reciprocals come from registers, but the point is still read from LDS -- a variant that
+        // fed the model from the carried x was not bitwise the LDS path at N = 40 and 50 (12 to 31 of 96 hard instances
+        // off in the last bits; presumably the model's products contract differently when their inputs are not loads)
         const bool st = k < N;
         double x[6], u[2] = {0.0, 0.0}, yk[6], y1[6] = {0, 0, 0, 0, 0, 0}, aj[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
         double xn[6] = {0, 0, 0, 0, 0, 0}, cc0[6] = {0, 0, 0, 0, 0, 0}, cc1[6] = {0, 0, 0, 0, 0, 0}, wc[7];
@@ -650,7 +672,9 @@ __device__ __forceinline__ Lin phase_linearize(const Ctx<BM>& c) {
             const double xv = v < 6 ? x[v] : u[v - 6];
             double sg = 0.0, db = 0.0;
             if (c.hl(v)) {
-                const double zl = c.r(rZL + v, k), s = xv - c.lb(v), rs = frcp(s);
+                double zl, s, rs;
+                if constexpr (CR) { zl = cy.zl[v]; s = cy.sl[v]; rs = cy.rl[v]; }
+                else { zl = c.r(rZL + v, k); s = xv - c.lb(v); rs = frcp(s); }
                 g -= zl;
                 zmx = fmax(zmx, zl * s);
                 zmn = fmin(zmn, zl * s);
@@ -660,7 +684,9 @@ __device__ __forceinline__ Lin phase_linearize(const Ctx<BM>& c) {
                 if (s <= 0.0) bad = true; else ls.add(s);
             }
             if (c.hu(v)) {
-                const double zu = c.r(rZU + v, k), s = c.ub(v) - xv, rs = frcp(s);
+                double zu, s, rs;
+                if constexpr (CR) { zu = cy.zu[v]; s = cy.su[v]; rs = cy.ru[v]; }
+                else { zu = c.r(rZU + v, k); s = c.ub(v) - xv; rs = frcp(s); }
                 g += zu;
                 zmx = fmax(zmx, zu * s);
                 zmn = fmin(zmn, zu * s);
@@ -687,12 +713,22 @@ __device__ __forceinline__ Lin phase_linearize(const Ctx<BM>& c) {
 #pragma unroll
             for (int i = 0; i < 6; ++i) c.r(rCC + i, k + 1) = cc1[i];
         }
+        if constexpr (CR) {  // kept in registers for phase_ric_tail (no Sigma / dB rows)
+#pragma unroll
+            for (int v = 0; v < 8; ++v) { cy.gf[v] = gfv[v]; cy.sg[v] = sgv[v]; cy.db[v] = dbv[v]; }
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+                cy.cn[i] = cc1[i];
+                cy.wd[i] = (st && w_idx(i, i) >= 0) ? wc[w_idx(i, i) >= 0 ? w_idx(i, i) : 0] : 0.0;
+            }
+        } else {
 #pragma unroll
         for (int v = 0; v < 8; ++v) {
             if (v >= 6 && k == N) break;
             c.r(rGF + v, k) = gfv[v];
             c.g(rSG + v, k) = sgv[v];
             c.g(rDB + v, k) = dbv[v];
+        }
         }
     }
     } else {
@@ -1015,6 +1051,97 @@ __device__ __forceinline__ void phase_ric_prep(const Ctx<BM>& c) {
     __syncthreads();
 }
 
+// The carried builds' phase_ric_prep: the same operand rows, written by the lanes that produced their sources in
+// phase_linearize, from registers (Carry) -- no Sigma / dB rows, no reads at all but gu_shift's weights.  Each source is
+// made opaque first (opq): the rows' values are the ones phase_ric_prep forms from the stored operands.  Lane pairs:
+// lane `part` writes the rows of its own variables 2t + part and residual rows 2q + part; g_u' needs the partner's input
+// gradient, Sigma_u and c_{k+1}[4 + part], exchanged by the DPP quad swap of stage_trig.
+template <int BM>
+__device__ __forceinline__ void phase_ric_tail(const Ctx<BM>& c, const Carry& cy) {
+    const int N = c.N;
+    if (c.pair) {
+        const int p = c.part(), k = c.k0();
+        const bool st = k < N;
+        double g[4], sg[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            sg[t] = opq(cy.sg[t]);
+            g[t] = opq(cy.gf[t]) + c.mu * opq(cy.db[t]);
+        }
+        const double cq = opq(cy.cn[2]);  // c_{k+1}[4 + part]
+        const double pg = dppd<0xB1>(g[3]), ps = dppd<0xB1>(sg[3]), pc = dppd<0xB1>(cq);
+        if (k <= N) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                if (t == 3 && !st) break;
+                c.r(rGF + 2 * t + p, k) = g[t];
+            }
+            double hd1 = sg[1], hd2 = sg[2];
+            if (st) {
+                hd1 += opq(cy.wd[1]);
+                const double w2 = sg[2] + opq(cy.wd[2]);  // (4, 4): the even lane's; (5, 5) has no curvature
+                hd2 = p ? hd2 : w2;
+            }
+            c.r(rHD + p, k) = sg[0];
+            c.r(rHD + 2 + p, k) = hd1;
+            c.r(rHD + 4 + p, k) = hd2;
+            c.r(rSGU + p, k) = st ? sg[3] : 0.0;
+            if (st) {
+                c.r(rBH + p, k) = -opq(cy.cn[0]);
+                c.r(rBH + 2 + p, k) = -opq(cy.cn[1]);
+                double g0, g1;
+                gu_shift(c, p ? pg : g[3], p ? g[3] : pg, p ? ps : sg[3], p ? sg[3] : ps, p ? pc : cq, p ? cq : pc, 0.0,
+                         g0, g1);
+                c.r(rGU + p, k) = p ? g1 : g0;
+            } else {  // terminal stage: no dynamics, so no curvature
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    if (q == 3 && p) break;
+                    c.r(rWC + 2 * q + p, k) = 0.0;
+                }
+            }
+        }
+    } else {
+        for (int k = c.lane; k <= N; k += W) {
+            const bool st = k < N;
+            double g[8], hd[6];
+#pragma unroll
+            for (int v = 0; v < 8; ++v) g[v] = (v >= 6 && !st) ? 0.0 : opq(cy.gf[v]) + c.mu * opq(cy.db[v]);
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+                double d = opq(cy.sg[i]);
+                if (w_idx(i, i) >= 0 && st) d += opq(cy.wd[i]);
+                hd[i] = d;
+            }
+            const double su0 = st ? opq(cy.sg[6]) : 0.0, su1 = st ? opq(cy.sg[7]) : 0.0;
+#pragma unroll
+            for (int v = 0; v < 8; ++v) {
+                if (v >= 6 && !st) break;
+                c.r(rGF + v, k) = g[v];
+            }
+#pragma unroll
+            for (int i = 0; i < 6; ++i) c.r(rHD + i, k) = hd[i];
+            c.r(rSGU, k) = su0;
+            c.r(rSGU + 1, k) = su1;
+            if (st) {
+                double cn[6];
+#pragma unroll
+                for (int i = 0; i < 6; ++i) cn[i] = opq(cy.cn[i]);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) c.r(rBH + i, k) = -cn[i];
+                double g0, g1;
+                gu_shift(c, g[6], g[7], su0, su1, cn[4], cn[5], 0.0, g0, g1);
+                c.r(rGU, k) = g0;
+                c.r(rGU + 1, k) = g1;
+            } else {  // terminal stage: no dynamics, so no curvature
+#pragma unroll
+                for (int i = 0; i < 7; ++i) c.r(rWC + i, k) = 0.0;
+            }
+        }
+    }
+    __syncthreads();
+}
+
 // Per-lane slots of entry (i, j): D[m][j] (m = 0..5) for PA, D[l][i] for F, H^[i][j], store rows.
 struct EpMap {
     int dj[4], di[4];
@@ -1301,8 +1428,10 @@ struct StepInfo {
 };
 
 // ============ new multipliers y+ = -(P dx + p), step bounds, merit slope (stage-parallel) ============
-template <int BM>
-__device__ __forceinline__ StepInfo phase_step(const Ctx<BM>& c, int dzr, bool primal_pieces) {
+// CR (carried builds): the point, the multipliers, the slacks and their reciprocals come from the carried state; the step
+// d and the lane's y+ rows stay there for phase_update (no y+ rows in LDS: nothing else reads them).
+template <int BM, bool CR>
+__device__ __forceinline__ StepInfo phase_step(const Ctx<BM>& c, Carry& cy, int dzr, bool primal_pieces) {
     const int N = c.N;
     double ap = 1.0, az = 1.0, Dg = 0.0, rel = 0.0;
     const int p = c.part();
@@ -1326,6 +1455,22 @@ __device__ __forceinline__ StepInfo phase_step(const Ctx<BM>& c, int dzr, bool p
             if (c.pair && t >= 4) break;
             const int vb = c.pair ? 2 * t : t, v = vb + p;
             if (vb >= 6 && k == N) break;
+            if constexpr (CR) {
+                const double d = c.r(dzr + v, k), xv = cy.x[t];
+                cy.d[t] = d;
+                Dg += c.gr(v, k) * d;
+                rel = fmax(rel, fabs(d) * frcp(1.0 + fabs(xv)));
+                if (c.hl(vb)) {
+                    const double s = cy.sl[t], rs = cy.rl[t], zl = cy.zl[t];
+                    ftb(s, d, c.tau, ap);
+                    ftb(zl, (c.mu - zl * d) * rs - zl, c.tau, az);
+                }
+                if (c.hu(vb)) {
+                    const double s = cy.su[t], rs = cy.ru[t], zu = cy.zu[t];
+                    ftb(s, -d, c.tau, ap);
+                    ftb(zu, (c.mu + zu * d) * rs - zu, c.tau, az);
+                }
+            } else {
             const double d = c.r(dzr + v, k), xv = c.r(rX + v, k);
             Dg += c.gr(v, k) * d;
             rel = fmax(rel, fabs(d) * frcp(1.0 + fabs(xv)));  // only tested against 1e-15
@@ -1339,8 +1484,15 @@ __device__ __forceinline__ StepInfo phase_step(const Ctx<BM>& c, int dzr, bool p
                 ftb(s, -d, c.tau, ap);
                 ftb(zu, (c.mu + zu * d) * rs - zu, c.tau, az);
             }
+            }
         }
-        if constexpr (Ctx<BM>::kLF)
+        if constexpr (CR) {
+#pragma unroll
+            for (int q = 0; q < 6; ++q) {
+                if (c.pair && q >= 3) break;
+                cy.yp[q] = yp[q];
+            }
+        } else if constexpr (Ctx<BM>::kLF)
 #pragma unroll
             for (int q = 0; q < 6; ++q) {
                 if (c.pair && q >= 3) break;
@@ -1553,9 +1705,74 @@ __device__ __forceinline__ bool filter_ok(const Ctx<BM>& c, int nf, const Trial&
 }
 
 // ============ accept the step (stage-parallel) ============
-template <int BM>
-__device__ __forceinline__ void phase_update(const Ctx<BM>& c, int dzr, double alpha, double az) {
-    if constexpr (Ctx<BM>::kLF) {
+// CR (carried builds): everything but y comes from the carried state, which leaves with the new point, the new
+// multipliers and the slacks and reciprocals at the new point (rn = mu / s_new needs them anyway) for the next
+// linearisation; X, z_L, z_U and Y are stored as ever (the partner lane, the trial and the output copy read them).
+template <int BM, bool CR>
+__device__ __forceinline__ void phase_update(const Ctx<BM>& c, Carry& cy, int dzr, double alpha, double az) {
+    if constexpr (CR) {
+    const int N = c.N, p = c.part();
+    for (int k = c.k0(); k <= N; k += c.kst()) {
+        double ynv[6], lbv[8], ubv[8];
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+            if (c.pair && q >= 3) break;
+            ynv[q] = c.r(rY + (c.pair ? 2 * q + p : q), k);
+        }
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            if (c.pair && t >= 4) break;
+            const int vb = c.pair ? 2 * t : t, v = vb + p;
+            if (vb >= 6 && k == N) break;
+            if (c.hl(vb)) lbv[t] = c.lb(v);
+            if (c.hu(vb)) ubv[t] = c.ub(v);
+        }
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            if (c.pair && t >= 4) break;
+            const int vb = c.pair ? 2 * t : t;
+            if (vb >= 6 && k == N) break;
+            const double d = cy.d[t], xo = cy.x[t], xn = xo + alpha * d;
+            if (c.hl(vb)) {
+                const double zl = cy.zl[t], rs = cy.rl[t];
+                const double sn = xn - lbv[t], rsn = frcp(sn);
+                const double znew = zl + az * ((c.mu - zl * d) * rs - zl), rn = c.mu * rsn;
+                cy.zl[t] = fmax(fmin(znew, 1e10 * rn), 1e-10 * rn);  // kappa_sigma = 1e10
+                cy.sl[t] = sn;
+                cy.rl[t] = rsn;
+            }
+            if (c.hu(vb)) {
+                const double zu = cy.zu[t], rs = cy.ru[t];
+                const double sn = ubv[t] - xn, rsn = frcp(sn);
+                const double znew = zu + az * ((c.mu + zu * d) * rs - zu), rn = c.mu * rsn;
+                cy.zu[t] = fmax(fmin(znew, 1e10 * rn), 1e-10 * rn);
+                cy.su[t] = sn;
+                cy.ru[t] = rsn;
+            }
+            cy.x[t] = xn;
+        }
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+            if (c.pair && q >= 3) break;
+            const double y = ynv[q];
+            ynv[q] = y + alpha * (cy.yp[q] - y);
+        }
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            if (c.pair && t >= 4) break;
+            const int vb = c.pair ? 2 * t : t, v = vb + p;
+            if (vb >= 6 && k == N) break;
+            if (c.hl(vb)) c.r(rZL + v, k) = cy.zl[t];
+            if (c.hu(vb)) c.r(rZU + v, k) = cy.zu[t];
+            c.r(rX + v, k) = cy.x[t];
+        }
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+            if (c.pair && q >= 3) break;
+            c.r(rY + (c.pair ? 2 * q + p : q), k) = ynv[q];
+        }
+    }
+    } else if constexpr (Ctx<BM>::kLF) {
     const int N = c.N, p = c.part();
     for (int k = c.k0(); k <= N; k += c.kst()) {
         // every LDS read of the stage before its stores (a read queued behind a store waits for it)
@@ -1804,6 +2021,33 @@ __device__ __forceinline__ void phase_init(const Ctx<BM>& c) {
     __syncthreads();
 }
 
+// Prime the carried state from the initial point in LDS (whichever of phase_load_init_reg and phase_load + phase_init
+// wrote it): the lane's own x, z_L, z_U, and the slacks and reciprocals phase_linearize would form from them.
+template <int BM>
+__device__ __forceinline__ void phase_prime(const Ctx<BM>& c, Carry& cy) {
+    const int N = c.N, p = c.part();
+    for (int k = c.k0(); k <= N; k += c.kst()) {
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            if (c.pair && t >= 4) break;
+            const int vb = c.pair ? 2 * t : t, v = vb + p;
+            if (vb >= 6 && k == N) break;
+            const double xv = c.r(rX + v, k);
+            cy.x[t] = xv;
+            if (c.hl(vb)) {
+                cy.zl[t] = c.r(rZL + v, k);
+                cy.sl[t] = xv - c.lb(v);
+                cy.rl[t] = frcp(cy.sl[t]);
+            }
+            if (c.hu(vb)) {
+                cy.zu[t] = c.r(rZU + v, k);
+                cy.su[t] = c.ub(v) - xv;
+                cy.ru[t] = frcp(cy.su[t]);
+            }
+        }
+    }
+}
+
 template <int BM, int OCC, int NS>
 __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(OCC))) void track_kernel(TrackArgs a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -1839,6 +2083,11 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(OCC))) void t
     c.Mh = a.Mh;
     c.mu = 0.1;
     c.tau = fmax(0.99, 1.0 - c.mu);
+    // the carried builds: one wave per SIMD (room in the register file) and a lane that keeps its stage for the whole solve
+    // (not the HBM-band build: it already fills the 512-register file and spills; carrying the state there took its
+    // scratch from 168 to 916 bytes, so it keeps the LDS / HBM round trips)
+    constexpr bool CR = Ctx<BM>::kLF && !Ctx<BM>::kPG && NS > 0 && NS < W;
+    Carry cy = {};
 #ifdef TT_STAMPS
     Stamps stamps;
     stamps.begin();
@@ -1865,6 +2114,7 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(OCC))) void t
     double E0 = INFINITY;
     if (!infeas) {
         if (!fused) phase_init(c);
+        if constexpr (CR) phase_prime(c, cy);
         STAMP(PH_LOAD);
         double dw_last = 0.0, th_max = 0.0, th_min = 0.0;
         int acc_count = 0, nf = 0;
@@ -1873,7 +2123,7 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(OCC))) void t
         // IPOPT's barrier floor (MonotoneMuUpdate::CalcNewMuAndTau): min(tol, compl_inf_tol) / (barrier_tol_factor + 1)
         const double mu_floor = fmin(a.tol, kComplInfTol) / 11.0, mu_floor_test = mu_floor * 1.0000001;
         for (iter = 0;; ++iter) {
-            const Lin e = phase_linearize(c);
+            const Lin e = phase_linearize<BM, CR>(c, cy);
             STAMP(PH_LIN);
             if (!isfinite(e.dinf) || !isfinite(e.pinf)) { status = 4; break; }
             // IPOPT's s_d, s_c (s_max = 100) as reciprocals: E = max(dinf / s_d, pinf, compl / s_c)
@@ -1908,7 +2158,8 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(OCC))) void t
             // Newton step: Riccati with inertia correction
             double dw = 0.0;
             bool ok = false;
-            phase_ric_prep(c);
+            if constexpr (CR) phase_ric_tail(c, cy);
+            else phase_ric_prep(c);
             for (int attempt = 0; attempt < 30; ++attempt) {
                 COUNT(PH_NRIC);
                 if (dw > 0.0) ric_gu_shift(c, dw);
@@ -1922,7 +2173,7 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(OCC))) void t
             STAMP(PH_RIC);
             phase_forward<BM, NS>(c, rCC, rBH, rDX);
             STAMP(PH_FWD);
-            const StepInfo si = phase_step(c, rDX, true);
+            const StepInfo si = phase_step<BM, CR>(c, cy, rDX, true);
             STAMP(PH_STEP);
             // IPOPT filter line search (Waechter & Biegler 2006, IPOPT defaults) with one second-order
             // correction; theta / phi_mu of the current point come from the linearisation pass
@@ -1955,7 +2206,7 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(OCC))) void t
                         accepted = 2;
                         soc = true;
                         alpha = as;
-                        az = phase_step(c, rDXS, false).az;  // y+ and dual step bound of the corrected step
+                        az = phase_step<BM, CR>(c, cy, rDXS, false).az;  // y+ and dual step bound of the corrected step
                         break;
                     }
                 }
@@ -1983,7 +2234,7 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(OCC))) void t
                 ++nf;
                 __syncthreads();
             }
-            phase_update(c, soc ? rDXS : rDX, alpha, az);
+            phase_update<BM, CR>(c, cy, soc ? rDXS : rDX, alpha, az);
             // the next linearisation point is the last trial point: reuse its trig (wave-uniform test)
             c.t_ok = c.regref && alpha == c.t_alpha && (soc ? rDXS : rDX) == c.t_dz;
             STAMP(PH_UPDATE);
