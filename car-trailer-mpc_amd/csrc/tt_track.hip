@@ -1176,7 +1176,9 @@ struct EpOps {
     double dj[4], di[4], h, sgu0, sgu1, gj0, gj1, gi0, gi1;
 };
 // in two halves: A (D[.][j], Sigma_u) is issued behind the P-row reads, B (D[.][i], H^, g_u) behind the
-// PA-column reads, which spreads the LDS queue over the stage (tools/ubench_riccati.hip: -44 cycles/stage)
+// PA-column reads, which spreads the LDS queue over the stage (tools/ubench_riccati.hip: -44 cycles/stage).
+// Both halves are loads only: o.h is the raw H^ row, the stage adds the lane's constant part (2 Qw, + dw on the diagonal)
+// where it uses it.
 template <int BM>
 __device__ __forceinline__ void ep_ops_a(const Ctx<BM>& c, const EpMap& m, int k, EpOps& o) {
 #pragma unroll
@@ -1185,20 +1187,20 @@ __device__ __forceinline__ void ep_ops_a(const Ctx<BM>& c, const EpMap& m, int k
     o.sgu1 = c.r(rSGU + 1, k);
 }
 template <int BM>
-__device__ __forceinline__ void ep_ops_b(const Ctx<BM>& c, const EpMap& m, int k, double dw, EpOps& o) {
+__device__ __forceinline__ void ep_ops_b(const Ctx<BM>& c, const EpMap& m, int k, EpOps& o) {
 #pragma unroll
     for (int t = 0; t < 4; ++t) o.di[t] = c.rl(m.di[t], k);
-    o.h = m.q2 + m.dg * dw + c.rl(m.hs, k);
+    o.h = c.rl(m.hs, k);
     o.gj0 = c.rl(m.gj0, k);
     o.gj1 = c.rl(m.gj1, k);
     o.gi0 = c.rl(m.gi0, k);
     o.gi1 = c.rl(m.gi1, k);
 }
 template <int BM>
-__device__ __forceinline__ EpOps ep_ops(const Ctx<BM>& c, const EpMap& m, int k, double dw) {
+__device__ __forceinline__ EpOps ep_ops(const Ctx<BM>& c, const EpMap& m, int k) {
     EpOps o;
     ep_ops_a(c, m, k, o);
-    ep_ops_b(c, m, k, dw, o);
+    ep_ops_b(c, m, k, o);
     return o;
 }
 
@@ -1224,7 +1226,8 @@ __device__ __forceinline__ bool phase_riccati(const Ctx<BM>& c, double dw) {
     const int sw_i = i & 4, sw_j = j & 4;
     const int pf_own = 8 * i + (j ^ sw_i);  // this lane's P^ entry
     // terminal P^_N = H^_N (no dynamics): padded lanes hold exact zeros
-    double Pij = m.q2 + m.dg * dw + c.rl(m.hs, N);
+    const double hb = m.q2 + m.dg * dw;  // the lane's constant part of H^[i][j]
+    double Pij = hb + c.rl(m.hs, N);
     PF[pf_own] = Pij;
     asm volatile("" ::: "memory");
     if constexpr (Ctx<BM>::kPG) {
@@ -1251,11 +1254,8 @@ __device__ __forceinline__ bool phase_riccati(const Ctx<BM>& c, double dw) {
         __builtin_amdgcn_sched_barrier(0);
         ep_ops_a(c, m, kn, nx);  // next stage's operands, first half
         __builtin_amdgcn_sched_barrier(0);
-        const double h00 = r00 + o.sgu0 + dw + dt2 * p5.y, h01 = r01 + dt2 * p5.x, h11 = r11 + o.sgu1 + dw + dt2 * p44;
-        const double det = h00 * h11 - h01 * h01;
-        pd = pd & (h00 > 0.0) & (h11 > 0.0) & (det > 1e-13 * h00 * h11);
-        const double id = frcp(det), i00 = h11 * id, i01 = -h01 * id, i11 = h00 * id;
-        // PA[i][j] = P[i][j] + sum_{m<4} P[i][m] D[m][j]
+        // PA[i][j] = P[i][j] + sum_{m<4} P[i][m] D[m][j].  First behind the P-row reads: the PA tile's write and its column
+        // reads are the next link of the stage-to-stage chain, and nothing else may issue ahead of them.
         double pa = fma(r01v.x, o.dj[0], Pij), pb = r01v.y * o.dj[1];
         pa = fma(r23v.x, o.dj[2], pa);
         pb = fma(r23v.y, o.dj[3], pb);
@@ -1265,11 +1265,19 @@ __device__ __forceinline__ bool phase_riccati(const Ctx<BM>& c, double dw) {
         // column j of PA (rows 0..5; rows 4, 5 also give G[.][j]) and G[.][i]
         const double2 c01 = ld2(PT + 8 * j + sw_j), c23 = ld2(PT + 8 * j + (2 ^ sw_j)), c45 = ld2(PT + 8 * j + (4 ^ sw_j));
         const double2 gi = ld2(PT + 8 * i + (4 ^ sw_i));  // PA[4][i], PA[5][i]
-        // next stage's operands, second half: issued behind the tile reads (LDS serves a wave in order)
+        // next stage's operands, second half: behind the tile reads (LDS serves a wave in order); the scheduler is free to
+        // place them anywhere below this fence (pinning them here, ahead of the arithmetic, measured slower)
         __builtin_amdgcn_sched_barrier(0);
-        ep_ops_b(c, m, kn, dw, nx);
+        ep_ops_b(c, m, kn, nx);
+        // H_uu and its inverse (wave-uniform, needed only for M below): a chain of about seventeen dependent FP64
+        // instructions that has no part in PA, so it runs here, in the shadow of the PA tile's round trip through LDS,
+        // instead of ahead of the tile write (where the source order used to put it: -12 cycles per stage in the kernel)
+        const double h00 = r00 + o.sgu0 + dw + dt2 * p5.y, h01 = r01 + dt2 * p5.x, h11 = r11 + o.sgu1 + dw + dt2 * p44;
+        const double det = h00 * h11 - h01 * h01;
+        pd = pd & (h00 > 0.0) & (h11 > 0.0) & (det > 1e-13 * h00 * h11);
+        const double id = frcp(det), i00 = h11 * id, i01 = -h01 * id, i11 = h00 * id;
         // F[i][j] = PA[i][j] + sum_{l<4} D[l][i] PA[l][j] + H^[i][j]
-        double fa = fma(o.di[0], c01.x, PAij + o.h), fb = o.di[1] * c01.y;
+        double fa = fma(o.di[0], c01.x, PAij + (hb + o.h)), fb = o.di[1] * c01.y;
         fa = fma(o.di[2], c23.x, fa);
         fb = fma(o.di[3], c23.y, fb);
         const double F = fa + fb;
@@ -1289,7 +1297,7 @@ __device__ __forceinline__ bool phase_riccati(const Ctx<BM>& c, double dw) {
         }
     };
     // two stages per trip with ping-pong operand buffers (no register copies between stages)
-    EpOps oa = ep_ops(c, m, N - 1, dw), ob;
+    EpOps oa = ep_ops(c, m, N - 1), ob;
     if constexpr (NS > 0) {
 #pragma unroll
         for (int k = NS - 1; k >= 1; k -= 2) {

@@ -68,10 +68,146 @@ __device__ __forceinline__ void r5_ops_b(const Ctx<UB_BM>& c, const R5Map& m, in
     o.gi1 = c.r(m.gi1, k);
 }
 
+// Round 8: private copies of the shipped four-term stage, for the A/B of its schedule in one binary (results and what
+// shipped: DESIGN.md section 3, profiles/r08_riccati_reads/).  V = 60 is the stage as round 7 shipped it, V = 66 the stage
+// as phase_riccati has it now (PAF alone).
+//   PIN   = false: no fence behind the second prefetch half, which the compiler then sinks below the F, G, M arithmetic
+//           to just ahead of the P^ write; true: fenced there, and the last subtraction and the P^ write fenced off too
+//   GSEL  = g_u' as one wave-uniform b128 read and four selects instead of four reads that return the zero pad to most lanes
+//   DEFER = the factor-row store of stage k issued one stage later, behind the first prefetch half of stage k - 1
+//   PAF   = PA and its tile write first, the H_uu inverse (det, rcp, two Newton steps) behind the tile reads
+//   AF    = the fences around the first prefetch half (false: the compiler places it); AB = both halves behind the PA reads
+template <bool PIN, bool GSEL, bool DEFER, bool PAF, bool AF = true, bool AB = false>
+__device__ __forceinline__ bool ub_sweep4(const Ctx<UB_BM>& c, double dw) {
+    constexpr int NS = UB_N;
+    const int N = c.N, i = c.lane >> 3, j = c.lane & 7;
+    EpMap m;
+    m.init(i, j, c.sm + hQW);
+    const double dt = c.dt, dt2 = dt * dt;
+    const double r00 = 2.0 * c.h(hRW), r01 = 2.0 * c.h(hRW + 1), r11 = 2.0 * c.h(hRW + 3);
+    double* PF = c.sm + hPF;
+    double* PT = c.sm + hPT;
+    const int sw_i = i & 4, sw_j = j & 4;
+    const int pf_own = 8 * i + (j ^ sw_i);
+    const double hb = m.q2 + m.dg * dw;
+    double Pij = hb + c.rl(m.hs, N);
+    PF[pf_own] = Pij;
+    asm volatile("" ::: "memory");
+    pstore(c, m.ps >= 0, m.ps, N, Pij);
+    bool pd = true;
+    const bool own_p = m.ps >= 0;
+    const bool k_row = i >= 6 && j < 7;
+    const int st_row = own_p ? m.ps : k_row ? (j < 6 ? rK + 6 * (i - 6) + j : rKF + (i - 6)) : rDX + 7;
+    double sv = 0.0;  // DEFER: the store value of the stage before
+    struct Ops {
+        double dj[4], di[4], h, sgu0, sgu1, gj0, gj1, gi0, gi1;
+        double2 gu;
+    };
+    auto ops_a = [&](int k, Ops& o) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) o.dj[t] = c.rl(m.dj[t], k);
+        o.sgu0 = c.r(rSGU, k);
+        o.sgu1 = c.r(rSGU + 1, k);
+    };
+    auto ops_b = [&](int k, Ops& o) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) o.di[t] = c.rl(m.di[t], k);
+        o.h = c.rl(m.hs, k);
+        if constexpr (GSEL) {
+            o.gu = ld2(&c.rl(rGU, k));
+        } else {
+            o.gj0 = c.rl(m.gj0, k);
+            o.gj1 = c.rl(m.gj1, k);
+            o.gi0 = c.rl(m.gi0, k);
+            o.gi1 = c.rl(m.gi1, k);
+        }
+    };
+    auto stage = [&](int k, const Ops& o, Ops& nx, int kn) {
+        const double2 r01v = ld2(PF + 8 * i + sw_i), r23v = ld2(PF + 8 * i + (2 ^ sw_i));
+        const double2 p5 = ld2(PF + 40);
+        const double p44 = PF[32];
+        if constexpr (AF) __builtin_amdgcn_sched_barrier(0);
+        if constexpr (!AB) ops_a(kn, nx);
+        if constexpr (DEFER) {
+            if (k < NS - 1) c.r(st_row, k + 1) = sv;
+        }
+        if constexpr (AF) __builtin_amdgcn_sched_barrier(0);
+        double i00, i01, i11;
+        auto huu = [&]() {
+            const double h00 = r00 + o.sgu0 + dw + dt2 * p5.y, h01 = r01 + dt2 * p5.x, h11 = r11 + o.sgu1 + dw + dt2 * p44;
+            const double det = h00 * h11 - h01 * h01;
+            pd = pd & (h00 > 0.0) & (h11 > 0.0) & (det > 1e-13 * h00 * h11);
+            const double id = frcp(det);
+            i00 = h11 * id, i01 = -h01 * id, i11 = h00 * id;
+        };
+        if constexpr (!PAF) huu();
+        double pa = fma(r01v.x, o.dj[0], Pij), pb = r01v.y * o.dj[1];
+        pa = fma(r23v.x, o.dj[2], pa);
+        pb = fma(r23v.y, o.dj[3], pb);
+        const double PAij = pa + pb;
+        PT[8 * j + (i ^ sw_j)] = PAij;
+        asm volatile("" ::: "memory");
+        const double2 c01 = ld2(PT + 8 * j + sw_j), c23 = ld2(PT + 8 * j + (2 ^ sw_j)), c45 = ld2(PT + 8 * j + (4 ^ sw_j));
+        const double2 gi = ld2(PT + 8 * i + (4 ^ sw_i));
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (AB) ops_a(kn, nx);
+        ops_b(kn, nx);
+        if constexpr (PIN) __builtin_amdgcn_sched_barrier(0);
+        if constexpr (PAF) huu();  // H_uu^-1 in the shadow of the PA tile's round trip, not ahead of its write
+        double gj0, gj1, gi0, gi1;
+        if constexpr (GSEL) {
+            gj0 = j == 6 ? o.gu.x : 0.0;
+            gj1 = j == 6 ? o.gu.y : 0.0;
+            gi0 = i == 6 ? o.gu.x : 0.0;
+            gi1 = i == 6 ? o.gu.y : 0.0;
+        } else {
+            gj0 = o.gj0, gj1 = o.gj1, gi0 = o.gi0, gi1 = o.gi1;
+        }
+        double fa = fma(o.di[0], c01.x, PAij + (hb + o.h)), fb = o.di[1] * c01.y;
+        fa = fma(o.di[2], c23.x, fa);
+        fb = fma(o.di[3], c23.y, fb);
+        const double F = fa + fb;
+        const double g0j = fma(dt, c45.y, gj0), g1j = fma(dt, c45.x, gj1);
+        const double g0i = fma(dt, gi.y, gi0), g1i = fma(dt, gi.x, gi1);
+        const double m0 = fma(i00, g0j, i01 * g1j), m1 = fma(i01, g0j, i11 * g1j);
+        double kv = i == 6 ? -m0 : -m1;
+        const double gm = fma(g0i, m0, g1i * m1);
+        if constexpr (PIN) asm volatile("" : "+v"(kv));
+        if constexpr (PIN) __builtin_amdgcn_sched_barrier(0);
+        Pij = F - gm;
+        PF[pf_own] = Pij;
+        asm volatile("" ::: "memory");
+        if constexpr (DEFER) sv = own_p ? Pij : kv;
+        else c.r(st_row, k) = own_p ? Pij : kv;
+    };
+    Ops oa, ob;
+    ops_a(N - 1, oa);
+    ops_b(N - 1, oa);
+#pragma unroll
+    for (int k = NS - 1; k >= 1; k -= 2) {
+        stage(k, oa, ob, k - 1);
+        stage(k - 1, ob, oa, k >= 2 ? k - 2 : 0);
+    }
+    if constexpr (DEFER) c.r(st_row, 0) = sv;
+    __syncthreads();
+    return pd;
+}
+
 template <int V>
 __device__ __forceinline__ bool ub_riccati(const Ctx<UB_BM>& c, double dw) {
     if constexpr (V == 9) {
         return phase_riccati<UB_BM, UB_N>(c, dw);
+    } else if constexpr (V == 69) {
+        return ub_sweep4<false, true, false, true>(c, dw);          // PA first, g select
+    } else if constexpr (V == 70) {
+        return ub_sweep4<false, false, false, true, false>(c, dw);  // PA first, first half unfenced
+    } else if constexpr (V == 71) {
+        return ub_sweep4<false, false, false, true, true, true>(c, dw);  // PA first, both halves behind the PA reads
+    } else if constexpr (V >= 60) {
+        // 60 round 7 | 61 fenced | 62 fenced, g select | 63 fenced, late store | 64 fenced, both
+        // 65 late store | 66 PA first | 67 PA first, late store | 68 fenced, PA first, late store
+        return ub_sweep4<(V >= 61 && V <= 64) || V == 68, (V == 62 || V == 64), (V == 63 || V == 64 || V == 65 || V >= 67),
+                         (V >= 66)>(c, dw);
     } else {
         constexpr int NS = UB_N;
         constexpr bool full = V == 50;
@@ -159,7 +295,7 @@ __global__ __launch_bounds__(64) void ub_kernel(int reps, unsigned long long* ou
     if (c.lane < 36) sm[hQW + c.lane] = (c.lane % 7 == 0) ? 1.0 : 0.0;
     if (c.lane < 4) sm[hRW + c.lane] = (c.lane == 0 || c.lane == 3) ? 10.0 : 0.0;
     for (int k = 0; k <= UB_N; ++k)
-        for (int q = c.lane; q < 6; q += 64) sm[HEAD + k * SR + rHD + q] = 2.0;  // diagonal Hessian rows
+        for (int q = c.lane; q < 7; q += 64) sm[HEAD + k * SR + (q < 6 ? rHD + q : PAD)] = q < 6 ? 2.0 : 0.0;  // diagonal Hessian rows, zero pad
     __syncthreads();
     bool ok = true;
     const unsigned long long t0 = __builtin_amdgcn_s_memtime();
@@ -266,11 +402,35 @@ void check_unaligned() {
 int main() {
     using namespace ttmpc;
     run<9>("phase_riccati<N=20> (input shift, 4-term)");
+    run<60>("round-7 stage (second half unfenced)");
+    run<61>("60 + second prefetch half and P^ write fenced");
+    run<62>("61 + g_u' by one b128 and selects");
+    run<63>("61 + factor-row store one stage later");
+    run<64>("61 + both");
+    run<65>("60 + factor-row store one stage later");
+    run<66>("60 + PA first, H_uu inverse behind the tile reads (= shipped)");
+    run<67>("60 + PA first + late store");
+    run<68>("61 + PA first + late store");
+    run<69>("66 + g_u' by one b128 and selects");
+    run<70>("66, first prefetch half unfenced");
+    run<71>("66, both prefetch halves behind the PA reads");
     run<50>("round-5 stage (6-term)");
     run<51>("round-5 stage, no prefetch, no store");
     run<9>("phase_riccati<N=20> (again)");
-    run<50>("round-5 stage (again)");
+    run<60>("round-7 stage (again)");
     run<9>("phase_riccati<N=20> B=256", 256);
+    run<60>("round-7 stage B=256", 256);
+    run<61>("60 + fenced B=256", 256);
+    run<62>("61 + g_u' by one b128 and selects B=256", 256);
+    run<63>("61 + factor-row store one stage later B=256", 256);
+    run<64>("61 + both B=256", 256);
+    run<65>("60 + late store B=256", 256);
+    run<66>("60 + PA first (= shipped) B=256", 256);
+    run<67>("60 + PA first + late store B=256", 256);
+    run<68>("61 + PA first + late store B=256", 256);
+    run<69>("66 + g select B=256", 256);
+    run<70>("66, first half unfenced B=256", 256);
+    run<71>("66, both halves behind the PA reads B=256", 256);
     run<50>("round-5 stage B=256", 256);
     check_unaligned();
     check_wred();
