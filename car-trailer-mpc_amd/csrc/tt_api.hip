@@ -48,6 +48,12 @@ struct Handle {
     // tracking builds that keep stage rows in HBM (the N = 50 build, ttmpc::track_global_bytes): one launch's rows
     double* d_prow = nullptr;
     size_t prow_cap = 0;  // bytes
+    // tt_solve_batch_ex*: the multipliers of a call that asks for a sensitivity but not for them (d_dual), and the
+    // device side of the host call's extra outputs (d_ex); both grown only, under the one-stream rule of d_prow
+    double* d_dual = nullptr;
+    size_t dual_cap = 0;  // bytes
+    char* d_ex = nullptr;
+    size_t ex_cap = 0;  // bytes
 };
 
 thread_local std::string g_err;
@@ -156,6 +162,24 @@ int ensure_prow(Handle* h, size_t bytes) {
         return fail(h, -ENOMEM, "stage-row workspace allocation failed (%s bytes)", std::to_string(bytes).c_str());
     }
     h->prow_cap = bytes;
+    return 0;
+}
+
+// a handle-owned device block of the _ex calls (grown only, like the stage rows above)
+template <class T>
+int ensure_block(Handle* h, T*& p, size_t& cap, size_t bytes, const char* what) {
+    if (bytes <= cap) return 0;
+    if (p) {
+        (void)hipDeviceSynchronize();
+        (void)hipFree(p);
+    }
+    p = nullptr;
+    cap = 0;
+    if (hipMalloc((void**)&p, bytes) != hipSuccess) {
+        p = nullptr;
+        return fail(h, -ENOMEM, "%s allocation failed", what);
+    }
+    cap = bytes;
     return 0;
 }
 
@@ -341,7 +365,7 @@ int tt_create(const tt_config* cfg, const double* Q, const double* R, const doub
 namespace {
 int solve_device_impl(Handle* h, int B, const double* d_x0, const double* d_xref, const double* d_uref,
                       const double* d_wq_wr, const double* d_z_guess, double* d_x_out, double* d_u_out, int* d_status,
-                      int* d_iters, double* d_kkt_res, void* stream, int host_done);
+                      int* d_iters, double* d_kkt_res, void* stream, int host_done, double* d_dual = nullptr);
 }  // namespace
 
 int tt_solve_batch_device(void* handle, int B, const double* d_x0, const double* d_xref, const double* d_uref,
@@ -354,7 +378,7 @@ int tt_solve_batch_device(void* handle, int B, const double* d_x0, const double*
 namespace {
 int solve_device_impl(Handle* h, int B, const double* d_x0, const double* d_xref, const double* d_uref,
                       const double* d_wq_wr, const double* d_z_guess, double* d_x_out, double* d_u_out, int* d_status,
-                      int* d_iters, double* d_kkt_res, void* stream, int host_done) {
+                      int* d_iters, double* d_kkt_res, void* stream, int host_done, double* d_dual) {
     void* handle = h;
     if (!h) return fail(nullptr, -EINVAL, "NULL handle%s");
     if (B < 0) return fail(h, -EINVAL, "B must be >= 0%s");
@@ -384,6 +408,7 @@ int solve_device_impl(Handle* h, int B, const double* d_x0, const double* d_xref
     a.status = d_status;
     a.iters = d_iters;
     a.host_done = host_done;
+    a.dual = d_dual;
     if (const size_t gb = ttmpc::track_global_bytes(a)) {
         const int rc = ensure_prow(h, gb);
         if (rc) return rc;
@@ -396,9 +421,27 @@ int solve_device_impl(Handle* h, int B, const double* d_x0, const double* d_xref
 }
 }  // namespace
 
+namespace {
+bool wants_sens(const tt_track_extra& x) { return x.gain || x.dxdx0 || x.dudx0 || x.sens_status; }
+bool wants_any(const tt_track_extra* x) { return x && (x->dual || wants_sens(*x)); }
+int ex_device_impl(Handle* h, int B, const double* d_x0, const double* d_xref, const double* d_uref,
+                   const double* d_wq_wr, const double* d_z_guess, double* d_x_out, double* d_u_out, int* d_status,
+                   int* d_iters, double* d_kkt_res, const tt_track_extra& x, void* stream);
+int solve_host(void* handle, int B, const double* x0, const double* xref, const double* uref, const double* wq_wr,
+               const double* z_guess, double* x_out, double* u_out, int* status, int* iters, double* kkt_res,
+               const tt_track_extra* extra);
+}  // namespace
+
 int tt_solve_batch(void* handle, int B, const double* x0, const double* xref, const double* uref,
                    const double* wq_wr, const double* z_guess, double* x_out, double* u_out, int* status,
                    int* iters, double* kkt_res) {
+    return solve_host(handle, B, x0, xref, uref, wq_wr, z_guess, x_out, u_out, status, iters, kkt_res, nullptr);
+}
+
+namespace {
+int solve_host(void* handle, int B, const double* x0, const double* xref, const double* uref, const double* wq_wr,
+               const double* z_guess, double* x_out, double* u_out, int* status, int* iters, double* kkt_res,
+               const tt_track_extra* extra) {
     Handle* h = static_cast<Handle*>(handle);
     if (!h) return fail(nullptr, -EINVAL, "NULL handle%s");
     if (B < 0) return fail(h, -EINVAL, "B must be >= 0%s");
@@ -406,9 +449,11 @@ int tt_solve_batch(void* handle, int B, const double* x0, const double* xref, co
     if (!x0 || !xref || !uref || !x_out || !u_out || !status) return fail(h, -EINVAL, "NULL host buffer%s");
     if (h->cfg.variant == TT_VARIANT_OBCA_PLAN)
         return fail(h, -EINVAL, "plan handles solve through tt_plan_batch / tt_obca_solve_batch%s");
-    if (is_obca(h->cfg))  // MPC+OBCA handle: its own host path (workspace, z_guess layout)
+    if (is_obca(h->cfg)) {  // MPC+OBCA handle: its own host path (workspace, z_guess layout)
+        if (extra) return fail(h, -EINVAL, "multipliers and sensitivities are exported by the tracking variants only%s");
         return tt_obca_solve_batch(handle, B, x0, nullptr, xref, uref, z_guess, x_out, u_out, nullptr, status, iters,
                                    kkt_res);
+    }
     // validate everything tt_solve_batch_device would refuse before the staging buffer is touched
     if (h->cfg.variant == TT_VARIANT_FUZZY && !wq_wr)
         return fail(h, -EINVAL, "fuzzy variant needs per-instance weights (mpc_control_fuzzy.py:54-58)%s");
@@ -426,8 +471,25 @@ int tt_solve_batch(void* handle, int B, const double* x0, const double* xref, co
     const size_t nxo = b * (N + 1) * 6, nuo = b * N * 2, out_d = nxo + nuo + b + b;  // 2 x int32 per instance = 1 double
     int rc = ensure_stage(h, in_d * 8, out_d * 8);
     if (rc) return rc;
-    // zero-copy for small batches (B = 1 latency: the two DMA copies cost more than the kernel's few PCIe reads)
-    const bool zc = B <= zero_copy_max() && N < 64;
+    // the extra outputs of tt_solve_batch_ex: one device block, dual | gain | dxdx0 | dudx0 | sens_status (a call that
+    // asks for a sensitivity always has the multipliers in it)
+    tt_track_extra dx = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    const size_t n_dual = b * (N + 1) * ttmpc::kDualPerStage, n_gain = b * 12, n_dxx = b * (N + 1) * 36, n_dux = b * N * 12;
+    if (extra) {
+        const size_t ex_d = n_dual + (extra->gain ? n_gain : 0) + (extra->dxdx0 ? n_dxx : 0) +
+                            (extra->dudx0 ? n_dux : 0) + (extra->sens_status ? (b + 1) / 2 : 0);
+        rc = ensure_block(h, h->d_ex, h->ex_cap, ex_d * 8, "extra-output workspace");
+        if (rc) return rc;
+        double* p = reinterpret_cast<double*>(h->d_ex);
+        dx.dual = p; p += n_dual;
+        if (extra->gain) { dx.gain = p; p += n_gain; }
+        if (extra->dxdx0) { dx.dxdx0 = p; p += n_dxx; }
+        if (extra->dudx0) { dx.dudx0 = p; p += n_dux; }
+        if (extra->sens_status) dx.sens_status = reinterpret_cast<int*>(p);
+    }
+    // zero-copy for small batches (B = 1 latency: the two DMA copies cost more than the kernel's few PCIe reads); a call
+    // with extra outputs always copies (they are not part of the coherent mirror)
+    const bool zc = !extra && B <= zero_copy_max() && N < 64;
     double* hin = reinterpret_cast<double*>(h->h_sin);
     const double* dptr[5];
     size_t off = 0;
@@ -451,8 +513,12 @@ int tt_solve_batch(void* handle, int B, const double* x0, const double* xref, co
     volatile int* hst = zc ? reinterpret_cast<volatile int*>(h->h_sout + (nxo + nuo + b) * 8) : nullptr;
     if (zc)
         for (int i = 0; i < B; ++i) hst[i] = kStatusPending;
-    rc = solve_device_impl(h, B, dptr[0], dptr[1], dptr[2], wq_wr ? dptr[3] : nullptr, z_guess ? dptr[4] : nullptr, dxo,
-                           duo, dst, dit, dkk, s, zc ? 1 : 0);
+    if (extra)
+        rc = ex_device_impl(h, B, dptr[0], dptr[1], dptr[2], wq_wr ? dptr[3] : nullptr, z_guess ? dptr[4] : nullptr, dxo,
+                            duo, dst, dit, dkk, dx, s);
+    else
+        rc = solve_device_impl(h, B, dptr[0], dptr[1], dptr[2], wq_wr ? dptr[3] : nullptr, z_guess ? dptr[4] : nullptr,
+                               dxo, duo, dst, dit, dkk, s, zc ? 1 : 0);
     if (rc) {
         (void)hipStreamSynchronize(s);  // the H2D from the pinned staging buffer may still be in flight
         return rc;
@@ -460,8 +526,21 @@ int tt_solve_batch(void* handle, int B, const double* x0, const double* xref, co
     bool done = false;
     if (zc) done = poll_done(hst, B);
     e = zc ? hipSuccess : hipMemcpyAsync(h->h_sout, h->d_sout, out_d * 8, hipMemcpyDeviceToHost, s);
+    if (extra) {  // straight into the caller's arrays (the stream wait below covers them)
+#define EX_D2H(m, n, t) \
+    if (e == hipSuccess && extra->m) e = hipMemcpyAsync(extra->m, dx.m, (n) * sizeof(t), hipMemcpyDeviceToHost, s)
+        EX_D2H(dual, n_dual, double);
+        EX_D2H(gain, n_gain, double);
+        EX_D2H(dxdx0, n_dxx, double);
+        EX_D2H(dudx0, n_dux, double);
+        EX_D2H(sens_status, b, int);
+#undef EX_D2H
+    }
     if (e == hipSuccess && !done) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(h, e, "solve");
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(s);
+        return hip_fail(h, e, "solve");
+    }
     const double* ho = reinterpret_cast<const double*>(h->h_sout);
     memcpy(x_out, ho, nxo * 8);
     memcpy(u_out, ho + nxo, nuo * 8);
@@ -471,6 +550,112 @@ int tt_solve_batch(void* handle, int B, const double* x0, const double* xref, co
     if (iters) memcpy(iters, hi + b, b * 4);
     return 0;
 }
+
+ttmpc::SensArgs make_sens_args(const Handle* h, int B) {
+    ttmpc::SensArgs a;
+    memset(&a, 0, sizeof a);
+    a.N = h->cfg.N;
+    a.B = B;
+    a.dt = h->cfg.dt;
+    a.L1 = h->cfg.L1;
+    a.L2 = h->cfg.L2;
+    a.Mh = h->cfg.Mh;
+    memcpy(a.Q, h->Q, sizeof a.Q);
+    memcpy(a.R, h->R, sizeof a.R);
+    memcpy(a.xlb, h->xlb, sizeof a.xlb);
+    memcpy(a.xub, h->xub, sizeof a.xub);
+    memcpy(a.ulb, h->ulb, sizeof a.ulb);
+    memcpy(a.uub, h->uub, sizeof a.uub);
+    return a;
+}
+
+// the sensitivity launch behind both entry points; the caller has made the handle's device current
+int sens_launch(Handle* h, int B, const double* d_x, const double* d_u, const double* d_dual, const double* d_wq_wr,
+                const int* d_status, const tt_track_extra& x, void* stream) {
+    ttmpc::SensArgs a = make_sens_args(h, B);
+    a.x = d_x;
+    a.u = d_u;
+    a.dual = d_dual;
+    a.wqwr = d_wq_wr;
+    a.status = d_status;
+    a.gain = x.gain;
+    a.dxdx0 = x.dxdx0;
+    a.dudx0 = x.dudx0;
+    a.sens_status = x.sens_status;
+    const hipError_t e = ttmpc::launch_track_sens(a, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(h, e, "sensitivity kernel launch");
+    return 0;
+}
+
+// solve (+ multiplier export) and, if asked for, the sensitivity launch behind it on the same stream
+int ex_device_impl(Handle* h, int B, const double* d_x0, const double* d_xref, const double* d_uref,
+                   const double* d_wq_wr, const double* d_z_guess, double* d_x_out, double* d_u_out, int* d_status,
+                   int* d_iters, double* d_kkt_res, const tt_track_extra& x, void* stream) {
+    if (!h) return fail(nullptr, -EINVAL, "NULL handle%s");
+    if (is_obca(h->cfg))
+        return fail(h, -EINVAL, "multipliers and sensitivities are exported by the tracking variants only%s");
+    if (B <= 0) return B < 0 ? fail(h, -EINVAL, "B must be >= 0%s") : 0;
+    const bool sens = wants_sens(x);
+    double* d_dual = x.dual;
+    DeviceGuard dg(h->device);
+    if (dg.err != hipSuccess) return hip_fail(h, dg.err, "hipSetDevice");
+    if (sens && !d_dual) {
+        const size_t bytes = (size_t)B * (h->cfg.N + 1) * ttmpc::kDualPerStage * sizeof(double);
+        const int rc = ensure_block(h, h->d_dual, h->dual_cap, bytes, "multiplier workspace");
+        if (rc) return rc;
+        d_dual = h->d_dual;
+    }
+    int rc = solve_device_impl(h, B, d_x0, d_xref, d_uref, d_wq_wr, d_z_guess, d_x_out, d_u_out, d_status, d_iters,
+                               d_kkt_res, stream, 0, d_dual);
+    if (rc || !sens) return rc;
+    return sens_launch(h, B, d_x_out, d_u_out, d_dual, d_wq_wr, d_status, x, stream);
+}
+}  // namespace
+
+int tt_solve_batch_ex(void* handle, int B, const double* x0, const double* xref, const double* uref,
+                      const double* wq_wr, const double* z_guess, double* x_out, double* u_out, int* status,
+                      int* iters, double* kkt_res, const tt_track_extra* extra) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (h && is_obca(h->cfg))
+        return fail(h, -EINVAL, "multipliers and sensitivities are exported by the tracking variants only%s");
+    return solve_host(handle, B, x0, xref, uref, wq_wr, z_guess, x_out, u_out, status, iters, kkt_res,
+                      wants_any(extra) ? extra : nullptr);
+}
+
+int tt_solve_batch_ex_device(void* handle, int B, const double* d_x0, const double* d_xref, const double* d_uref,
+                             const double* d_wq_wr, const double* d_z_guess, double* d_x_out, double* d_u_out,
+                             int* d_status, int* d_iters, double* d_kkt_res, const tt_track_extra* d_extra,
+                             void* stream) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (h && is_obca(h->cfg))
+        return fail(h, -EINVAL, "multipliers and sensitivities are exported by the tracking variants only%s");
+    if (!wants_any(d_extra))
+        return solve_device_impl(h, B, d_x0, d_xref, d_uref, d_wq_wr, d_z_guess, d_x_out, d_u_out, d_status, d_iters,
+                                 d_kkt_res, stream, 0);
+    return ex_device_impl(h, B, d_x0, d_xref, d_uref, d_wq_wr, d_z_guess, d_x_out, d_u_out, d_status, d_iters,
+                          d_kkt_res, *d_extra, stream);
+}
+
+int tt_track_sens_device(void* handle, int B, const double* d_x, const double* d_u, const double* d_dual,
+                         const double* d_wq_wr, const int* d_status, double* d_gain, double* d_dxdx0,
+                         double* d_dudx0, int* d_sens_status, void* stream) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (!h) return fail(nullptr, -EINVAL, "NULL handle%s");
+    if (is_obca(h->cfg))
+        return fail(h, -EINVAL, "multipliers and sensitivities are exported by the tracking variants only%s");
+    if (B < 0) return fail(h, -EINVAL, "B must be >= 0%s");
+    if (B == 0) return 0;
+    if (B > (1 << 30)) return fail(h, -EINVAL, "B too large%s");
+    if (!d_x || !d_u || !d_dual || !d_status) return fail(h, -EINVAL, "NULL device buffer%s");
+    if (h->cfg.variant == TT_VARIANT_FUZZY && !d_wq_wr)
+        return fail(h, -EINVAL, "fuzzy variant needs per-instance weights (mpc_control_fuzzy.py:54-58)%s");
+    DeviceGuard dg(h->device);
+    if (dg.err != hipSuccess) return hip_fail(h, dg.err, "hipSetDevice");
+    const tt_track_extra x = {nullptr, d_gain, d_dxdx0, d_dudx0, d_sens_status};
+    return sens_launch(h, B, d_x, d_u, d_dual, d_wq_wr, d_status, x, stream);
+}
+
+long long tt_track_dual_len(int N) { return N < 1 ? -EINVAL : (long long)ttmpc::kDualPerStage * (N + 1); }
 
 #ifdef TT_STAMPS
 // Diagnostic-build-only entry point: per-instance phase cycle sums into d_stamps[B][kNumPhases].
@@ -703,6 +888,8 @@ void tt_destroy(void* handle) {
     free_ows(h);
     free_stage(h);
     if (h->d_prow) (void)hipFree(h->d_prow);
+    if (h->d_dual) (void)hipFree(h->d_dual);
+    if (h->d_ex) (void)hipFree(h->d_ex);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }

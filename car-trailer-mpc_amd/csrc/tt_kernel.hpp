@@ -29,6 +29,7 @@ struct TrackArgs {
     double* prow;                         // [B][N+1][kGlobalRows]: the stage rows a build keeps in HBM, or nullptr
     int host_done;                        // 1: status[b] is the instance's completion flag for a polling host (zero-copy
                                           //    host calls): written last, after a system-scope release of the rest
+    double* dual;                         // [B][N+1][kDualPerStage]: y 6, z_L 8, z_U 8 per stage (ttmpc.h), or nullptr
 };
 
 // phases timed by the TT_STAMPS diagnostic build
@@ -58,6 +59,29 @@ constexpr int kGlobalRows = 28;
 size_t track_global_bytes(const TrackArgs& a);
 
 hipError_t launch_track(const TrackArgs& a, hipStream_t stream);
+// the exporting twins of the same builds (tt_track_dual.hip); launch_track forwards to it when a.dual is set
+hipError_t launch_track_dual(const TrackArgs& a, hipStream_t stream);
+
+// ---------------- sensitivity of a tracking solution to x_init (tt_sens.hip) ----------------
+constexpr int kDualPerStage = 22;  // y 6 | z_L 8 | z_U 8: the stage rows rY .. rZU + 7 of tt_track.hip, in that order
+struct SensArgs {
+    int N, B;
+    double dt, L1, L2, Mh;
+    double Q[36], R[4];
+    double xlb[6], xub[6], ulb[2], uub[2];  // raw bounds (relaxed in-kernel as track_kernel relaxes them)
+    const double* x;      // [B][N+1][6]
+    const double* u;      // [B][N][2]
+    const double* dual;   // [B][N+1][kDualPerStage]
+    const double* wqwr;   // [B][8] or nullptr
+    const int* status;    // [B] of the solve
+    double* gain;         // [B][2][6] or nullptr
+    double* dxdx0;        // [B][N+1][6][6] or nullptr
+    double* dudx0;        // [B][N][2][6] or nullptr
+    int* sens_status;     // [B] or nullptr
+};
+// LDS doubles of one instance: 24 per stage (dt*J 9, curvature 7, Sigma 8), 12 per input stage (K), and the tiles
+inline int sens_lds_doubles(int N) { return 24 * (N + 1) + 12 * N + 192; }
+hipError_t launch_track_sens(const SensArgs& a, hipStream_t stream);
 
 }  // namespace ttmpc
 

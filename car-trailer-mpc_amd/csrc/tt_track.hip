@@ -44,16 +44,33 @@
 // Bound pattern: template parameter BM (bit v = finite lower bound on variable v, bit 8+v = finite
 // upper bound; v = 0..5 states, 6..7 inputs) so the common patterns compile to straight-line code;
 // BM < 0 = pattern read at run time.
+//
+// Multiplier export: this file is compiled twice.  tt_track_dual.hip defines TT_TRACK_DUAL and includes it: the same
+// kernels with the export of y, z_L, z_U (TrackArgs::dual) in their epilogue, behind launch_track_dual.  Compiled into
+// the one kernel behind a run-time test, the export moved the register allocation of every build (scratch of the
+// two-wave N = 30 build 112 -> 120 B/lane, AGPRs of the carried builds +-2..10); as a second set of instantiations in
+// this code object it left the plain kernels' instructions identical, yet C3 measured +0.5 % (DESIGN.md "Multiplier
+// export").  As a translation unit of its own it leaves this one's code object what it was, and C2 / C3 measure as
+// the parent.
 #include <math.h>
 
 #include <atomic>
 
+#ifdef TT_TRACK_DUAL
+#define track_kernel track_kernel_dual
+#define launch_track launch_track_dual
+#endif
 #include "tt_kernel.hpp"
 #include "tt_trig.hpp"
 
 namespace ttmpc {
 namespace {
 
+#ifdef TT_TRACK_DUAL
+constexpr bool kDual = true;
+#else
+constexpr bool kDual = false;
+#endif
 constexpr int W = 64;
 // A stage row kept in HBM (Ctx::kPG builds): raw buffer load / store through the instance's descriptor (SGPRs) with a
 // 32-bit lane offset and a scalar offset -- the access form that needs no 64-bit address registers.
@@ -2255,6 +2272,22 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(OCC))) void t
         for (int t = lane; t < S * 6; t += W) xo[t] = c.r(rX + t % 6, t / 6);
         double* uo = a.uout + (size_t)b * N * 2;
         for (int t = lane; t < N * 2; t += W) uo[t] = c.r(rX + 6 + t % 2, t / 2);
+        // Multiplier export (tt_solve_batch_ex): the Y, zL, zU rows are consecutive and current at every exit -- the
+        // carried builds store them in phase_update and no exit lies between an update and the next linearisation.
+        // An infeasible instance never initialised them, the stage-N input slots are never written, and a free
+        // variable has no multiplier: those entries are 0.
+        if constexpr (kDual) {
+            static_assert(rZL == rY + 6 && rZU == rZL + 8 && kDualPerStage == 22, "y | z_L | z_U in consecutive rows");
+            double* dl = a.dual + (size_t)b * S * kDualPerStage;
+            for (int t = lane; t < S * kDualPerStage; t += W) {
+                const int k = t / kDualPerStage, j = t % kDualPerStage;
+                const int v = j < 6 ? -1 : (j - 6) & 7;
+                bool live = !infeas;
+                if (v >= 6 && k == N) live = false;
+                if (v >= 0 && !(j < 14 ? c.hl(v) : c.hu(v))) live = false;
+                dl[t] = live ? c.r(rY + j, k) : 0.0;
+            }
+        }
 #ifdef TT_STAMPS
         stamps.store(a.stamps ? a.stamps + (size_t)b * kNumPhases : nullptr, lane);
 #endif
@@ -2307,7 +2340,7 @@ constexpr int kOccBit = 1 << 17;   // the two-waves-per-SIMD build (Ctx::kLF)
 constexpr int kPGBit = 1 << 18;    // the P / p band of the stage record in HBM (Ctx::kPG)
 
 // Q and R diagonal after symmetrisation (the kernel's weights are 0.5 (Q + Q'), 0.5 (R + R'))
-bool diagonal_weights(const TrackArgs& a) {
+static bool diagonal_weights(const TrackArgs& a) {
     for (int i = 0; i < 6; ++i)
         for (int j = i + 1; j < 6; ++j)
             if (0.5 * (a.Q[i * 6 + j] + a.Q[j * 6 + i]) != 0.0) return false;
@@ -2317,7 +2350,7 @@ bool diagonal_weights(const TrackArgs& a) {
 // Above three instances per CU (768 on MI355X's 256 CUs) the LDS build of N = 50 needs a second round of instances;
 // the HBM-band build fits four per CU.  Below, the LDS build is faster per instance (B = 1 host call 0.140 vs 0.161 ms).
 // The two builds are bitwise one another (profiles/r06/n50_hbm_band/), so results do not depend on B.
-int current_cu_count() {
+static int current_cu_count() {
     static std::atomic<int> cache[64];  // per device, 0 = not queried yet (a race only queries twice)
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0) return 256;
@@ -2328,15 +2361,21 @@ int current_cu_count() {
     if (dev < 64) cache[dev].store(cus, std::memory_order_relaxed);
     return cus;
 }
-bool uses_global_rows(const TrackArgs& a) {
+static bool uses_global_rows(const TrackArgs& a) {
     return bound_mask(a) == kMaskMPC && diagonal_weights(a) && a.N == 50 && a.B > 3 * current_cu_count();
 }
 
+#ifndef TT_TRACK_DUAL
 size_t track_global_bytes(const TrackArgs& a) {
     return uses_global_rows(a) ? (size_t)a.B * (a.N + 1) * kGlobalRows * sizeof(double) : 0;
 }
+#endif
 
+// (launch_track_dual in tt_track_dual.hip's compilation of this file: the same dispatch over the exporting twins)
 hipError_t launch_track(const TrackArgs& a, hipStream_t stream) {
+#ifndef TT_TRACK_DUAL
+    if (a.dual) return launch_track_dual(a, stream);
+#endif
     const int m = bound_mask(a);
     const bool d = diagonal_weights(a);
     // Two waves per SIMD only pay where LDS lets more than 4 waves share a CU (N <= 31 with the 118-double

@@ -39,8 +39,25 @@ class TTPlant(C.Structure):
                 ("lateral_slip_gain", C.c_double), ("slip_angle_max", C.c_double)]
 
 
+class TTTrackExtra(C.Structure):
+    """tt_track_extra (include/ttmpc.h): the optional outputs of tt_solve_batch_ex*; NULL members are skipped."""
+    _fields_ = [("dual", C.c_void_p), ("gain", C.c_void_p), ("dxdx0", C.c_void_p), ("dudx0", C.c_void_p),
+                ("sens_status", C.c_void_p)]
+
+
 class TTError(RuntimeError):
     pass
+
+
+class TrackExResult:
+    """What ``BatchSolver.solve_ex`` returns: the plain outputs X (B,N+1,6), U (B,N,2), status, iters, kkt and, where
+    asked for (else None), dual (B,N+1,22: y 6 | z_L 8 | z_U 8 per stage), gain (B,2,6) = du_0/dx_init,
+    dXdx0 (B,N+1,6,6), dUdx0 (B,N,2,6) and sens_status (B,) (0 ok, 1 undefined, 2 solve not successful)."""
+    __slots__ = ("X", "U", "status", "iters", "kkt", "dual", "gain", "dXdx0", "dUdx0", "sens_status")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
 
 
 _lib = None
@@ -80,6 +97,17 @@ def lib():
     L.tt_solve_batch.restype = C.c_int
     L.tt_solve_batch_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 10 + [C.c_void_p]
     L.tt_solve_batch_device.restype = C.c_int
+    if not os.environ.get("TTMPC_LIB") or hasattr(L, "tt_track_dual_len"):  # (A/B against a build without them)
+        L.tt_solve_batch_ex.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp,
+                                        C.POINTER(TTTrackExtra)]
+        L.tt_solve_batch_ex.restype = C.c_int
+        L.tt_solve_batch_ex_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 10 + [C.POINTER(TTTrackExtra),
+                                                                                          C.c_void_p]
+        L.tt_solve_batch_ex_device.restype = C.c_int
+        L.tt_track_sens_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 10
+        L.tt_track_sens_device.restype = C.c_int
+        L.tt_track_dual_len.argtypes = [C.c_int]
+        L.tt_track_dual_len.restype = C.c_longlong
     L.tt_plan_batch.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _ip]
     L.tt_plan_batch.restype = C.c_int
     L.tt_obca_solve_batch.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp]
@@ -141,7 +169,8 @@ EXPORTED_SYMBOLS = ("tt_create", "tt_solve_batch", "tt_solve_batch_device", "tt_
                     "tt_collision_device", "tt_plant_update_device", "tt_warm_start_device",
                     "tt_record_solution_device", "tt_interpolate_device", "tt_lqr_score_device",
                     "tt_sim_window_indexed_device", "tt_sim_log_advance_device", "tt_policy_plant_device",
-                    "tt_fuzzy_weights_device", "tt_plant_update_noise_device", "tt_policy_plant_noise_device")
+                    "tt_fuzzy_weights_device", "tt_plant_update_noise_device", "tt_policy_plant_noise_device",
+                    "tt_track_dual_len", "tt_solve_batch_ex", "tt_solve_batch_ex_device", "tt_track_sens_device")
 
 
 def _ptr(a):
@@ -284,6 +313,55 @@ class BatchSolver:
                                            u_out, status, iters or None, kkt or None, stream or None)
         if rc != 0:
             self._err(rc, "tt_solve_batch_device")
+
+    def solve_ex(self, x0, xref, uref, wq_wr=None, z_guess=None, duals=True, gain=True, trajectory_sens=False):
+        """``solve`` plus the multipliers and the first-order sensitivities to x0 (include/ttmpc.h, tt_solve_batch_ex).
+        duals: the (B,N+1,22) multipliers; gain: du_0/dx0 (B,2,6); trajectory_sens: dX/dx0 (B,N+1,6,6) and
+        dU/dx0 (B,N,2,6).  sens_status comes with either sensitivity.  Returns a ``TrackExResult``; X, U, status, iters
+        and kkt are bitwise those of ``solve``."""
+        N = self.N
+        x0 = _f64(x0)
+        B = x0.shape[0] if x0.ndim == 2 else 1
+        x0 = x0.reshape(B, 6)
+        xref = _f64(xref, (B, N + 1, 6))
+        uref = _f64(uref, (B, N, 2))
+        w = None if wq_wr is None else _f64(wq_wr, (B, 8))
+        zg = None if z_guess is None else _f64(z_guess, (B, 8 * N + 6))
+        r = TrackExResult(X=np.empty((B, N + 1, 6)), U=np.empty((B, N, 2)), status=np.empty(B, dtype=np.int32),
+                          iters=np.empty(B, dtype=np.int32), kkt=np.empty(B))
+        if duals:
+            r.dual = np.empty((B, N + 1, 22))
+        if gain:
+            r.gain = np.empty((B, 2, 6))
+        if trajectory_sens:
+            r.dXdx0 = np.empty((B, N + 1, 6, 6))
+            r.dUdx0 = np.empty((B, N, 2, 6))
+        if gain or trajectory_sens:
+            r.sens_status = np.empty(B, dtype=np.int32)
+        ex = TTTrackExtra(*[None if a is None else a.ctypes.data for a in (r.dual, r.gain, r.dXdx0, r.dUdx0,
+                                                                             r.sens_status)])
+        rc = self._L.tt_solve_batch_ex(self._h, B, _ptr(x0), _ptr(xref), _ptr(uref), _ptr(w), _ptr(zg), _ptr(r.X),
+                                       _ptr(r.U), r.status.ctypes.data_as(_ip), r.iters.ctypes.data_as(_ip),
+                                       _ptr(r.kkt), C.byref(ex))
+        if rc != 0:
+            self._err(rc, "tt_solve_batch_ex")
+        return r
+
+    def solve_ex_device(self, B, x0, xref, uref, x_out, u_out, status, iters=0, kkt=0, wq_wr=0, z_guess=0, dual=0,
+                        gain=0, dxdx0=0, dudx0=0, sens_status=0, stream=0):
+        """``solve_device`` with the optional device outputs of tt_solve_batch_ex_device (0 = not wanted)."""
+        ex = TTTrackExtra(dual or None, gain or None, dxdx0 or None, dudx0 or None, sens_status or None)
+        rc = self._L.tt_solve_batch_ex_device(self._h, int(B), x0, xref, uref, wq_wr or None, z_guess or None, x_out,
+                                              u_out, status, iters or None, kkt or None, C.byref(ex), stream or None)
+        if rc != 0:
+            self._err(rc, "tt_solve_batch_ex_device")
+
+    def sens_device(self, B, x, u, dual, status, gain=0, dxdx0=0, dudx0=0, sens_status=0, wq_wr=0, stream=0):
+        """tt_track_sens_device: the sensitivity kernel alone on device arrays of an earlier ``solve_ex_device``."""
+        rc = self._L.tt_track_sens_device(self._h, int(B), x, u, dual, wq_wr or None, status, gain or None,
+                                          dxdx0 or None, dudx0 or None, sens_status or None, stream or None)
+        if rc != 0:
+            self._err(rc, "tt_track_sens_device")
 
 
 def obca_n(N: int, M: int) -> int:

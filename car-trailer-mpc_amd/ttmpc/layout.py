@@ -44,3 +44,17 @@ def shift(z, N, bug_compatible=True):
         X, U = unpack(z, N)
         last_state, last_input = X[:, -1], U[:, -1]
     return np.ascontiguousarray(np.concatenate([body, last_state, last_input, last_state], axis=1).reshape(B, -1))
+
+
+def casadi_multipliers(dual, N):
+    """The multiplier export of ``BatchSolver.solve_ex`` (dual (B,N+1,22) or (N+1,22): y 6 | z_L 8 | z_U 8 per stage)
+    in CasADi's order and sign: lam_g ((N+1)*6), the multipliers of g = [x_0 - x_init, x_1 - F(x_0, u_0), ...]
+    (trajectory_planning.py:28-36), and lam_x (8N+6) = z_U - z_L in the order of the decision vector z."""
+    d = np.asarray(dual, dtype=np.float64)
+    single = d.ndim == 2
+    d = d.reshape(-1, N + 1, 22)
+    B = d.shape[0]
+    lam_g = np.ascontiguousarray(d[:, :, :6].reshape(B, (N + 1) * 6))
+    lx = d[:, :, 14:22] - d[:, :, 6:14]
+    lam_x = np.ascontiguousarray(np.concatenate([lx[:, :N].reshape(B, 8 * N), lx[:, N, :6]], axis=1))
+    return (lam_g[0], lam_x[0]) if single else (lam_g, lam_x)

@@ -19,6 +19,7 @@ class MPCTrackingControl(TrajectoryPlanning):
         super().__init__(dynamics, params, Q, R, state_bound, input_bound, device=device)
         self.last_status = None
         self.last_iters = None
+        self.last_sens_status = None
 
     def solve(self, initial_state, reference_states, reference_inputs):
         """mpc_control.py:67-110: returns (states (6,N+1), inputs (2,N)); on failure prints
@@ -28,6 +29,19 @@ class MPCTrackingControl(TrajectoryPlanning):
         if not self._success(st[0]):
             print("Cannot find a solution!")
         return X[0], U[0]
+
+    def solve_with_gain(self, initial_state, reference_states, reference_inputs):
+        """``solve`` plus the feedback gain K = du_0/dx_init (2x6) of the returned optimum: to first order, and with the
+        active bounds held, the optimal first input for a state that moved to x_new is u_0 + K (x_new - initial_state).
+        K is all zeros where the sensitivity is undefined (``last_sens_status`` != 0: failed solve, or a reduced
+        Hessian that is not positive definite).  Returns (states (6,N+1), inputs (2,N), K)."""
+        x0, xr, ur = self._batch_inputs(np.asarray(initial_state)[None], np.asarray(reference_states)[None],
+                                        np.asarray(reference_inputs)[None])
+        r = self._solver.solve_ex(x0, xr, ur, duals=False, gain=True)
+        self.last_status, self.last_iters, self.last_sens_status = r.status, r.iters, r.sens_status
+        if not self._success(r.status[0]):
+            print("Cannot find a solution!")
+        return r.X[0].T.copy(), r.U[0].T.copy(), r.gain[0]
 
     def solve_batch(self, initial_states, reference_states, reference_inputs):
         """B instances at once: (B,6), (B,6,N+1), (B,2,N) -> (B,6,N+1), (B,2,N), status (B,)."""

@@ -70,6 +70,29 @@ class MPCTrackingControlFuzzy(TrajectoryPlanning):
         self._last_solution[ok] = layout.pack(X[ok], U[ok])
         return X.transpose(0, 2, 1).copy(), U.transpose(0, 2, 1).copy(), st
 
+    def solve_with_gain(self, initial_state, reference_states, reference_inputs):
+        """``solve`` plus the feedback gain K = du_0/dx_init (2x6) of the returned optimum (MPCTrackingControl.
+        solve_with_gain), at the weights the accepted solve used; the same warm start, unit-weight retry and
+        bookkeeping as ``solve``.  Failure of both attempts -> (None, None, None)."""
+        x0, xr, ur = self._batch_inputs(np.asarray(initial_state)[None], np.asarray(reference_states)[None],
+                                        np.asarray(reference_inputs)[None])
+        N = self._horizon
+        guess = layout.pack(xr, ur)
+        if self._last_solution is not None and self._last_solution.shape[0] == 1 \
+                and np.all(np.isfinite(self._last_solution[0])):
+            guess[0] = layout.shift(self._last_solution, N, self._bug_compatible)[0]
+        w = np.concatenate(fuzzy_weights(x0[0], xr[0].T))[None]
+        r = self._solver.solve_ex(x0, xr, ur, wq_wr=w, z_guess=guess, duals=False, gain=True)
+        if not self._success(r.status[0]):  # retry with unit weights, same guess (mpc_control_fuzzy.py:145-159)
+            r = self._solver.solve_ex(x0, xr, ur, wq_wr=np.ones((1, 8)), z_guess=guess, duals=False, gain=True)
+        self.last_sens_status = r.sens_status
+        if not self._success(r.status[0]):
+            return None, None, None
+        if self._last_solution is None or self._last_solution.shape[0] != 1:
+            self._last_solution = np.full((1, 8 * N + 6), np.nan)
+        self._last_solution[0] = layout.pack(r.X, r.U)[0]
+        return r.X[0].T.copy(), r.U[0].T.copy(), r.gain[0]
+
     def solve(self, initial_state, reference_states, reference_inputs):
         X, U, st = self.solve_batch(np.asarray(initial_state)[None], np.asarray(reference_states)[None],
                                     np.asarray(reference_inputs)[None])

@@ -46,6 +46,20 @@ class TruckTrailerNMPC(TrajectoryPlanning):
         self._last_solution[ok] = layout.pack(X[ok], U[ok])
         return X.transpose(0, 2, 1).copy(), U.transpose(0, 2, 1).copy(), st
 
+    def solve_with_gain(self, initial_state, reference_states, reference_inputs):
+        """``solve`` plus the feedback gain K = du_0/dx_init (2x6) of the returned optimum (MPCTrackingControl.
+        solve_with_gain); same warm start and bookkeeping as ``solve``.  Failure -> (None, None, None)."""
+        x0, xr, ur = self._batch_inputs(np.asarray(initial_state)[None], np.asarray(reference_states)[None],
+                                        np.asarray(reference_inputs)[None])
+        r = self._solver.solve_ex(x0, xr, ur, z_guess=self._guess(xr, ur), duals=False, gain=True)
+        self.last_sens_status = r.sens_status
+        if not self._success(r.status[0]):
+            return None, None, None
+        if self._last_solution is None or self._last_solution.shape[0] != 1:
+            self._last_solution = np.full((1, 8 * self._horizon + 6), np.nan)
+        self._last_solution[0] = layout.pack(r.X, r.U)[0]
+        return r.X[0].T.copy(), r.U[0].T.copy(), r.gain[0]
+
     def solve(self, initial_state, reference_states, reference_inputs):
         X, U, st = self.solve_batch(np.asarray(initial_state)[None], np.asarray(reference_states)[None],
                                     np.asarray(reference_inputs)[None])

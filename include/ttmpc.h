@@ -35,8 +35,14 @@
  *    outputs are the last iterate, possibly partial; INTEGRATION.md "Helper workgroups").
  *    CasADi's stats()['success'] == (status <= TT_ACCEPTABLE).
  *  - a handle is not thread-safe (like the reference objects, which mutate _last_solution); use
- *    one handle per host thread.  Host-pointer calls are synchronous; device-pointer calls are
- *    asynchronous on the given HIP stream.
+ *    one handle per host thread.  Every host-pointer call (tt_solve_batch, tt_solve_batch_ex, tt_plan_batch,
+ *    tt_obca_solve_batch, tt_obca_solve_batch_iterate) is synchronous for its caller: its outputs are complete
+ *    when it returns.  A tracking tt_solve_batch of a small batch (B <= 64, N < 64) returns as soon as every
+ *    instance has published its outputs to host memory, which can be before its kernel has retired on the
+ *    handle's private stream: later host calls on the handle are ordered behind it on that stream and
+ *    tt_destroy waits for it, but an asynchronous error of that kernel would be reported by a later call.
+ *    tt_solve_batch_ex with any extra output always copies and waits for the stream.  Device-pointer calls
+ *    (*_device) are asynchronous on the given HIP stream and return after enqueueing.
  *  - GPU only: there is no CPU fallback; tt_create fails (-ENODEV) without a usable gfx950 device.
  */
 #ifndef TTMPC_H
@@ -88,6 +94,55 @@ int tt_solve_batch(void* handle, int B, const double* x0, const double* xref, co
 int tt_solve_batch_device(void* handle, int B, const double* d_x0, const double* d_xref, const double* d_uref,
                           const double* d_wq_wr, const double* d_z_guess, double* d_x_out, double* d_u_out,
                           int* d_status, int* d_iters, double* d_kkt_res, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Multipliers and first-order sensitivities of a tracking solve (TT_VARIANT_TRACK, _NMPC, _FUZZY; an OBCA
+ * handle returns -EINVAL).  CasADi's `sol` carries lam_g and lam_x next to x; these calls return the same
+ * multipliers, and the sensitivity of the solution to the measured state x_init that a parametric-NLP user
+ * (sIPOPT, advanced-step NMPC) takes from the same KKT factorisation.
+ *
+ * dual [B][N+1][22], tt_track_dual_len(N) = 22 (N+1) doubles per instance; per stage k = 0..N:
+ *     y_k   (6)  multiplier of the equality row whose left side is x_k:  x_0 - x_init for k = 0, else
+ *                x_k - x_{k-1} - dt f(x_{k-1}, u_{k-1})                  (the reference's g, trajectory_planning.py:28-36)
+ *     z_L   (8)  multipliers of the lower bounds of (x_k 6, u_k 2)
+ *     z_U   (8)  multipliers of the upper bounds
+ *   The u entries are 0 at k = N, entries of free variables are 0, and an instance with status TT_INFEASIBLE has
+ *   all zeros.  Sign convention: IPOPT's and CasADi's,  grad f + J' y - z_L + z_U = 0,  z >= 0  (so CasADi's
+ *   lam_g = y and lam_x = z_U - z_L; the Python mirror's layout.casadi_multipliers reorders them).  They are the
+ *   solver's final iterate: multipliers of the bounds relaxed by IPOPT's bound_relax_factor (1e-8), at a point
+ *   that meets IPOPT's stopping test, not exact multipliers of an exact optimum.
+ *
+ * Sensitivities, as sIPOPT defines them: the Newton matrix of the primal-dual system at the returned point,
+ * solved for a unit perturbation of the x_0 - x_init row (one Riccati pass, no regularisation):
+ *     gain   [B][2][6]        du_0 / dx_init   (the feedback gain K: u_0(x_init + d) ~ u_0 + K d)
+ *     dxdx0  [B][N+1][6][6]   dx_k / dx_init   (k = 0: the identity)
+ *     dudx0  [B][N][2][6]     du_k / dx_init   (k = 0: the gain)
+ *     sens_status [B]         0 ok; 1 a reduced input Hessian was not positive definite or a value was not
+ *                             finite (the sensitivity is undefined there); 2 the solve's status is above
+ *                             TT_ACCEPTABLE (skipped).  For 1 and 2 the instance's three arrays are zeroed.
+ *   First order only: a variable sitting on a bound has (numerically) zero sensitivity and stays there; the
+ *   active set is taken as fixed.
+ *
+ * Every member of tt_track_extra may be NULL; extra == NULL or all members NULL is exactly the plain call.
+ * A sensitivity output without `dual` keeps the multipliers in a buffer of the handle (grown, never shrunk:
+ * like the other workspaces, calls on one handle must be serialised on ONE stream).  The solve, the export
+ * and the sensitivity kernel are enqueued on the same stream in that order.
+ * tt_solve_batch_ex: host pointers (also inside `extra`), synchronous.  tt_solve_batch_ex_device: device
+ * pointers inside a host-side struct, asynchronous on `stream`.  tt_track_sens_device: the sensitivity alone
+ * from device arrays x [B][N+1][6], u [B][N][2], dual, wq_wr (the solve's, or NULL) and status of an earlier
+ * tt_solve_batch_ex_device; the same kernel, so bitwise the fused call's outputs. */
+typedef struct { double* dual; double* gain; double* dxdx0; double* dudx0; int* sens_status; } tt_track_extra;
+long long tt_track_dual_len(int N);
+int tt_solve_batch_ex(void* handle, int B, const double* x0, const double* xref, const double* uref,
+                      const double* wq_wr, const double* z_guess, double* x_out, double* u_out, int* status,
+                      int* iters, double* kkt_res, const tt_track_extra* extra);
+int tt_solve_batch_ex_device(void* handle, int B, const double* d_x0, const double* d_xref, const double* d_uref,
+                             const double* d_wq_wr, const double* d_z_guess, double* d_x_out, double* d_u_out,
+                             int* d_status, int* d_iters, double* d_kkt_res, const tt_track_extra* d_extra,
+                             void* stream);
+int tt_track_sens_device(void* handle, int B, const double* d_x, const double* d_u, const double* d_dual,
+                         const double* d_wq_wr, const int* d_status, double* d_gain, double* d_dxdx0,
+                         double* d_dudx0, int* d_sens_status, void* stream);
 
 /* Replaces TrajectoryOptimization.plan (trajectory_optimization.py:311-331) for B scenarios of a
  * TT_VARIANT_OBCA_PLAN handle.  x0, xgoal [B][6] (ca.vertcat(initial_state, goal_state), 316-323);
