@@ -655,6 +655,119 @@ int tt_track_sens_device(void* handle, int B, const double* d_x, const double* d
     return sens_launch(h, B, d_x, d_u, d_dual, d_wq_wr, d_status, x, stream);
 }
 
+int tt_track_vjp_device(void* handle, int B, const double* d_x, const double* d_u, const double* d_dual,
+                        const double* d_xref, const double* d_uref, const double* d_wq_wr, const int* d_status,
+                        const double* d_grad_x, const double* d_grad_u, const tt_track_vjp_out* d_out, void* stream) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (!h) return fail(nullptr, -EINVAL, "NULL handle%s");
+    if (is_obca(h->cfg))
+        return fail(h, -EINVAL, "multipliers and sensitivities are exported by the tracking variants only%s");
+    if (B < 0) return fail(h, -EINVAL, "B must be >= 0%s");
+    if (!d_grad_x && !d_grad_u) return fail(h, -EINVAL, "grad_x and grad_u are both NULL: no loss to differentiate%s");
+    if (B == 0) return 0;
+    if (B > (1 << 30)) return fail(h, -EINVAL, "B too large%s");
+    if (!d_x || !d_u || !d_dual || !d_status || !d_out) return fail(h, -EINVAL, "NULL device buffer%s");
+    if (d_out->g_wq_wr && (!d_xref || !d_uref))
+        return fail(h, -EINVAL, "the weight gradient needs xref and uref of the solve%s");
+    if (h->cfg.variant == TT_VARIANT_FUZZY && !d_wq_wr)
+        return fail(h, -EINVAL, "fuzzy variant needs per-instance weights (mpc_control_fuzzy.py:54-58)%s");
+    DeviceGuard dg(h->device);
+    if (dg.err != hipSuccess) return hip_fail(h, dg.err, "hipSetDevice");
+    ttmpc::VjpArgs a;
+    memset(&a, 0, sizeof a);
+    a.N = h->cfg.N;
+    a.B = B;
+    a.dt = h->cfg.dt;
+    a.L1 = h->cfg.L1;
+    a.L2 = h->cfg.L2;
+    a.Mh = h->cfg.Mh;
+    memcpy(a.Q, h->Q, sizeof a.Q);
+    memcpy(a.R, h->R, sizeof a.R);
+    memcpy(a.xlb, h->xlb, sizeof a.xlb);
+    memcpy(a.xub, h->xub, sizeof a.xub);
+    memcpy(a.ulb, h->ulb, sizeof a.ulb);
+    memcpy(a.uub, h->uub, sizeof a.uub);
+    a.x = d_x;
+    a.u = d_u;
+    a.dual = d_dual;
+    a.xref = d_xref;
+    a.uref = d_uref;
+    a.wqwr = d_wq_wr;
+    a.status = d_status;
+    a.gx = d_grad_x;
+    a.gu = d_grad_u;
+    a.g_x0 = d_out->g_x0;
+    a.g_xref = d_out->g_xref;
+    a.g_uref = d_out->g_uref;
+    a.g_wqwr = d_out->g_wq_wr;
+    a.vjp_status = d_out->vjp_status;
+    const hipError_t e = ttmpc::launch_track_vjp(a, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(h, e, "adjoint kernel launch");
+    return 0;
+}
+
+int tt_track_vjp(void* handle, int B, const double* x, const double* u, const double* dual, const double* xref,
+                 const double* uref, const double* wq_wr, const int* status, const double* grad_x,
+                 const double* grad_u, const tt_track_vjp_out* out) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (!h) return fail(nullptr, -EINVAL, "NULL handle%s");
+    if (is_obca(h->cfg))
+        return fail(h, -EINVAL, "multipliers and sensitivities are exported by the tracking variants only%s");
+    if (B < 0) return fail(h, -EINVAL, "B must be >= 0%s");
+    if (!grad_x && !grad_u) return fail(h, -EINVAL, "grad_x and grad_u are both NULL: no loss to differentiate%s");
+    if (B == 0) return 0;
+    if (B > (1 << 30)) return fail(h, -EINVAL, "B too large%s");
+    if (!x || !u || !dual || !status || !out) return fail(h, -EINVAL, "NULL host buffer%s");
+    DeviceGuard dg(h->device);
+    if (dg.err != hipSuccess) return hip_fail(h, dg.err, "hipSetDevice");
+    // one device block: the eight double inputs, the four outputs, then the two int arrays (status, vjp_status)
+    const size_t N = h->cfg.N, b = (size_t)B, nx = b * (N + 1) * 6, nu = b * N * 2;
+    const double* src[8] = {x, u, dual, xref, uref, wq_wr, grad_x, grad_u};
+    const size_t len[8] = {nx, nu, b * (N + 1) * ttmpc::kDualPerStage, nx, nu, b * 8, nx, nu};
+    double* dst[4] = {out->g_x0, out->g_xref, out->g_uref, out->g_wq_wr};
+    const size_t olen[4] = {b * 6, nx, nu, b * 8};
+    size_t tot = b;  // the two int arrays
+    for (int t = 0; t < 8; ++t) tot += src[t] ? len[t] : 0;
+    for (int t = 0; t < 4; ++t) tot += dst[t] ? olen[t] : 0;
+    const int rc0 = ensure_block(h, h->d_ex, h->ex_cap, tot * 8, "adjoint staging");
+    if (rc0) return rc0;
+    hipStream_t s = h->stream;
+    double* p = reinterpret_cast<double*>(h->d_ex);
+    const double* din[8];
+    hipError_t e = hipSuccess;
+    for (int t = 0; t < 8; ++t) {
+        din[t] = src[t] ? p : nullptr;
+        if (src[t] && e == hipSuccess) e = hipMemcpyAsync(p, src[t], len[t] * 8, hipMemcpyHostToDevice, s);
+        if (src[t]) p += len[t];
+    }
+    tt_track_vjp_out dout = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    double** dmem[4] = {&dout.g_x0, &dout.g_xref, &dout.g_uref, &dout.g_wq_wr};
+    for (int t = 0; t < 4; ++t) {
+        if (dst[t]) { *dmem[t] = p; p += olen[t]; }
+    }
+    int* dst_st = reinterpret_cast<int*>(p);
+    if (out->vjp_status) dout.vjp_status = dst_st + b;
+    if (e == hipSuccess) e = hipMemcpyAsync(dst_st, status, b * sizeof(int), hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(s);
+        return hip_fail(h, e, "H2D copy");
+    }
+    const int rc = tt_track_vjp_device(handle, B, din[0], din[1], din[2], din[3], din[4], din[5], dst_st, din[6], din[7],
+                                       &dout, s);
+    if (rc) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    for (int t = 0; t < 4; ++t)
+        if (dst[t] && e == hipSuccess) e = hipMemcpyAsync(dst[t], *dmem[t], olen[t] * 8, hipMemcpyDeviceToHost, s);
+    if (out->vjp_status && e == hipSuccess)
+        e = hipMemcpyAsync(out->vjp_status, dout.vjp_status, b * sizeof(int), hipMemcpyDeviceToHost, s);
+    const hipError_t es = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return hip_fail(h, e, "adjoint");
+    return 0;
+}
+
 long long tt_track_dual_len(int N) { return N < 1 ? -EINVAL : (long long)ttmpc::kDualPerStage * (N + 1); }
 
 #ifdef TT_STAMPS

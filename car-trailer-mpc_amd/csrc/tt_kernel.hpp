@@ -83,6 +83,33 @@ struct SensArgs {
 inline int sens_lds_doubles(int N) { return 24 * (N + 1) + 12 * N + 192; }
 hipError_t launch_track_sens(const SensArgs& a, hipStream_t stream);
 
+// ---------------- adjoint of a tracking solution: dL/d(x_init, xref, uref, weights) (tt_vjp.hip) ----------------
+struct VjpArgs {
+    int N, B;
+    double dt, L1, L2, Mh;
+    double Q[36], R[4];
+    double xlb[6], xub[6], ulb[2], uub[2];  // raw bounds (relaxed in-kernel as track_kernel relaxes them)
+    const double* x;      // [B][N+1][6]
+    const double* u;      // [B][N][2]
+    const double* dual;   // [B][N+1][kDualPerStage]
+    const double* xref;   // [B][N+1][6]; read for g_wqwr only
+    const double* uref;   // [B][N][2];   read for g_wqwr only
+    const double* wqwr;   // [B][8] or nullptr
+    const int* status;    // [B] of the solve
+    const double* gx;     // [B][N+1][6] upstream dL/dX, or nullptr (zeros)
+    const double* gu;     // [B][N][2]   upstream dL/dU, or nullptr (zeros)
+    double* g_x0;         // [B][6] or nullptr
+    double* g_xref;       // [B][N+1][6] or nullptr
+    double* g_uref;       // [B][N][2] or nullptr
+    double* g_wqwr;       // [B][8] or nullptr
+    int* vjp_status;      // [B] or nullptr
+};
+// LDS doubles of one instance: 33 per stage (the 24 of the sensitivity record, the upstream gradient 8, one pad that
+// keeps the stage-parallel phases free of bank conflicts), 12 per input stage (K), and the tiles: 61.3 KB at N = 170
+constexpr int kVjpStage = 33, kVjpTiles = 164;
+inline int vjp_lds_doubles(int N) { return kVjpStage * (N + 1) + 12 * N + kVjpTiles; }
+hipError_t launch_track_vjp(const VjpArgs& a, hipStream_t stream);
+
 }  // namespace ttmpc
 
 namespace ttmpc {

@@ -22,30 +22,22 @@
 #include <math.h>
 
 #include "tt_kernel.hpp"
+#include "tt_sens_stage.hpp"
 
 #pragma clang fp contract(off)
 
 namespace ttmpc {
 namespace {
 
-constexpr int W = 64;
-constexpr int kStage = 24;  // per stage: dt*J (9) | curvature (7) | Sigma (8)
-constexpr int sAJ = 0, sWC = 9, sSG = 16;
+using sens::W;
+using sens::sAJ;
+using sens::sWC;
+using sens::sSG;
+using sens::d_idx;
+using sens::w_idx;
+constexpr int kStage = 24;  // per stage: dt*J (9) | curvature (7) | Sigma (8), tt_sens_stage.hpp
 // tiles behind the stage and gain records: P, M = P A, A, two Phi buffers, 2 R_w  (sens_lds_doubles: 24 S + 12 N + 192)
 constexpr int tP = 0, tM = 36, tA = 72, tF0 = 108, tF1 = 144, tRW = 180;
-
-// nonzero of dt*J at (r, c) (the order of tt_track.hip's rAJ rows), or -1
-__device__ __forceinline__ int d_idx(int r, int c) {
-    return (r == 0 && c == 2) ? 0 : (r == 0 && c == 5) ? 1 : (r == 1 && c == 2) ? 2 : (r == 1 && c == 5) ? 3
-         : (r == 2 && c == 4) ? 4 : (r == 2 && c == 5) ? 5 : (r == 3 && c == 3) ? 6 : (r == 3 && c == 4) ? 7
-         : (r == 3 && c == 5) ? 8 : -1;
-}
-// nonzero of the curvature at (i, j), symmetric (the order of tt_track.hip's rWC rows), or -1
-__device__ __forceinline__ int w_idx(int i, int j) {
-    if (i > j) { const int t = i; i = j; j = t; }
-    return (i == 2 && j == 2) ? 0 : (i == 2 && j == 5) ? 1 : (i == 3 && j == 3) ? 2 : (i == 3 && j == 4) ? 3
-         : (i == 3 && j == 5) ? 4 : (i == 4 && j == 4) ? 5 : (i == 4 && j == 5) ? 6 : -1;
-}
 
 __device__ __forceinline__ void zero_outputs(const SensArgs& a, int b, int lane) {
     const int N = a.N, S = N + 1;
@@ -76,48 +68,8 @@ __global__ __launch_bounds__(W) void track_sens_kernel(SensArgs a) {
     const double dt = a.dt;
 
     // ---- stage-parallel pre-pass ----
-    for (int k = lane; k <= N; k += W) {
-        double* r = stg + k * kStage;
-        const double* xk = x + k * 6;
-        const double* dk = dl + k * kDualPerStage;
-        for (int v = 0; v < 8; ++v) {
-            double sg = 0.0;
-            if (v < 6 || k < N) {
-                const double val = v < 6 ? xk[v] : u[k * 2 + (v - 6)];
-                const double l = v < 6 ? a.xlb[v] : a.ulb[v - 6], ub = v < 6 ? a.xub[v] : a.uub[v - 6];
-                if (isfinite(l) && l > -1e19) sg += dk[6 + v] / (val - (l - 1e-8 * fmax(1.0, fabs(l))));
-                if (isfinite(ub) && ub < 1e19) sg += dk[14 + v] / ((ub + 1e-8 * fmax(1.0, fabs(ub))) - val);
-            }
-            r[sSG + v] = sg;
-        }
-        if (k < N) {
-            const double* y = dk + kDualPerStage;  // y_{k+1}
-            const double iL1 = 1.0 / a.L1, iL2 = 1.0 / a.L2, iL1L2 = iL1 * iL2, Mh = a.Mh;
-            double sth, cth, sps, cps, sph, cph;
-            sincos(xk[2], &sth, &cth);
-            sincos(xk[3], &sps, &cps);
-            sincos(xk[4], &sph, &cph);
-            const double v = xk[5], ic = 1.0 / cph, t = sph * ic, c2 = ic * ic;
-            const double kk = 1.0 + Mh * iL2 * cps;
-            r[sAJ + 0] = dt * (-v * sth);
-            r[sAJ + 1] = dt * cth;
-            r[sAJ + 2] = dt * (v * cth);
-            r[sAJ + 3] = dt * sth;
-            r[sAJ + 4] = dt * (v * c2 * iL1);
-            r[sAJ + 5] = dt * (t * iL1);
-            r[sAJ + 6] = dt * (v * t * Mh * sps * iL1L2 - v * cps * iL2);
-            r[sAJ + 7] = dt * (-v * c2 * iL1 * kk);
-            r[sAJ + 8] = dt * (-t * iL1 * kk - sps * iL2);
-            const double s = -dt;
-            r[sWC + 0] = s * (y[0] * (-v * cth) + y[1] * (-v * sth));
-            r[sWC + 1] = s * (y[0] * (-sth) + y[1] * cth);
-            r[sWC + 2] = s * (y[3] * (v * t * Mh * cps * iL1L2 + v * sps * iL2));
-            r[sWC + 3] = s * (y[3] * (v * c2 * Mh * sps * iL1L2));
-            r[sWC + 4] = s * (y[3] * (t * Mh * sps * iL1L2 - cps * iL2));
-            r[sWC + 5] = s * (y[2] * (2.0 * v * t * c2 * iL1) + y[3] * (-2.0 * v * t * c2 * kk * iL1));
-            r[sWC + 6] = s * (y[2] * (c2 * iL1) + y[3] * (-c2 * kk * iL1));
-        }
-    }
+    for (int k = lane; k <= N; k += W)
+        sens::linearise_stage(a, stg + k * kStage, x + k * 6, u + k * 2, dl + k * kDualPerStage, k == N);
     // ---- entry-parallel roles ----
     const bool ent = lane < 36, gl = lane >= 36 && lane < 48;
     const int i = ent ? lane / 6 : 0, j = ent ? lane % 6 : 0;

@@ -45,8 +45,24 @@ class TTTrackExtra(C.Structure):
                 ("sens_status", C.c_void_p)]
 
 
+class TTTrackVjpOut(C.Structure):
+    """tt_track_vjp_out (include/ttmpc.h): the outputs of tt_track_vjp*; NULL members are skipped."""
+    _fields_ = [("g_x0", C.c_void_p), ("g_xref", C.c_void_p), ("g_uref", C.c_void_p), ("g_wq_wr", C.c_void_p),
+                ("vjp_status", C.c_void_p)]
+
+
 class TTError(RuntimeError):
     pass
+
+
+class TrackVjpResult:
+    """What ``BatchSolver.vjp`` returns: g_x0 (B,6) = dL/dx0, g_xref (B,N+1,6), g_uref (B,N,2), g_wq_wr (B,8) and
+    vjp_status (B,) (0 ok, 1 undefined, 2 solve not successful; the gradients of a failed instance are zeros)."""
+    __slots__ = ("g_x0", "g_xref", "g_uref", "g_wq_wr", "vjp_status")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
 
 
 class TrackExResult:
@@ -108,6 +124,13 @@ def lib():
         L.tt_track_sens_device.restype = C.c_int
         L.tt_track_dual_len.argtypes = [C.c_int]
         L.tt_track_dual_len.restype = C.c_longlong
+    if not os.environ.get("TTMPC_LIB") or hasattr(L, "tt_track_vjp_device"):  # (A/B against a build without them)
+        L.tt_track_vjp_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 9 + [C.POINTER(TTTrackVjpOut),
+                                                                                    C.c_void_p]
+        L.tt_track_vjp_device.restype = C.c_int
+        L.tt_track_vjp.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp,
+                                   C.POINTER(TTTrackVjpOut)]
+        L.tt_track_vjp.restype = C.c_int
     L.tt_plan_batch.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _ip]
     L.tt_plan_batch.restype = C.c_int
     L.tt_obca_solve_batch.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp]
@@ -170,7 +193,8 @@ EXPORTED_SYMBOLS = ("tt_create", "tt_solve_batch", "tt_solve_batch_device", "tt_
                     "tt_record_solution_device", "tt_interpolate_device", "tt_lqr_score_device",
                     "tt_sim_window_indexed_device", "tt_sim_log_advance_device", "tt_policy_plant_device",
                     "tt_fuzzy_weights_device", "tt_plant_update_noise_device", "tt_policy_plant_noise_device",
-                    "tt_track_dual_len", "tt_solve_batch_ex", "tt_solve_batch_ex_device", "tt_track_sens_device")
+                    "tt_track_dual_len", "tt_solve_batch_ex", "tt_solve_batch_ex_device", "tt_track_sens_device",
+                    "tt_track_vjp_device", "tt_track_vjp")
 
 
 def _ptr(a):
@@ -362,6 +386,43 @@ class BatchSolver:
                                           dxdx0 or None, dudx0 or None, sens_status or None, stream or None)
         if rc != 0:
             self._err(rc, "tt_track_sens_device")
+
+    def vjp_device(self, B, x, u, dual, xref, uref, status, grad_x=0, grad_u=0, g_x0=0, g_xref=0, g_uref=0, g_wq_wr=0,
+                   vjp_status=0, wq_wr=0, stream=0):
+        """tt_track_vjp_device: the adjoint kernel on device arrays of an earlier ``solve_ex_device`` (its x, u, dual,
+        status, and its inputs xref, uref, wq_wr) and the upstream gradients grad_x = dL/dX, grad_u = dL/dU (0 = zeros,
+        not both).  Outputs (0 = not wanted): g_x0, g_xref, g_uref, g_wq_wr, vjp_status.  Uses no buffer of the handle:
+        any stream will do, behind the solve whose outputs it reads."""
+        out = TTTrackVjpOut(g_x0 or None, g_xref or None, g_uref or None, g_wq_wr or None, vjp_status or None)
+        rc = self._L.tt_track_vjp_device(self._h, int(B), x, u, dual, xref or None, uref or None, wq_wr or None, status,
+                                         grad_x or None, grad_u or None, C.byref(out), stream or None)
+        if rc != 0:
+            self._err(rc, "tt_track_vjp_device")
+
+    def vjp(self, x, u, dual, xref, uref, status, grad_x, grad_u, wq_wr=None):
+        """Host arrays: the gradient of a scalar loss L(X, U) with respect to the inputs of the solve that returned
+        x (B,N+1,6), u (B,N,2), dual (B,N+1,22) and status (B,) for xref, uref and wq_wr; grad_x (B,N+1,6) = dL/dX and
+        grad_u (B,N,2) = dL/dU (either may be None for zeros).  Returns a ``TrackVjpResult``."""
+        N = self.N
+        x = _f64(x)
+        B = x.shape[0] if x.ndim == 3 else 1
+        x = x.reshape(B, N + 1, 6)
+        u = _f64(u, (B, N, 2))
+        dual = _f64(dual, (B, N + 1, 22))
+        xref = _f64(xref, (B, N + 1, 6))
+        uref = _f64(uref, (B, N, 2))
+        st = np.ascontiguousarray(np.asarray(status, dtype=np.int32)).reshape(B)
+        gx = None if grad_x is None else _f64(grad_x, (B, N + 1, 6))
+        gu = None if grad_u is None else _f64(grad_u, (B, N, 2))
+        w = None if wq_wr is None else _f64(wq_wr, (B, 8))
+        r = TrackVjpResult(g_x0=np.empty((B, 6)), g_xref=np.empty((B, N + 1, 6)), g_uref=np.empty((B, N, 2)),
+                           g_wq_wr=np.empty((B, 8)), vjp_status=np.empty(B, dtype=np.int32))
+        out = TTTrackVjpOut(*[a.ctypes.data for a in (r.g_x0, r.g_xref, r.g_uref, r.g_wq_wr, r.vjp_status)])
+        rc = self._L.tt_track_vjp(self._h, B, _ptr(x), _ptr(u), _ptr(dual), _ptr(xref), _ptr(uref), _ptr(w),
+                                  st.ctypes.data_as(_ip), _ptr(gx), _ptr(gu), C.byref(out))
+        if rc != 0:
+            self._err(rc, "tt_track_vjp")
+        return r
 
 
 def obca_n(N: int, M: int) -> int:

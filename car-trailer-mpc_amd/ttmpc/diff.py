@@ -1,0 +1,94 @@
+"""Differentiable tracking solve for PyTorch: the batched MPC solve as an autograd node.
+
+``DifferentiableTracking(solver)`` wraps a ``BatchSolver`` of a tracking variant.  Forward is one
+``solve_ex_device`` (the solve with its multipliers), backward one ``vjp_device`` (track_vjp_kernel): for a scalar loss
+L(X, U) it returns dL/d(x0, xref, uref, wq_wr) as sIPOPT defines the sensitivity of the solution, from one Riccati pass
+at the returned primal-dual point (include/ttmpc.h, "Reverse mode").  First order: the active set is taken as fixed.
+Both run on ``torch.cuda.current_stream()`` without any host synchronisation.
+"""
+from __future__ import annotations
+
+import torch
+
+__all__ = ["TrackingSolveFunction", "DifferentiableTracking"]
+
+
+def _ptr(t):
+    return 0 if t is None else t.data_ptr()
+
+
+def _check(name, t, shape):
+    if not (t.is_cuda and t.dtype == torch.float64):
+        raise TypeError(f"{name} must be a float64 CUDA tensor, got {t.dtype} on {t.device}")
+    if tuple(t.shape) != shape:
+        raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+    return t.detach().contiguous()
+
+
+class TrackingSolveFunction(torch.autograd.Function):
+    """``X, U, status = TrackingSolveFunction.apply(solver, x0, xref, uref, wq_wr, z_guess)``.
+
+    x0 (B,6), xref (B,N+1,6), uref (B,N,2), wq_wr (B,8) or None, z_guess (B,8N+6) or None: float64 CUDA tensors on the
+    solver's device.  X (B,N+1,6) and U (B,N,2) are differentiable with respect to x0, xref, uref and wq_wr; status
+    (B,) int32 is not, and z_guess gets no gradient (it does not move a converged solution).  An instance whose solve
+    status is above TT_ACCEPTABLE, or whose adjoint is undefined, contributes a zero gradient."""
+
+    @staticmethod
+    def forward(ctx, solver, x0, xref, uref, wq_wr, z_guess):
+        N, B = solver.N, x0.shape[0]
+        x0 = _check("x0", x0, (B, 6))
+        xref = _check("xref", xref, (B, N + 1, 6))
+        uref = _check("uref", uref, (B, N, 2))
+        wq_wr = None if wq_wr is None else _check("wq_wr", wq_wr, (B, 8))
+        z_guess = None if z_guess is None else _check("z_guess", z_guess, (B, 8 * N + 6))
+        dev = x0.device
+        X = torch.empty((B, N + 1, 6), dtype=torch.float64, device=dev)
+        U = torch.empty((B, N, 2), dtype=torch.float64, device=dev)
+        dual = torch.empty((B, N + 1, 22), dtype=torch.float64, device=dev)
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        solver.solve_ex_device(B, x0.data_ptr(), xref.data_ptr(), uref.data_ptr(), X.data_ptr(), U.data_ptr(),
+                               status.data_ptr(), wq_wr=_ptr(wq_wr), z_guess=_ptr(z_guess), dual=dual.data_ptr(),
+                               stream=torch.cuda.current_stream(dev).cuda_stream)
+        ctx.solver = solver
+        ctx.has_w = wq_wr is not None
+        ctx.save_for_backward(X, U, dual, status, xref, uref, *(() if wq_wr is None else (wq_wr,)))
+        ctx.mark_non_differentiable(status)
+        return X, U, status
+
+    @staticmethod
+    def backward(ctx, grad_X, grad_U, _grad_status):
+        X, U, dual, status, xref, uref = ctx.saved_tensors[:6]
+        wq_wr = ctx.saved_tensors[6] if ctx.has_w else None
+        need = ctx.needs_input_grad  # (solver, x0, xref, uref, wq_wr, z_guess)
+        if grad_X is None and grad_U is None:
+            return (None,) * 6
+        B, N, dev = X.shape[0], ctx.solver.N, X.device
+        gX = None if grad_X is None else grad_X.to(torch.float64).contiguous()
+        gU = None if grad_U is None else grad_U.to(torch.float64).contiguous()
+        new = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)  # noqa: E731
+        g_x0 = new(B, 6) if need[1] else None
+        g_xref = new(B, N + 1, 6) if need[2] else None
+        g_uref = new(B, N, 2) if need[3] else None
+        g_w = new(B, 8) if need[4] else None
+        ctx.solver.vjp_device(B, X.data_ptr(), U.data_ptr(), dual.data_ptr(), xref.data_ptr(), uref.data_ptr(),
+                              status.data_ptr(), grad_x=_ptr(gX), grad_u=_ptr(gU), g_x0=_ptr(g_x0), g_xref=_ptr(g_xref),
+                              g_uref=_ptr(g_uref), g_wq_wr=_ptr(g_w), wq_wr=_ptr(wq_wr),
+                              stream=torch.cuda.current_stream(dev).cuda_stream)
+        return None, g_x0, g_xref, g_uref, g_w, None
+
+
+class DifferentiableTracking:
+    """``X, U, status = layer(x0, xref, uref, wq_wr=None, z_guess=None)`` with float64 CUDA tensors.
+
+    A thin callable over ``TrackingSolveFunction`` for one ``BatchSolver`` (TT_VARIANT_TRACK, _NMPC or _FUZZY; the
+    fuzzy variant needs wq_wr).  One handle serialises its solves on one stream: the forward uses workspaces of the
+    handle, so every forward of one layer must be enqueued on the same stream (and a second layer wants its own
+    solver).  The backward uses no buffer of the handle and may run on any stream that is ordered behind the forward,
+    as autograd's stream bookkeeping arranges.  Look at ``status`` (and at ``solver.vjp_device(..., vjp_status=...)``
+    when in doubt) to see which instances gave a gradient: failed ones give zeros."""
+
+    def __init__(self, solver):
+        self.solver = solver
+
+    def __call__(self, x0, xref, uref, wq_wr=None, z_guess=None):
+        return TrackingSolveFunction.apply(self.solver, x0, xref, uref, wq_wr, z_guess)

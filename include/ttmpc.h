@@ -144,6 +144,47 @@ int tt_track_sens_device(void* handle, int B, const double* d_x, const double* d
                          const double* d_wq_wr, const int* d_status, double* d_gain, double* d_dxdx0,
                          double* d_dudx0, int* d_sens_status, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Reverse mode (vector-Jacobian product) of a tracking solve: for a scalar loss L(X, U) over the outputs of a
+ * solve, its gradient with respect to the solve's inputs x_init, xref, uref and wq_wr in one pass.  Same
+ * variants as above (an OBCA handle returns -EINVAL), same Newton matrix K = [[W + Sigma, J'], [J, 0]] at the
+ * returned primal-dual point, same definition as sIPOPT's sensitivity ds/dtheta = -K^-1 dF/dtheta.  K is
+ * symmetric, so with the upstream gradient g = dL/d(X, U):
+ *     K (lam_z, lam_y) = (g, 0),     dL/dtheta = -lam' dF/dtheta          (one Riccati pass, no regularisation)
+ *
+ * Inputs: x [B][N+1][6], u [B][N][2], dual [B][N+1][22], wq_wr [B][8] or NULL and status [B] exactly as
+ * tt_solve_batch_ex* returned or took them, xref [B][N+1][6] and uref [B][N][2] of that solve, and
+ *     grad_x [B][N+1][6]  dL/dx_k          grad_u [B][N][2]  dL/du_k
+ *   A NULL grad_x or grad_u stands for zeros; both NULL is -EINVAL.
+ * Outputs (tt_track_vjp_out; every member may be NULL):
+ *     g_x0    [B][6]        dL/dx_init
+ *     g_xref  [B][N+1][6]   dL/dxref_k = 2 Q_w lam_x,k   (row k = 0 is exactly 0: x_0 is pinned to x_init)
+ *     g_uref  [B][N][2]     dL/duref_k = 2 R_w lam_u,k
+ *     g_wq_wr [B][8]        dL/dwq_i (6), dL/dwr_i (2), Q_w = diag(wq) Q_s diag(wq), R_w likewise, Q_s the
+ *                           symmetrised Q.  With wq_wr == NULL the weights are ones and this is the gradient with
+ *                           respect to such a diagonal scaling of Q and R.  xref and uref are read for this
+ *                           output only (without it they may be NULL).
+ *     vjp_status [B]        as sens_status: 0 ok; 1 a reduced input Hessian was not positive definite or a value
+ *                           (an upstream gradient entry included) was not finite; 2 the solve's status is above
+ *                           TT_ACCEPTABLE (skipped).  For 1 and 2 the instance's four arrays are zeroed, so a
+ *                           failed instance contributes nothing to a batch gradient.
+ *   Signs: the arrays are gradients of L (descent moves a parameter against them); a positive g_x0 entry means
+ *   L grows with that x_init entry.
+ *   First order only, as above: the active set is taken as fixed, and a variable sitting on a bound carries
+ *   (numerically) zero lam, so a loss on it has no gradient.
+ *
+ * tt_track_vjp_device: device pointers (inside the host-side struct too), asynchronous on `stream`.  It uses
+ * no buffer of the handle, so it may run on any stream, also beside a solve of the same handle on another
+ * stream; the caller orders it behind the solve whose outputs it reads.  tt_track_vjp: the same with host
+ * pointers, synchronous (it stages through a buffer of the handle: one host call per handle at a time). */
+typedef struct { double* g_x0; double* g_xref; double* g_uref; double* g_wq_wr; int* vjp_status; } tt_track_vjp_out;
+int tt_track_vjp_device(void* handle, int B, const double* d_x, const double* d_u, const double* d_dual,
+                        const double* d_xref, const double* d_uref, const double* d_wq_wr, const int* d_status,
+                        const double* d_grad_x, const double* d_grad_u, const tt_track_vjp_out* d_out, void* stream);
+int tt_track_vjp(void* handle, int B, const double* x, const double* u, const double* dual, const double* xref,
+                 const double* uref, const double* wq_wr, const int* status, const double* grad_x,
+                 const double* grad_u, const tt_track_vjp_out* out);
+
 /* Replaces TrajectoryOptimization.plan (trajectory_optimization.py:311-331) for B scenarios of a
  * TT_VARIANT_OBCA_PLAN handle.  x0, xgoal [B][6] (ca.vertcat(initial_state, goal_state), 316-323);
  * z_guess [B][n], n = N(8+16M)+6+16M, the reference's interleaved [x_k,u_k,mu_k,lam_k] vector
