@@ -172,7 +172,9 @@ def lib():
            "tt_policy_plant_device": [i, C.POINTER(TTPlant), i, vp, vp, ll, vp, vp, vp, vp, vp, vp, vp],
            "tt_plant_update_noise_device": [i, C.POINTER(TTPlant), vp, vp, ll, vp, i, vp, vp, vp],
            "tt_policy_plant_noise_device": [i, C.POINTER(TTPlant), i, vp, vp, ll, vp, vp, vp, vp, vp, vp, vp, vp],
-           "tt_fuzzy_weights_device": [i, i, vp, vp, vp, vp]}
+           "tt_fuzzy_weights_device": [i, i, vp, vp, vp, vp],
+           "tt_policy_plant_vjp_device": [i, i, C.POINTER(TTPlant), i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+           "tt_sim_window_vjp_device": [i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]}
     sim["ttx_obca_set_helpers"] = [C.c_void_p, i]  # diagnostics (not in include/ttmpc.h)
     sim["ttx_obca_set_handoff_debug"] = [C.c_void_p, ll, i]
     for name, args in sim.items():
@@ -194,7 +196,7 @@ EXPORTED_SYMBOLS = ("tt_create", "tt_solve_batch", "tt_solve_batch_device", "tt_
                     "tt_sim_window_indexed_device", "tt_sim_log_advance_device", "tt_policy_plant_device",
                     "tt_fuzzy_weights_device", "tt_plant_update_noise_device", "tt_policy_plant_noise_device",
                     "tt_track_dual_len", "tt_solve_batch_ex", "tt_solve_batch_ex_device", "tt_track_sens_device",
-                    "tt_track_vjp_device", "tt_track_vjp")
+                    "tt_track_vjp_device", "tt_track_vjp", "tt_policy_plant_vjp_device", "tt_sim_window_vjp_device")
 
 
 def _ptr(a):

@@ -1,16 +1,21 @@
-"""Differentiable tracking solve for PyTorch: the batched MPC solve as an autograd node.
+"""Differentiable tracking solve and differentiable closed loop for PyTorch: autograd nodes over the batched MPC solve.
 
 ``DifferentiableTracking(solver)`` wraps a ``BatchSolver`` of a tracking variant.  Forward is one
 ``solve_ex_device`` (the solve with its multipliers), backward one ``vjp_device`` (track_vjp_kernel): for a scalar loss
 L(X, U) it returns dL/d(x0, xref, uref, wq_wr) as sIPOPT defines the sensitivity of the solution, from one Riccati pass
 at the returned primal-dual point (include/ttmpc.h, "Reverse mode").  First order: the active set is taken as fixed.
 Both run on ``torch.cuda.current_stream()`` without any host synchronisation.
+
+``DifferentiableClosedLoop(loop)`` wraps a ``ttmpc.simulation.ClosedLoop``: forward is ``run_tape`` (K closed-loop steps
+with every solve taped on the device), backward is ``ClosedLoop.backward`` (the plant, policy and window adjoints around
+one ``vjp_device`` per step).  For a scalar loss on the visited states S and the applied controls Ua it returns
+dL/d(x_init, wq_wr, plan_x, plan_u, noise).
 """
 from __future__ import annotations
 
 import torch
 
-__all__ = ["TrackingSolveFunction", "DifferentiableTracking"]
+__all__ = ["TrackingSolveFunction", "DifferentiableTracking", "ClosedLoopFunction", "DifferentiableClosedLoop"]
 
 
 def _ptr(t):
@@ -92,3 +97,61 @@ class DifferentiableTracking:
 
     def __call__(self, x0, xref, uref, wq_wr=None, z_guess=None):
         return TrackingSolveFunction.apply(self.solver, x0, xref, uref, wq_wr, z_guess)
+
+
+class ClosedLoopFunction(torch.autograd.Function):
+    """``S, Ua, status = ClosedLoopFunction.apply(loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise)``.
+
+    x_init (B,6), wq_wr (B,8) or None, plan_x (P,Np+1,6) and plan_u (P,Np,2) with P = 1 (shared) or B, or None for the
+    loop's own plan, noise (K,B,6) or None: float64 CUDA tensors on the loop's device.  S (K+1,B,6) and Ua (K,B,2) are
+    differentiable with respect to all five; status (K,B) int32 is not."""
+
+    @staticmethod
+    def forward(ctx, loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise):
+        if (plan_x is None) != (plan_u is None):
+            raise ValueError("give plan_x and plan_u together")
+        B = x_init.shape[0]
+        x_init = _check("x_init", x_init, (B, 6))
+        if plan_x is not None:
+            Np = plan_u.shape[-2]
+            P = plan_x.shape[0]
+            if plan_x.dim() != 3 or P not in (1, B):
+                raise ValueError("plan_x must be (1, Np+1, 6) for a shared plan or (B, Np+1, 6)")
+            loop.plan_x, loop.plan_u = _check("plan_x", plan_x, (P, Np + 1, 6)), _check("plan_u", plan_u, (P, Np, 2))
+        out = loop.run_tape(x_init, T_sim, noise=noise, wq_wr=wq_wr)
+        tape = out["tape"]
+        ctx.loop, ctx.tape = loop, tape
+        status = tape.status.clone()   # (copies: the node keeps the tape, the outputs must not keep the node)
+        ctx.mark_non_differentiable(status)
+        return tape.S.clone(), tape.Ua.clone(), status
+
+    @staticmethod
+    def backward(ctx, grad_S, grad_Ua, _grad_status):
+        need = ctx.needs_input_grad  # (loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise)
+        tape = ctx.tape
+        if grad_S is None and grad_Ua is None:
+            return (None,) * 7
+        GS = torch.zeros_like(tape.S) if grad_S is None else grad_S.to(torch.float64).contiguous()
+        GU = torch.zeros_like(tape.Ua) if grad_Ua is None else grad_Ua.to(torch.float64).contiguous()
+        g = ctx.loop.backward(tape, GS, GU)
+        pick = lambda i, k: g[k] if need[i] else None  # noqa: E731
+        return (None, None, pick(2, "g_x_init"), pick(3, "g_wq_wr"), pick(4, "g_plan_x"), pick(5, "g_plan_u"),
+                pick(6, "g_noise"))
+
+
+class DifferentiableClosedLoop:
+    """``S, Ua, status = layer(x_init, T_sim, wq_wr=None, plan_x=None, plan_u=None, noise=None)``.
+
+    A thin callable over ``ClosedLoopFunction`` for one ``ClosedLoop`` whose solver is TT_VARIANT_TRACK or
+    TT_VARIANT_NMPC (any of the three failure policies, warm start on or off, measurement or in-plant noise, shared or
+    per-instance plan).  A TT_VARIANT_FUZZY solver and a switch solver raise ValueError.  A plan given here replaces
+    the loop's.  The forward synchronises once at its end, as ``run`` does; the backward does not.  Zero gradient comes
+    from: failed solves (whatever the policy then applies), stopped instances, variables sitting on a bound, and the
+    warm start (z_guess does not move a converged solution)."""
+
+    def __init__(self, loop):
+        loop._check_differentiable()
+        self.loop = loop
+
+    def __call__(self, x_init, T_sim, wq_wr=None, plan_x=None, plan_u=None, noise=None):
+        return ClosedLoopFunction.apply(self.loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise)

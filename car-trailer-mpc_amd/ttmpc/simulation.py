@@ -15,9 +15,14 @@ MPCTrackingControlObs (the OBCA kernel) and their results replace the tracking s
 
 The reference draws the measurement noise with np.random.normal; pass ``noise`` (steps, B, 6) to
 reproduce a given draw, else it is drawn on the device with a seeded torch generator.
+
+Reverse mode: ``ClosedLoop.run_tape`` keeps every step's solve on the device and ``ClosedLoop.backward`` sweeps that
+tape for the gradient of a loss on the visited states and applied controls with respect to x_init, the weights, the
+plan and the noise (tt_sim_vjp.hip around tt_vjp.hip; ``ttmpc.diff.DifferentiableClosedLoop`` is the autograd layer).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 
@@ -149,6 +154,66 @@ def interpolate(state_traj, input_traj, dt_1, dt_2, stream=None):
     return so, uo
 
 
+def policy_plant_vjp(state, status, active_after, consecutive, adj_state, adj_u_last, grad_u, params,
+                     disturbance_params=None, policy="track", active_before=None, grad_u_applied=None,
+                     g_state_noise=None, stream=None):
+    """Adjoint of one policy + plant step (tt_policy_plant_vjp_device; include/ttmpc.h has the branch table), device
+    tensors: state (B,6) = S_t, status / active_after / consecutive (B,) int32 from the logs, active_before (B,) or None
+    (the first step: all active), grad_u_applied (B,2) = dL/dUa_t or None.  In place: adj_state (B,6) = dL/dS_{t+1}
+    becomes the plant's share of dL/dS_t, adj_u_last (B,2) the adjoint of u_last; grad_u (B,N,2) gets the seed
+    dL/dU_t[0] in row 0; g_state_noise (B,6), if given, dL/d(in-plant noise)."""
+    dev = state.device
+    if policy not in POLICIES:
+        raise ValueError(f"policy must be one of {sorted(POLICIES)}")
+    p = plant(params, disturbance_params)
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    _check(lib().tt_policy_plant_vjp_device(state.shape[0], grad_u.shape[1], C.byref(p), POLICIES[policy],
+                                            state.data_ptr(), status.data_ptr(), ptr(active_before),
+                                            active_after.data_ptr(), consecutive.data_ptr(), ptr(grad_u_applied),
+                                            adj_state.data_ptr(), adj_u_last.data_ptr(), grad_u.data_ptr(),
+                                            ptr(g_state_noise), _stream(stream, dev)), "tt_policy_plant_vjp_device")
+    return adj_state, adj_u_last, grad_u
+
+
+def window_vjp(g_xref, g_uref, k, Np, g_plan_x=None, g_plan_u=None, shared=False, g_x0=None, grad_state=None,
+               adj_state=None, g_wq_wr=None, g_wq_wr_acc=None, g_meas_noise=None, stream=None):
+    """Adjoint of ``window`` at step index k (tt_sim_window_vjp_device): g_xref (B,N+1,6), g_uref (B,N,2) are
+    scatter-added, with the forward's end padding and without atomics, into the per-instance plan gradients g_plan_x
+    (B,Np+1,6), g_plan_u (B,Np,2) (made of zeros when None).  shared=True returns their sums over B, (1,Np+1,6) and
+    (1,Np,2), the gradient of one plan shared by all instances.  The step's per-instance accumulation rides along when
+    asked for: adj_state += g_x0 + grad_state, g_wq_wr_acc += g_wq_wr, g_meas_noise = g_x0."""
+    dev = g_xref.device
+    B, N = g_uref.shape[0], g_uref.shape[1]
+    z = lambda *sh: torch.zeros(sh, dtype=torch.float64, device=dev)  # noqa: E731
+    g_plan_x = z(B, Np + 1, 6) if g_plan_x is None else g_plan_x
+    g_plan_u = z(B, Np, 2) if g_plan_u is None else g_plan_u
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    _check(lib().tt_sim_window_vjp_device(B, N, int(k), int(Np), g_xref.data_ptr(), g_uref.data_ptr(),
+                                          g_plan_x.data_ptr(), g_plan_u.data_ptr(), ptr(g_x0), ptr(grad_state),
+                                          ptr(adj_state), ptr(g_wq_wr), ptr(g_wq_wr_acc), ptr(g_meas_noise),
+                                          _stream(stream, dev)), "tt_sim_window_vjp_device")
+    if shared:
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            return g_plan_x.sum(dim=0, keepdim=True), g_plan_u.sum(dim=0, keepdim=True)
+    return g_plan_x, g_plan_u
+
+
+class LoopTape:
+    """What ``ClosedLoop.run_tape`` keeps on the device for ``ClosedLoop.backward``: the step indices ks, the logs S
+    (K+1,B,6), Ua (K,B,2), status / active / consec (K,B) (active and the consecutive-failure count after each step),
+    each step's solve X (K,B,N+1,6), U (K,B,N,2), dual (K,B,N+1,22), the noise it used (K,B,6) or None, the weights
+    wq_wr (B,8) or None, and the plan the run saw."""
+    __slots__ = ("ks", "S", "Ua", "status", "active", "consec", "X", "U", "dual", "noise", "wq_wr", "plan_x", "plan_u")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in (getattr(self, k) for k in self.__slots__)
+                   if isinstance(t, torch.Tensor))
+
+
 def step_indices(T_sim, dt):
     """The reference's step sequence: t = 0; while t <= T_sim: k = floor(t/dt); ...; t += dt."""
     ks, t = [], 0.0
@@ -255,10 +320,11 @@ class ClosedLoop:
             got = (tuple(noise.shape), noise.dtype, noise.device) if isinstance(noise, torch.Tensor) else type(noise)
             raise ValueError(f"noise must be a float64 tensor of shape {tuple(shape)} on {self.dev}, got {got}")
 
-    def step(self, k, noise=None):
+    def step(self, k, noise=None, dual=None, wq_wr=None):
         """Enqueue one closed-loop step at window index k (noise: (B,6) float64 device tensor or None: the measurement
         noise, or with noise_in_plant -- the default of the "nmpc" / "fuzzy" policies -- the plant's process noise
-        before its dt factor)."""
+        before its dt factor).  dual (B,N+1,22): also export the solve's multipliers (run_tape; the solve is bitwise
+        the plain one); wq_wr (B,8): per-instance weights of a solver that is not TT_VARIANT_FUZZY."""
         L, s, B, N = lib(), self.stream, self.B, self.N
         sp = C.c_void_p(s.cuda_stream)
         if noise is not None:
@@ -282,9 +348,17 @@ class ClosedLoop:
                 _check(L.tt_fuzzy_weights_device(B, N, self.x_meas.data_ptr(), self.xref.data_ptr(), self.wq.data_ptr(),
                                                  sp), "tt_fuzzy_weights_device")
                 wq = self.wq.data_ptr()
-            self.solver.solve_device(B, self.x_meas.data_ptr(), self.xref.data_ptr(), self.uref.data_ptr(),
-                                     self.X.data_ptr(), self.U.data_ptr(), self.st.data_ptr(), self.it.data_ptr(),
-                                     self.kkt.data_ptr(), wq_wr=wq, z_guess=zg, stream=s.cuda_stream)
+            elif wq_wr is not None:
+                wq = wq_wr.data_ptr()
+            if dual is None:
+                self.solver.solve_device(B, self.x_meas.data_ptr(), self.xref.data_ptr(), self.uref.data_ptr(),
+                                         self.X.data_ptr(), self.U.data_ptr(), self.st.data_ptr(), self.it.data_ptr(),
+                                         self.kkt.data_ptr(), wq_wr=wq, z_guess=zg, stream=s.cuda_stream)
+            else:
+                self.solver.solve_ex_device(B, self.x_meas.data_ptr(), self.xref.data_ptr(), self.uref.data_ptr(),
+                                            self.X.data_ptr(), self.U.data_ptr(), self.st.data_ptr(),
+                                            self.it.data_ptr(), self.kkt.data_ptr(), wq_wr=wq, z_guess=zg,
+                                            dual=dual.data_ptr(), stream=s.cuda_stream)
             if self.fuzzy:
                 self._fuzzy_retry(s)
             if self.switch is not None and self.check_collision:
@@ -472,6 +546,131 @@ class ClosedLoop:
         return dict(pol, k=np.array(ks), states=S.cpu().numpy(), controls=Ua.cpu().numpy(), status=Ss.cpu().numpy(),
                     iters=Si.cpu().numpy(), collide=Sc.cpu().numpy().astype(bool),
                     success=Ss.cpu().numpy() <= TT_ACCEPTABLE, active=act.astype(bool), stop_step=stop)
+
+    # ---------------- reverse mode: taped run and backward sweep ----------------
+    def _check_differentiable(self):
+        if self.fuzzy:
+            raise ValueError("the closed loop of a TT_VARIANT_FUZZY solver is not differentiable here: its weights "
+                             "depend on the measured state and its retry compacts the failed instances on the host")
+        if self.switch is not None:
+            raise ValueError("the closed loop with a switch solver is not differentiable: the OBCA solve has no adjoint")
+
+    def run_tape(self, x_init, T_sim, noise=None, wq_wr=None):
+        """``run`` that also keeps what ``backward`` needs: the same steps with the solve's multipliers exported
+        (solve_ex_device: bitwise the plain solve) and each step's X, U, dual copied to a ``LoopTape`` on the device,
+        (30 (N+1) - 2) * 8 bytes per instance and step.  wq_wr: constant per-instance weights (B,8), host or device.
+        Returns run()'s dict plus "tape".  Solver variants TT_VARIANT_TRACK and TT_VARIANT_NMPC; no switch solver."""
+        tape, Si, Sc, drawn = self._tape_begin(x_init, T_sim, noise, wq_wr)
+        self._tape_steps(tape, Si, Sc, drawn)
+        torch.cuda.synchronize(self.dev)
+        act, Ss = tape.active.cpu().numpy(), tape.status.cpu().numpy()
+        stop = np.where((act == 0).any(axis=0), (act == 0).argmax(axis=0), -1)
+        return dict(self._policy_logs(), k=np.array(tape.ks), states=tape.S.cpu().numpy(),
+                    controls=tape.Ua.cpu().numpy(), status=Ss, iters=Si.cpu().numpy(),
+                    collide=Sc.cpu().numpy().astype(bool), success=Ss <= TT_ACCEPTABLE, active=act.astype(bool),
+                    stop_step=stop, tape=tape)
+
+    def _tape_begin(self, x_init, T_sim, noise=None, wq_wr=None):
+        """reset() and the tape of a run of T_sim: -> (tape, iteration log, collision log, whether the noise is drawn)."""
+        self._check_differentiable()
+        ks = step_indices(T_sim, float(self.params["dt"]))
+        if isinstance(x_init, torch.Tensor):
+            x_init = x_init.detach().cpu().numpy()
+        self.reset(x_init)
+        B, K, N, d, f = self.B, len(ks), self.N, self.dev, torch.float64
+        new = lambda *sh, dtype=f: torch.empty(sh, dtype=dtype, device=d)  # noqa: E731
+        w = None if wq_wr is None else _dev(wq_wr.detach() if isinstance(wq_wr, torch.Tensor) else wq_wr, d)
+        if w is not None and tuple(w.shape) != (B, 8):
+            raise ValueError(f"wq_wr must have shape (B, 8) = {(B, 8)}, got {tuple(w.shape)}")
+        nz = None if noise is None else _dev(noise.detach() if isinstance(noise, torch.Tensor) else noise, d)
+        if nz is not None and tuple(nz.shape) != (K, B, 6):
+            raise ValueError(f"noise must have shape (steps, B, 6) = {(K, B, 6)}, got {tuple(nz.shape)}")
+        drawn = nz is None and (self.measurement_noise or self.noise_in_plant) and self.dist is not None
+        if drawn:
+            nz = new(K, B, 6)
+        tape = LoopTape(ks=list(ks), S=new(K + 1, B, 6), Ua=new(K, B, 2), status=new(K, B, dtype=torch.int32),
+                        active=new(K, B, dtype=torch.int32), consec=new(K, B, dtype=torch.int32),
+                        X=new(K, B, N + 1, 6), U=new(K, B, N, 2), dual=new(K, B, N + 1, 22), noise=nz, wq_wr=w,
+                        plan_x=self.plan_x, plan_u=self.plan_u)
+        Si, Sc = new(K, B, dtype=torch.int32), new(K, B, dtype=torch.int32)
+        tape.S[0].copy_(self.state)
+        self.stream.wait_stream(torch.cuda.current_stream(d))
+        return tape, Si, Sc, drawn
+
+    def _tape_steps(self, tape, Si, Sc, drawn=False):
+        """Enqueue the K steps of a taped run on the loop's stream (no host synchronisation): step() with the multiplier
+        export, then the step's logs and its X, U copied to the tape."""
+        B, d, f, nz = self.B, self.dev, torch.float64, tape.noise
+        for j, k in enumerate(tape.ks):
+            if drawn:   # the draw step() would make, kept
+                with torch.cuda.stream(self.stream):
+                    nz[j].copy_(torch.randn((B, 6), generator=self.gen, dtype=f, device=d))
+                    nz[j].mul_(float(self.dist.get("process_noise_std", 0.0)))
+            self.step(k, None if nz is None else nz[j], dual=tape.dual[j], wq_wr=tape.wq_wr)
+            with torch.cuda.stream(self.stream):
+                tape.S[j + 1].copy_(self.state)
+                tape.Ua[j].copy_(self.u_applied)
+                tape.status[j].copy_(self.st)
+                Si[j].copy_(self.it)
+                Sc[j].copy_(self.flag)
+                tape.active[j].copy_(self.active)
+                tape.consec[j].copy_(self.consec)
+                tape.X[j].copy_(self.X)
+                tape.U[j].copy_(self.U)
+
+    def backward(self, tape, GS, GU):
+        """The adjoint of a taped run for a scalar loss L(S, Ua): GS = dL/dS (K+1,B,6), GU = dL/dUa (K,B,2), float64
+        device tensors.  Per step, backwards: tt_policy_plant_vjp_device, the step's window again,
+        tt_track_vjp_device on the taped solve, tt_sim_window_vjp_device (include/ttmpc.h, "Reverse mode of the closed
+        loop").  Enqueued on the loop's stream, which is ordered behind the current stream at entry and ahead of it at
+        exit; no host synchronisation.  Returns device tensors dict(g_x_init (B,6), g_wq_wr (B,8), g_plan_x, g_plan_u
+        (shaped as the loop's plan: summed over B for a shared one), g_noise (K,B,6): of the measurement noise, or with
+        noise_in_plant of the plant's process noise; zeros where the run had no noise)."""
+        self._check_differentiable()
+        L, s, d, N = lib(), self.stream, self.dev, self.N
+        K, B = tape.status.shape
+        Np = tape.plan_u.shape[-2]
+        per = int(tape.plan_x.shape[0] != 1)
+        for name, t, shape in (("GS", GS, (K + 1, B, 6)), ("GU", GU, (K, B, 2))):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.device == d and
+                    tuple(t.shape) == shape):
+                raise ValueError(f"{name} must be a float64 tensor of shape {shape} on {d}")
+        GS, GU = GS.contiguous(), GU.contiguous()
+        z = lambda *sh: torch.zeros(sh, dtype=torch.float64, device=d)  # noqa: E731
+        a, abar, gU = GS[K].clone(), z(B, 2), z(B, N, 2)
+        g_w, g_px, g_pu, g_n = z(B, 8), z(B, Np + 1, 6), z(B, Np, 2), z(K, B, 6)
+        xref, uref = z(B, N + 1, 6), z(B, N, 2)
+        g_x0, g_xr, g_ur, g_ws = z(B, 6), z(B, N + 1, 6), z(B, N, 2), z(B, 8)
+        in_plant = self.noise_in_plant and tape.noise is not None
+        meas = self.measurement_noise and tape.noise is not None
+        p = plant(self.params, self.dist)
+        sp = C.c_void_p(s.cuda_stream)
+        wq = 0 if tape.wq_wr is None else tape.wq_wr.data_ptr()
+        s.wait_stream(torch.cuda.current_stream(d))
+        for t in range(K - 1, -1, -1):
+            _check(L.tt_policy_plant_vjp_device(B, N, C.byref(p), POLICIES[self.policy], tape.S[t].data_ptr(),
+                                                tape.status[t].data_ptr(),
+                                                None if t == 0 else tape.active[t - 1].data_ptr(),
+                                                tape.active[t].data_ptr(), tape.consec[t].data_ptr(), GU[t].data_ptr(),
+                                                a.data_ptr(), abar.data_ptr(), gU.data_ptr(),
+                                                g_n[t].data_ptr() if in_plant else None, sp),
+                   "tt_policy_plant_vjp_device")
+            _check(L.tt_sim_window_device(B, N, int(tape.ks[t]), int(Np), tape.plan_x.data_ptr(),
+                                          tape.plan_u.data_ptr(), per, None, None, None, xref.data_ptr(),
+                                          uref.data_ptr(), sp), "tt_sim_window_device")
+            self.solver.vjp_device(B, tape.X[t].data_ptr(), tape.U[t].data_ptr(), tape.dual[t].data_ptr(),
+                                   xref.data_ptr(), uref.data_ptr(), tape.status[t].data_ptr(), grad_u=gU.data_ptr(),
+                                   g_x0=g_x0.data_ptr(), g_xref=g_xr.data_ptr(), g_uref=g_ur.data_ptr(),
+                                   g_wq_wr=g_ws.data_ptr(), wq_wr=wq, stream=s.cuda_stream)
+            _check(L.tt_sim_window_vjp_device(B, N, int(tape.ks[t]), int(Np), g_xr.data_ptr(), g_ur.data_ptr(),
+                                              g_px.data_ptr(), g_pu.data_ptr(), g_x0.data_ptr(), GS[t].data_ptr(),
+                                              a.data_ptr(), g_ws.data_ptr(), g_w.data_ptr(),
+                                              g_n[t].data_ptr() if meas else None, sp), "tt_sim_window_vjp_device")
+        with torch.cuda.stream(s):
+            if not per:
+                g_px, g_pu = g_px.sum(dim=0, keepdim=True), g_pu.sum(dim=0, keepdim=True)
+        torch.cuda.current_stream(d).wait_stream(s)
+        return {"g_x_init": a, "g_wq_wr": g_w, "g_plan_x": g_px, "g_plan_u": g_pu, "g_noise": g_n}
 
     def _policy_logs(self):
         """failure_count / consecutive_failures of the reference drivers, per instance, and whether the

@@ -316,6 +316,57 @@ int tt_record_solution_device(int B, int N, const double* x_out, const double* u
 int tt_interpolate_device(int B, int Np, int factor, const double* state_traj, const double* input_traj,
                           double* state_out, double* input_out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Reverse mode of the closed loop: the adjoints of the glue around the solve, for a backward sweep over a taped
+ * run (ttmpc.simulation.ClosedLoop.run_tape / backward).  With S (K+1 states), Ua (K applied controls) the logs
+ * and GS = dL/dS, GU = dL/dUa, the sweep carries a = dL/dS_{t+1} [B][6] and abar = the adjoint of u_last [B][2]
+ * (a = GS[K], abar = 0 at the start) and does, for t = K-1 .. 0:
+ *     tt_policy_plant_vjp_device   plant and failure-policy adjoint: a <- J_q' a, seed g_u0, abar
+ *     tt_sim_window_device         xref_t, uref_t again (they are not taped)
+ *     tt_track_vjp_device          on step t's taped x, u, dual, status with grad_x = NULL, grad_u = the buffer
+ *                                  whose row 0 holds g_u0 (rows 1.. zeroed once by the caller)
+ *     tt_sim_window_vjp_device     a += g_x0 + GS[t], weight and plan gradients accumulated
+ * and dL/dx_init = a at the end.  Device pointers, asynchronous on `stream`, no atomics: two sweeps over one
+ * tape give the same bits.  Both calls return -EINVAL for B <= 0 or N outside 1..tt_max_horizon().
+ *
+ * tt_policy_plant_vjp_device: the adjoint of tt_policy_plant[_noise]_device for one step, one instance per thread.
+ *   state [B][6] is S_t (before the step), status [B] the step's solve status, active_before / active_after [B] the
+ *   `active` flags before (NULL: all 1, the first step) and after the step, consecutive [B] the consecutive-failure
+ *   count after the step, grad_u_applied [B][2] = GU[t] or NULL.  The applied control itself is not needed: the
+ *   plant is linear in it.  With J_q = dS_{t+1}/dS_t, J_u = dS_{t+1}/du_t (u_t before the friction / slippage
+ *   scaling) and c = J_u' a + GU[t]:
+ *       branch                                        g_u0      abar
+ *       not active before the step, or stopped in it  0         unchanged (TT_POLICY_NMPC: 0 on the stopping step)
+ *       success (status <= TT_ACCEPTABLE)             c + abar  0
+ *       failure, TT_POLICY_TRACK                      c         unchanged   (tt_track_vjp_device zeroes a failed
+ *                                                                            instance: nothing to differentiate)
+ *       failure, TT_POLICY_NMPC                       0         0           (u_last was overwritten with 0)
+ *       failure, TT_POLICY_FUZZY, count <= 15         0         abar + c    (u_last was re-applied)
+ *       failure, TT_POLICY_FUZZY, count > 15          0         unchanged
+ *   and a <- J_q' a for every instance that moved; a stopped instance keeps a.  adj_state [B][6] = a and
+ *   adj_u_last [B][2] = abar are updated in place; g_u0 goes to grad_u[b * 2N + 0..1] (row 0 of a [B][N][2] array).
+ *   g_state_noise [B][6] (may be NULL) receives dL/d(state_noise) = dt a, taken before the J_q product, for the
+ *   in-plant noise of tt_policy_plant_noise_device (0 for a stopped instance).
+ *   Kinks: d|x|/dx = sign(x) with 0 at 0 (the |phi| |v| terms of the slip factor and of the lateral slip);
+ *   d min(s, 0.3)/ds = 1 for s < 0.3 and 0 otherwise.  Plain IEEE arithmetic without contraction, as the plant.
+ *
+ * tt_sim_window_vjp_device: the adjoint of tt_sim_window_device at step index k plus the step's accumulation.
+ *   g_xref [B][N+1][6], g_uref [B][N][2] (tt_track_vjp_device's) are scatter-added into the per-instance plan
+ *   gradients g_plan_x [B][Np+1][6], g_plan_u [B][Np][2] with the forward's end padding: state row j to plan row
+ *   min(k+j, Np), input row j to min(k+j, Np-1) while k < Np (for k >= Np the input window is zeros and nothing
+ *   reaches g_plan_u).  Each plan row is written by one thread; the rows that the padding folds onto the last plan
+ *   row are summed in ascending j first.  A shared plan's gradient is the sum of the [B] slices (the caller's).
+ *   Then, per instance: adj_state += g_x0 + grad_state (GS[t]), g_wq_wr_acc [B][8] += g_wq_wr, and g_meas_noise
+ *   [B][6] = g_x0 (the measurement noise enters x_meas = S_t + n_t).  Accumulators are `+=` into buffers the
+ *   caller zeroes.  Every pointer may be NULL (that part is skipped). */
+int tt_policy_plant_vjp_device(int B, int N, const tt_plant* p, int policy, const double* state, const int* status,
+                               const int* active_before, const int* active_after, const int* consecutive,
+                               const double* grad_u_applied, double* adj_state, double* adj_u_last, double* grad_u,
+                               double* g_state_noise, void* stream);
+int tt_sim_window_vjp_device(int B, int N, int k, int Np, const double* g_xref, const double* g_uref, double* g_plan_x,
+                             double* g_plan_u, const double* g_x0, const double* grad_state, double* adj_state,
+                             const double* g_wq_wr, double* g_wq_wr_acc, double* g_meas_noise, void* stream);
+
 /* lqr_distance (LQR_cost.py:7-41) for B instances: A, B of the forward-Euler map at (x_goal, u_goal),
  * P = DARE(A, B, Q, R) symmetrised, score[b] = (x_cur - x_goal)' P (x_cur - x_goal).  Q (6x6), R (2x2) are
  * HOST row-major arrays; x_cur, x_goal [B][6], u_goal [B][2] (may be NULL: the map is linear in u) are device
