@@ -51,6 +51,12 @@ class TTTrackVjpOut(C.Structure):
                 ("vjp_status", C.c_void_p)]
 
 
+class TTLqrVjpOut(C.Structure):
+    """tt_lqr_vjp_out (include/ttmpc.h): the outputs of tt_lqr_score_vjp_device; NULL members are skipped."""
+    _fields_ = [("g_x_cur", C.c_void_p), ("g_x_goal", C.c_void_p), ("g_Q", C.c_void_p), ("g_R", C.c_void_p),
+                ("vjp_status", C.c_void_p), ("iters", C.c_void_p)]
+
+
 class TTError(RuntimeError):
     pass
 
@@ -174,7 +180,9 @@ def lib():
            "tt_policy_plant_noise_device": [i, C.POINTER(TTPlant), i, vp, vp, ll, vp, vp, vp, vp, vp, vp, vp, vp],
            "tt_fuzzy_weights_device": [i, i, vp, vp, vp, vp],
            "tt_policy_plant_vjp_device": [i, i, C.POINTER(TTPlant), i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-           "tt_sim_window_vjp_device": [i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]}
+           "tt_sim_window_vjp_device": [i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+           "tt_lqr_score_vjp_device": [i, C.POINTER(TTPlant), _dp, vp, vp, vp, vp, vp, vp, C.POINTER(TTLqrVjpOut),
+                                       vp]}
     sim["ttx_obca_set_helpers"] = [C.c_void_p, i]  # diagnostics (not in include/ttmpc.h)
     sim["ttx_obca_set_handoff_debug"] = [C.c_void_p, ll, i]
     for name, args in sim.items():
@@ -196,7 +204,8 @@ EXPORTED_SYMBOLS = ("tt_create", "tt_solve_batch", "tt_solve_batch_device", "tt_
                     "tt_sim_window_indexed_device", "tt_sim_log_advance_device", "tt_policy_plant_device",
                     "tt_fuzzy_weights_device", "tt_plant_update_noise_device", "tt_policy_plant_noise_device",
                     "tt_track_dual_len", "tt_solve_batch_ex", "tt_solve_batch_ex_device", "tt_track_sens_device",
-                    "tt_track_vjp_device", "tt_track_vjp", "tt_policy_plant_vjp_device", "tt_sim_window_vjp_device")
+                    "tt_track_vjp_device", "tt_track_vjp", "tt_policy_plant_vjp_device", "tt_sim_window_vjp_device",
+                    "tt_lqr_score_vjp_device")
 
 
 def _ptr(a):

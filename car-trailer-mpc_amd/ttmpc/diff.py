@@ -10,12 +10,20 @@ Both run on ``torch.cuda.current_stream()`` without any host synchronisation.
 with every solve taped on the device), backward is ``ClosedLoop.backward`` (the plant, policy and window adjoints around
 one ``vjp_device`` per step).  For a scalar loss on the visited states S and the applied controls Ua it returns
 dL/d(x_init, wq_wr, plan_x, plan_u, noise).
+
+``DifferentiableLqrScore(params)`` is the LQR terminal score the drivers report at the end of a run
+(``ttmpc.lqr.lqr_scores``): forward one lqr_kernel launch, backward one lqr_vjp_kernel launch
+(``ttmpc.lqr.lqr_scores_vjp``), differentiable with respect to x_cur, x_goal, Q and R.  Fed with the last state of a
+``DifferentiableClosedLoop`` and the plan's last row it closes the chain from the reference's own metric back to the
+weights, the plan, x_init and the noise.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
-__all__ = ["TrackingSolveFunction", "DifferentiableTracking", "ClosedLoopFunction", "DifferentiableClosedLoop"]
+__all__ = ["TrackingSolveFunction", "DifferentiableTracking", "ClosedLoopFunction", "DifferentiableClosedLoop",
+           "LqrScoreFunction", "DifferentiableLqrScore"]
 
 
 def _ptr(t):
@@ -155,3 +163,73 @@ class DifferentiableClosedLoop:
 
     def __call__(self, x_init, T_sim, wq_wr=None, plan_x=None, plan_u=None, noise=None):
         return ClosedLoopFunction.apply(self.loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise)
+
+
+def _host(name, m, n):
+    """Q or R as a host (n,n) float64 array; a device tensor is copied (one synchronisation)."""
+    a = np.ascontiguousarray(np.asarray(m.detach().cpu() if torch.is_tensor(m) else m, dtype=np.float64))
+    if a.shape != (n, n):
+        raise ValueError(f"{name} must have shape {(n, n)}, got {a.shape}")
+    return a
+
+
+class LqrScoreFunction(torch.autograd.Function):
+    """``score, P, doublings = LqrScoreFunction.apply(params, x_cur, x_goal, Q, R)``.
+
+    x_cur, x_goal (B,6): float64 CUDA tensors on one device; Q (6,6) and R (2,2): tensors (any device and dtype) or
+    arrays, shared by the batch.  score (B,) and P (B,6,6) are differentiable with respect to x_cur, x_goal, Q and R;
+    doublings (B,) int32 (the forward's, -1 = the DARE did not converge) is not.  The Q and R gradients are the
+    per-instance ones summed over B, symmetric (the gradients for symmetric Q and R).  An instance whose DARE did not
+    converge, or whose adjoint is undefined, contributes a zero gradient."""
+
+    @staticmethod
+    def forward(ctx, params, x_cur, x_goal, Q, R):
+        from . import lqr
+        B = x_cur.shape[0]
+        xc = _check("x_cur", x_cur, (B, 6))
+        xg = _check("x_goal", x_goal, (B, 6))
+        if xg.device != xc.device:
+            raise ValueError(f"x_goal is on {xg.device}, x_cur on {xc.device}")
+        q, r = _host("Q", Q, 6), _host("R", R, 2)
+        score, P, it = lqr.lqr_scores(xc, xg, params, q, r)
+        ctx.params, ctx.R = params, r
+        ctx.like = [(m.device, m.dtype) if torch.is_tensor(m) else None for m in (Q, R)]
+        ctx.save_for_backward(xc, xg, P, it)
+        ctx.mark_non_differentiable(it)
+        ctx.set_materialize_grads(False)
+        return score, P, it
+
+    @staticmethod
+    def backward(ctx, grad_score, grad_P, _grad_doublings):
+        from . import lqr
+        need = ctx.needs_input_grad  # (params, x_cur, x_goal, Q, R)
+        if grad_score is None and grad_P is None:
+            return (None,) * 5
+        xc, xg, P, it = ctx.saved_tensors
+        gs = None if grad_score is None else grad_score.to(torch.float64).contiguous()
+        gP = None if grad_P is None else grad_P.to(torch.float64).contiguous()
+        g = lqr.lqr_scores_vjp(xc, xg, ctx.params, ctx.R, P, grad_score=gs, grad_P=gP, fwd_iters=it)
+        shared = lambda k, n: g[k].sum(dim=0).to(*ctx.like[n - 3]) if need[n] else None  # noqa: E731
+        return (None, g["g_x_cur"] if need[1] else None, g["g_x_goal"] if need[2] else None, shared("g_Q", 3),
+                shared("g_R", 4))
+
+
+class DifferentiableLqrScore:
+    """``score, P, doublings = layer(x_cur, x_goal, Q, R)`` for one parameter dict (dt, L1, L2, M; no gradient).
+
+    A thin callable over ``LqrScoreFunction``.  The C ABI takes Q and R from the host: given as device tensors, the
+    forward copies them to the host once (one synchronisation; host tensors and arrays cost none); the backward reads
+    the copy it kept and does not synchronise.  The Q and R gradients arrive on the device and in the dtype of the Q and
+    R tensors given (for a host tensor that move is a synchronisation the caller chose).  With the last
+    state of a differentiable closed loop::
+
+        S, Ua, st = DifferentiableClosedLoop(loop)(x_init, T, wq_wr=w, plan_x=px, plan_u=pu)
+        score, P, _ = DifferentiableLqrScore(params)(S[-1], px[:, -1].expand(B, 6), Q, R)
+        score.sum().backward()        # w.grad, px.grad, pu.grad, x_init.grad: the derivative of the drivers' metric
+    """
+
+    def __init__(self, params):
+        self.params = params
+
+    def __call__(self, x_cur, x_goal, Q, R):
+        return LqrScoreFunction.apply(self.params, x_cur, x_goal, Q, R)

@@ -375,6 +375,37 @@ int tt_lqr_score_device(int B, const tt_plant* p, const double* Q, const double*
                         const double* x_goal, const double* u_goal, double* P_out, double* score, int* iters,
                         void* stream);
 
+/* Reverse mode of tt_lqr_score_device: for a scalar loss L(score, P) over its outputs, the gradient with respect
+ * to x_cur, x_goal, Q and R in one launch (lqr_vjp_kernel), at the P the forward returned (the DARE is not rerun).
+ * With B = dt [e5 e4] (constant), K = (R + B'PB)^-1 B'PA and Ac = A - BK, the DARE differentiates at its
+ * stabilising solution to
+ *     dP = Ac' dP Ac + M,     M = dQ + K' dR K + dA' P Ac + Ac' P dA.
+ * The upstream gradients gs = dL/dscore and GP = dL/dP combine to G = gs dx dx' + (GP + GP')/2 (the forward
+ * symmetrises P; dx = x_cur - x_goal), one discrete Lyapunov equation S = Ac S Ac' + G is solved by Smith doubling
+ * (S <- S + T S T', T <- T^2 from S = G, T = Ac; the forward's stopping rule, at most 64 doublings; S symmetrised
+ * once at the end), and
+ *     g_x_cur  [B][6]    2 gs P dx
+ *     g_x_goal [B][6]    -2 gs (P dx)[m] + dt sum_ij (dL/dA)_ij d2f_i/dq_j dq_m,   dL/dA = 2 P Ac S
+ *     g_Q      [B][36]   S        symmetric: the gradient for a symmetric Q, i.e. <g_Q, dQ> for a symmetric dQ
+ *     g_R      [B][4]    K S K'   symmetric, in the same sense
+ *     vjp_status [B]     0 ok; 1 undefined: a value (an upstream gradient included) was not finite,
+ *                        det(R + B'PB) <= 0, or the doubling did not converge in 64; 2 skipped: fwd_iters[b] < 0
+ *                        (the forward's DARE did not converge).  For 1 and 2 the instance's four arrays are zeros.
+ *     iters    [B]       the Lyapunov doublings run (0 for a skipped instance)
+ * Every member of tt_lqr_vjp_out may be NULL.  The gradients are per instance: the sum over B for a Q and R shared
+ * by the batch is the caller's.  The model parameters (tt_plant) get no gradient, and u_goal does not enter, as in
+ * the forward.
+ * Inputs: R HOST 2x2 row-major; x_cur, x_goal [B][6], P [B][36] (the forward's P_out) device; fwd_iters [B] (the
+ * forward's iters) device or NULL; grad_score [B], grad_P [B][36] device, either may be NULL and stands for zeros.
+ * Returns -EINVAL for B < 0, a NULL p, R or out, a singular R (the forward's check), and, for B > 0, a NULL x_cur,
+ * x_goal or P or both upstream gradients NULL; B = 0 returns 0.  Asynchronous on `stream`; no handle, no shared
+ * buffer, no atomics: two launches on the same inputs give the same bits. */
+typedef struct { double* g_x_cur; double* g_x_goal; double* g_Q; double* g_R;
+                 int* vjp_status; int* iters; } tt_lqr_vjp_out;
+int tt_lqr_score_vjp_device(int B, const tt_plant* p, const double* R, const double* x_cur, const double* x_goal,
+                            const double* P, const int* fwd_iters, const double* grad_score, const double* grad_P,
+                            const tt_lqr_vjp_out* out, void* stream);
+
 void tt_destroy(void* handle);
 const char* tt_last_error(void* handle);
 
