@@ -20,20 +20,40 @@
 
 namespace {
 
+// A device block that only grows.  A larger request waits for the device before the old block is freed (work that
+// still reads it may be in flight on any stream); a failed allocation leaves the buffer empty.
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;  // bytes
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+    bool ensure(size_t bytes) {
+        if (bytes <= cap) return true;
+        if (p) {
+            (void)hipDeviceSynchronize();
+            (void)hipFree(p);
+        }
+        p = nullptr;
+        cap = 0;
+        if (hipMalloc(&p, bytes) != hipSuccess) {
+            p = nullptr;
+            return false;
+        }
+        cap = bytes;
+        return true;
+    }
+};
+
 struct Handle {
     tt_config cfg;
     double Q[36], R[4], xlb[6], xub[6], ulb[2], uub[2];
     double obs[4 * ttmpc::kObcaMaxM] = {};
-    // OBCA variants: per-instance solver workspace + host-call staging buffers
-    size_t ocap = 0;
-    double* d_ows = nullptr;
-    double *d_oxg = nullptr, *d_ozg = nullptr, *d_ozo = nullptr;
     int device = 0;
     hipStream_t stream = nullptr;
-    size_t cap = 0;  // instances the workspace holds
-    double *d_x0 = nullptr, *d_xref = nullptr, *d_uref = nullptr, *d_w = nullptr, *d_zg = nullptr;
-    double *d_xo = nullptr, *d_uo = nullptr, *d_kkt = nullptr;
-    int *d_st = nullptr, *d_it = nullptr;
     // tracking host calls: one packed device input / output block and its pinned host mirror, so a
     // host-pointer solve is one H2D, the launch and one D2H (bytes).  The mirror is coherent (fine-grained) pinned
     // memory: small batches skip both copies and let the kernel read and write it in place (zd_*: its device view)
@@ -41,19 +61,15 @@ struct Handle {
     char *d_sin = nullptr, *d_sout = nullptr, *h_sin = nullptr, *h_sout = nullptr, *zd_sin = nullptr, *zd_sout = nullptr;
     std::string err;
     unsigned long long* obca_stamps = nullptr;  // diagnostics: per-phase clocks (ttx_obca_set_stamps)
-    unsigned long long* d_board = nullptr;      // OBCA helper-workgroup board, (ocap + 1) lines
     int nhelp = -1;                             // OBCA helper workgroups per launch (-1: one per CU; ttx_obca_set_helpers)
     unsigned long long spin_ticks = 0;          // hand-off spin limit (0: 5 s) and forced-timeout instance (-1: none),
     int fail_b = -1;                            //   ttx_obca_set_handoff_debug
-    // tracking builds that keep stage rows in HBM (the N = 50 build, ttmpc::track_global_bytes): one launch's rows
-    double* d_prow = nullptr;
-    size_t prow_cap = 0;  // bytes
-    // tt_solve_batch_ex*: the multipliers of a call that asks for a sensitivity but not for them (d_dual), and the
-    // device side of the host call's extra outputs (d_ex); both grown only, under the one-stream rule of d_prow
-    double* d_dual = nullptr;
-    size_t dual_cap = 0;  // bytes
-    char* d_ex = nullptr;
-    size_t ex_cap = 0;  // bytes
+    // Device workspaces, all under the one-stream rule of a handle's calls:
+    DevBuf prow;   // tracking builds that keep stage rows in HBM (the N = 50 build, ttmpc::track_global_bytes)
+    DevBuf dual;   // the multipliers of a tt_solve_batch_ex* call that asks for a sensitivity but not for them
+    DevBuf xfer;   // the Stager's block: host arrays of tt_track_vjp, the _ex extras and the OBCA host calls
+    DevBuf ows;    // OBCA solver workspace (HBM: ~1.8 MB per instance at N=200, M=6)
+    DevBuf board;  // OBCA helper-workgroup board, one line per instance and a header line
 };
 
 thread_local std::string g_err;
@@ -93,18 +109,93 @@ int hip_fail(Handle* h, hipError_t e, const char* where) {
     return -EIO;
 }
 
-void free_ws(Handle* h) {
-    double** dp[] = {&h->d_x0, &h->d_xref, &h->d_uref, &h->d_w, &h->d_zg, &h->d_xo, &h->d_uo, &h->d_kkt};
-    for (double** p : dp) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    if (h->d_st) (void)hipFree(h->d_st);
-    if (h->d_it) (void)hipFree(h->d_it);
-    h->d_st = h->d_it = nullptr;
-    h->cap = 0;
+int no_memory(Handle* h, const char* what) { return fail(h, -ENOMEM, "%s allocation failed", what); }
+
+bool is_obca(const tt_config& c) { return c.variant == TT_VARIANT_TRACK_OBCA || c.variant == TT_VARIANT_OBCA_PLAN; }
+
+// ---------------- the prelude of every entry point ----------------
+// The checks an entry asks for run in this order: handle, variant class, sign of B, empty batch, fuzzy weights, size of
+// B.  An entry whose own checks (its pointers) sit between two of them asks in two steps.  Returns 0 to go on, an
+// error code, or kEmptyBatch (the entry returns 0 without touching anything): `if (rc) return result(rc);`.
+enum : unsigned {
+    kHandle = 1, kTrackOnly = 2, kObcaOnly = 4, kPlanOnly = 8, kNotPlan = 16, kSign = 32, kEmpty = 64, kFuzzy = 128,
+    kRange = 256
+};
+constexpr int kEmptyBatch = 1;
+int result(int rc) { return rc == kEmptyBatch ? 0 : rc; }
+
+int prelude(Handle* h, int B, unsigned checks, const void* weights = nullptr, int max_b = 1 << 30) {
+    if (!h) return fail(nullptr, -EINVAL, "NULL handle%s");
+    if ((checks & kTrackOnly) && is_obca(h->cfg))
+        return fail(h, -EINVAL, "multipliers and sensitivities are exported by the tracking variants only%s");
+    if ((checks & kObcaOnly) && !is_obca(h->cfg)) return fail(h, -EINVAL, "handle is not an OBCA variant%s");
+    if ((checks & kPlanOnly) && h->cfg.variant != TT_VARIANT_OBCA_PLAN)
+        return fail(h, -EINVAL, "tt_plan_batch needs a TT_VARIANT_OBCA_PLAN handle%s");
+    if ((checks & kNotPlan) && h->cfg.variant == TT_VARIANT_OBCA_PLAN)
+        return fail(h, -EINVAL, "plan handles solve through tt_plan_batch / tt_obca_solve_batch%s");
+    if ((checks & kSign) && B < 0) return fail(h, -EINVAL, "B must be >= 0%s");
+    if ((checks & kEmpty) && B == 0) return kEmptyBatch;
+    if ((checks & kFuzzy) && h->cfg.variant == TT_VARIANT_FUZZY && !weights)
+        return fail(h, -EINVAL, "fuzzy variant needs per-instance weights (mpc_control_fuzzy.py:54-58)%s");
+    if ((checks & kRange) && B > max_b) return fail(h, -EINVAL, "B too large%s");
+    return 0;
 }
 
+// ---------------- host staging ----------------
+// Host arrays of one call behind one device block: register the arrays (absent ones get a NULL device pointer and no
+// memory), carve the block, enqueue the uploads, launch, enqueue the downloads.  err keeps the first failed copy.
+class Stager {
+  public:
+    hipError_t err = hipSuccess;
+    // an input: copied to the device if the host has it
+    template <class T>
+    void in(const T* host, size_t count, const T** dev) {
+        add(host, nullptr, count * sizeof(T), host != nullptr, (void**)dev);
+    }
+    // an output: copied back if the host wants it; device_only: the launch needs the array even if the host does not
+    template <class T>
+    void out(T* host, size_t count, T** dev, bool device_only = false) {
+        add(nullptr, host, count * sizeof(T), host != nullptr || device_only, (void**)dev);
+    }
+    bool carve(DevBuf& buf) {
+        if (!buf.ensure(total_)) return false;
+        for (int t = 0; t < n_; ++t)
+            if (it_[t].used) *it_[t].dev = static_cast<char*>(buf.p) + it_[t].off;
+        return true;
+    }
+    void upload(hipStream_t s) { copy(s, true); }
+    void download(hipStream_t s) { copy(s, false); }
+
+  private:
+    struct Item {
+        const void* h2d;
+        void* d2h;
+        size_t bytes, off;
+        bool used;
+        void** dev;
+    };
+    static constexpr int kMax = 16;
+    Item it_[kMax];
+    int n_ = 0;
+    size_t total_ = 0;
+
+    void add(const void* h2d, void* d2h, size_t bytes, bool used, void** dev) {
+        if (n_ == kMax) abort();  // (a fixed list per entry point: never at run time)
+        *dev = nullptr;
+        it_[n_++] = Item{h2d, d2h, bytes, total_, used, dev};
+        if (used) total_ += (bytes + 255) & ~(size_t)255;  // every array as aligned as an allocation of its own
+    }
+    void copy(hipStream_t s, bool up) {
+        for (int t = 0; t < n_; ++t) {
+            const Item& i = it_[t];
+            if (err != hipSuccess || !i.used || !(up ? i.h2d != nullptr : i.d2h != nullptr)) continue;
+            err = up ? hipMemcpyAsync(*i.dev, i.h2d, i.bytes, hipMemcpyHostToDevice, s)
+                     : hipMemcpyAsync(i.d2h, *i.dev, i.bytes, hipMemcpyDeviceToHost, s);
+        }
+    }
+};
+
+// ---------------- the zero-copy mirror of tracking host calls ----------------
 void free_stage(Handle* h) {
     if (h->d_sin) (void)hipFree(h->d_sin);
     if (h->d_sout) (void)hipFree(h->d_sout);
@@ -148,41 +239,6 @@ int zero_copy_max() {
     return v;
 }
 
-// the HBM stage rows of a launch (grown only: a larger batch waits for the device before the old block is freed)
-int ensure_prow(Handle* h, size_t bytes) {
-    if (bytes <= h->prow_cap) return 0;
-    if (h->d_prow) {
-        (void)hipDeviceSynchronize();
-        (void)hipFree(h->d_prow);
-    }
-    h->d_prow = nullptr;
-    h->prow_cap = 0;
-    if (hipMalloc((void**)&h->d_prow, bytes) != hipSuccess) {
-        h->d_prow = nullptr;
-        return fail(h, -ENOMEM, "stage-row workspace allocation failed (%s bytes)", std::to_string(bytes).c_str());
-    }
-    h->prow_cap = bytes;
-    return 0;
-}
-
-// a handle-owned device block of the _ex calls (grown only, like the stage rows above)
-template <class T>
-int ensure_block(Handle* h, T*& p, size_t& cap, size_t bytes, const char* what) {
-    if (bytes <= cap) return 0;
-    if (p) {
-        (void)hipDeviceSynchronize();
-        (void)hipFree(p);
-    }
-    p = nullptr;
-    cap = 0;
-    if (hipMalloc((void**)&p, bytes) != hipSuccess) {
-        p = nullptr;
-        return fail(h, -ENOMEM, "%s allocation failed", what);
-    }
-    cap = bytes;
-    return 0;
-}
-
 // a status value no kernel writes: the zero-copy path's "not finished yet"
 constexpr int kStatusPending = -0x40000000;
 
@@ -206,65 +262,6 @@ bool poll_done(volatile int* st, int B) {
     }
 }
 
-bool is_obca(const tt_config& c) { return c.variant == TT_VARIANT_TRACK_OBCA || c.variant == TT_VARIANT_OBCA_PLAN; }
-
-void free_ows(Handle* h) {
-    double** dp[] = {&h->d_ows, &h->d_oxg, &h->d_ozg, &h->d_ozo};
-    for (double** p : dp) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    if (h->d_board) (void)hipFree(h->d_board);
-    h->d_board = nullptr;
-    h->ocap = 0;
-}
-
-// OBCA solver workspace for B instances (HBM: ~1.8 MB per instance at N=200, M=6)
-int ensure_ows(Handle* h, int B) {
-    if ((size_t)B <= h->ocap) return 0;
-    free_ows(h);
-    const size_t b = (size_t)B, N = h->cfg.N, M = h->cfg.M, n = ttmpc::obca_n(h->cfg.N, h->cfg.M);
-    hipError_t e = hipMalloc((void**)&h->d_ows, b * ttmpc::obca_ws_doubles(h->cfg.N, h->cfg.M) * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_oxg, b * 6 * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_ozg, b * n * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_ozo, b * n * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_board, (b + 1) * ttmpc::kObcaBoardStride * 8);
-    (void)N; (void)M;
-    if (e != hipSuccess) {
-        free_ows(h);
-        return fail(h, -ENOMEM, "OBCA workspace allocation failed for B=%s", std::to_string(B).c_str());
-    }
-    h->ocap = b;
-    return 0;
-}
-
-int ensure_ws(Handle* h, int B) {
-    if ((size_t)B <= h->cap) return 0;
-    free_ws(h);
-    const size_t N = h->cfg.N, nz = is_obca(h->cfg) ? ttmpc::obca_n(h->cfg.N, h->cfg.M) : 8 * N + 6;
-    const size_t cap = (size_t)B;
-    hipError_t e = hipSuccess;
-#define ALLOC(p, bytes) \
-    if (e == hipSuccess) e = hipMalloc((void**)&(p), (bytes))
-    ALLOC(h->d_x0, cap * 6 * 8);
-    ALLOC(h->d_xref, cap * (N + 1) * 6 * 8);
-    ALLOC(h->d_uref, cap * N * 2 * 8);
-    ALLOC(h->d_w, cap * 8 * 8);
-    ALLOC(h->d_zg, cap * nz * 8);
-    ALLOC(h->d_xo, cap * (N + 1) * 6 * 8);
-    ALLOC(h->d_uo, cap * N * 2 * 8);
-    ALLOC(h->d_kkt, cap * 8);
-    ALLOC(h->d_st, cap * 4);
-    ALLOC(h->d_it, cap * 4);
-#undef ALLOC
-    if (e != hipSuccess) {
-        free_ws(h);
-        return fail(h, -ENOMEM, "device workspace allocation failed for B=%s", std::to_string(B).c_str());
-    }
-    h->cap = cap;
-    return 0;
-}
-
 void defaults(tt_config& c) {
     const bool relaxed = c.variant == TT_VARIANT_NMPC || c.variant == TT_VARIANT_FUZZY;
     // IPOPT options of the reference classes: mpc_control.py:35-39 (defaults tol 1e-8, acceptable
@@ -276,26 +273,218 @@ void defaults(tt_config& c) {
     if (c.acc_iter <= 0) c.acc_iter = relaxed ? 5 : 15;
 }
 
-ttmpc::TrackArgs make_args(const Handle* h, int B) {
-    ttmpc::TrackArgs a;
-    memset(&a, 0, sizeof a);
-    a.N = h->cfg.N;
-    a.B = B;
-    a.max_iter = h->cfg.max_iter;
-    a.acc_iter = h->cfg.acc_iter;
+// ---------------- kernel arguments ----------------
+// the model block every args struct carries under the same names
+template <class Args>
+void fill_model(Args& a, const Handle* h) {
     a.dt = h->cfg.dt;
     a.L1 = h->cfg.L1;
     a.L2 = h->cfg.L2;
     a.Mh = h->cfg.Mh;
-    a.tol = h->cfg.tol;
-    a.acc_tol = h->cfg.acc_tol;
     memcpy(a.Q, h->Q, sizeof a.Q);
     memcpy(a.R, h->R, sizeof a.R);
     memcpy(a.xlb, h->xlb, sizeof a.xlb);
     memcpy(a.xub, h->xub, sizeof a.xub);
     memcpy(a.ulb, h->ulb, sizeof a.ulb);
     memcpy(a.uub, h->uub, sizeof a.uub);
+}
+
+// a tracking launch without its arrays; the launch's HBM stage rows come from the handle
+int make_track_args(Handle* h, int B, ttmpc::TrackArgs& a) {
+    memset(&a, 0, sizeof a);
+    a.N = h->cfg.N;
+    a.B = B;
+    a.max_iter = h->cfg.max_iter;
+    a.acc_iter = h->cfg.acc_iter;
+    a.tol = h->cfg.tol;
+    a.acc_tol = h->cfg.acc_tol;
+    fill_model(a, h);
+    if (const size_t gb = ttmpc::track_global_bytes(a)) {
+        if (!h->prow.ensure(gb)) return no_memory(h, "stage-row workspace");
+        a.prow = static_cast<double*>(h->prow.p);
+    }
+    return 0;
+}
+
+// SensArgs / VjpArgs with their common head filled
+template <class Args>
+Args diff_args(const Handle* h, int B, const double* d_x, const double* d_u, const double* d_dual,
+               const double* d_wq_wr, const int* d_status) {
+    Args a{};
+    a.N = h->cfg.N;
+    a.B = B;
+    fill_model(a, h);
+    a.x = d_x;
+    a.u = d_u;
+    a.dual = d_dual;
+    a.wqwr = d_wq_wr;
+    a.status = d_status;
     return a;
+}
+
+// ---------------- tracking solves ----------------
+int solve_device_impl(Handle* h, int B, const double* d_x0, const double* d_xref, const double* d_uref,
+                      const double* d_wq_wr, const double* d_z_guess, double* d_x_out, double* d_u_out, int* d_status,
+                      int* d_iters, double* d_kkt_res, void* stream, int host_done, double* d_dual = nullptr) {
+    if (const int rc = prelude(h, B, kHandle | kSign | kEmpty | kRange)) return result(rc);
+    if (!d_x0 || !d_xref || !d_uref || !d_x_out || !d_u_out || !d_status)
+        return fail(h, -EINVAL, "NULL device buffer%s");
+    if (const int rc = prelude(h, B, kNotPlan)) return rc;
+    if (h->cfg.variant == TT_VARIANT_TRACK_OBCA)
+        return tt_obca_solve_batch_device(h, B, d_x0, nullptr, d_xref, d_uref, d_z_guess, d_x_out, d_u_out, nullptr,
+                                          d_status, d_iters, d_kkt_res, stream);
+    if (const int rc = prelude(h, B, kFuzzy, d_wq_wr)) return rc;
+    DeviceGuard dg(h->device);
+    if (dg.err != hipSuccess) return hip_fail(h, dg.err, "hipSetDevice");
+    ttmpc::TrackArgs a;
+    if (const int rc = make_track_args(h, B, a)) return rc;
+    a.x0 = d_x0;
+    a.xref = d_xref;
+    a.uref = d_uref;
+    a.wqwr = d_wq_wr;
+    a.zg = d_z_guess;
+    a.xout = d_x_out;
+    a.uout = d_u_out;
+    a.kkt = d_kkt_res;
+    a.status = d_status;
+    a.iters = d_iters;
+    a.host_done = host_done;
+    a.dual = d_dual;
+    const hipError_t e = ttmpc::launch_track(a, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(h, e, "track kernel launch");
+    return 0;
+}
+
+bool wants_sens(const tt_track_extra& x) { return x.gain || x.dxdx0 || x.dudx0 || x.sens_status; }
+bool wants_any(const tt_track_extra* x) { return x && (x->dual || wants_sens(*x)); }
+
+// the sensitivity launch behind both entry points; the caller has made the handle's device current
+int sens_launch(Handle* h, int B, const double* d_x, const double* d_u, const double* d_dual, const double* d_wq_wr,
+                const int* d_status, const tt_track_extra& x, void* stream) {
+    ttmpc::SensArgs a = diff_args<ttmpc::SensArgs>(h, B, d_x, d_u, d_dual, d_wq_wr, d_status);
+    a.gain = x.gain;
+    a.dxdx0 = x.dxdx0;
+    a.dudx0 = x.dudx0;
+    a.sens_status = x.sens_status;
+    const hipError_t e = ttmpc::launch_track_sens(a, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(h, e, "sensitivity kernel launch");
+    return 0;
+}
+
+// solve (+ multiplier export) and, if asked for, the sensitivity launch behind it on the same stream
+int ex_device_impl(Handle* h, int B, const double* d_x0, const double* d_xref, const double* d_uref,
+                   const double* d_wq_wr, const double* d_z_guess, double* d_x_out, double* d_u_out, int* d_status,
+                   int* d_iters, double* d_kkt_res, const tt_track_extra& x, void* stream) {
+    if (const int rc = prelude(h, B, kHandle | kTrackOnly | kSign | kEmpty)) return result(rc);
+    const bool sens = wants_sens(x);
+    double* d_dual = x.dual;
+    DeviceGuard dg(h->device);
+    if (dg.err != hipSuccess) return hip_fail(h, dg.err, "hipSetDevice");
+    if (sens && !d_dual) {
+        if (!h->dual.ensure((size_t)B * (h->cfg.N + 1) * ttmpc::kDualPerStage * sizeof(double)))
+            return no_memory(h, "multiplier workspace");
+        d_dual = static_cast<double*>(h->dual.p);
+    }
+    const int rc = solve_device_impl(h, B, d_x0, d_xref, d_uref, d_wq_wr, d_z_guess, d_x_out, d_u_out, d_status,
+                                     d_iters, d_kkt_res, stream, 0, d_dual);
+    if (rc || !sens) return rc;
+    return sens_launch(h, B, d_x_out, d_u_out, d_dual, d_wq_wr, d_status, x, stream);
+}
+
+int solve_host(Handle* h, int B, const double* x0, const double* xref, const double* uref, const double* wq_wr,
+               const double* z_guess, double* x_out, double* u_out, int* status, int* iters, double* kkt_res,
+               const tt_track_extra* extra) {
+    if (const int rc = prelude(h, B, kHandle | kSign | kEmpty)) return result(rc);
+    if (!x0 || !xref || !uref || !x_out || !u_out || !status) return fail(h, -EINVAL, "NULL host buffer%s");
+    if (const int rc = prelude(h, B, kNotPlan)) return rc;
+    if (is_obca(h->cfg)) {  // MPC+OBCA handle: its own host path (workspace, z_guess layout)
+        if (extra) return prelude(h, B, kTrackOnly);
+        return tt_obca_solve_batch(h, B, x0, nullptr, xref, uref, z_guess, x_out, u_out, nullptr, status, iters,
+                                   kkt_res);
+    }
+    // validate everything tt_solve_batch_device would refuse before the staging buffer is touched
+    if (const int rc = prelude(h, B, kFuzzy | kRange, wq_wr)) return rc;
+    DeviceGuard dg(h->device);
+    hipError_t e = dg.err;
+    if (e != hipSuccess) return hip_fail(h, e, "hipSetDevice");
+    // packed layout, instance-major within each array: in  = x0 | xref | uref | [wq_wr] | [z_guess]
+    //                                                   out = X | U | kkt | status, iters (int32)
+    const size_t N = h->cfg.N, b = (size_t)B, nz = 8 * N + 6;
+    const size_t sizes[5] = {b * 6, b * (N + 1) * 6, b * N * 2, wq_wr ? b * 8 : 0, z_guess ? b * nz : 0};
+    const double* srcs[5] = {x0, xref, uref, wq_wr, z_guess};
+    size_t in_d = 0;
+    for (size_t v : sizes) in_d += v;
+    const size_t nxo = b * (N + 1) * 6, nuo = b * N * 2, out_d = nxo + nuo + b + b;  // 2 x int32 per instance = 1 double
+    int rc = ensure_stage(h, in_d * 8, out_d * 8);
+    if (rc) return rc;
+    // the extra outputs of tt_solve_batch_ex, straight into the caller's arrays (a call that asks for a sensitivity
+    // always has the multipliers on the device)
+    Stager ex;
+    tt_track_extra dx = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (extra) {
+        ex.out(extra->dual, b * (N + 1) * ttmpc::kDualPerStage, &dx.dual, true);
+        ex.out(extra->gain, b * 12, &dx.gain);
+        ex.out(extra->dxdx0, b * (N + 1) * 36, &dx.dxdx0);
+        ex.out(extra->dudx0, b * N * 12, &dx.dudx0);
+        ex.out(extra->sens_status, b, &dx.sens_status);
+        if (!ex.carve(h->xfer)) return no_memory(h, "extra-output workspace");
+    }
+    // zero-copy for small batches (B = 1 latency: the two DMA copies cost more than the kernel's few PCIe reads); a call
+    // with extra outputs always copies (they are not part of the coherent mirror)
+    const bool zc = !extra && B <= zero_copy_max() && N < 64;
+    double* hin = reinterpret_cast<double*>(h->h_sin);
+    const double* dptr[5];
+    size_t off = 0;
+    for (int a = 0; a < 5; ++a) {
+        if (sizes[a]) memcpy(hin + off, srcs[a], sizes[a] * 8);
+        dptr[a] = reinterpret_cast<const double*>(zc ? h->zd_sin : h->d_sin) + off;
+        off += sizes[a];
+    }
+    hipStream_t s = h->stream;
+    if (!zc) {
+        e = hipMemcpyAsync(h->d_sin, h->h_sin, in_d * 8, hipMemcpyHostToDevice, s);
+        if (e != hipSuccess) return hip_fail(h, e, "H2D copy");
+    }
+    double* dxo = reinterpret_cast<double*>(zc ? h->zd_sout : h->d_sout);
+    double* duo = dxo + nxo;
+    double* dkk = duo + nuo;
+    int* dst = reinterpret_cast<int*>(dkk + b);
+    int* dit = dst + b;
+    // zero-copy: status[] in the host block doubles as the instances' completion flags (the kernel writes each last,
+    // behind a system-scope release); a pending sentinel, then a poll of host memory instead of the stream wait
+    volatile int* hst = zc ? reinterpret_cast<volatile int*>(h->h_sout + (nxo + nuo + b) * 8) : nullptr;
+    if (zc)
+        for (int i = 0; i < B; ++i) hst[i] = kStatusPending;
+    if (extra)
+        rc = ex_device_impl(h, B, dptr[0], dptr[1], dptr[2], wq_wr ? dptr[3] : nullptr, z_guess ? dptr[4] : nullptr, dxo,
+                            duo, dst, dit, dkk, dx, s);
+    else
+        rc = solve_device_impl(h, B, dptr[0], dptr[1], dptr[2], wq_wr ? dptr[3] : nullptr, z_guess ? dptr[4] : nullptr,
+                               dxo, duo, dst, dit, dkk, s, zc ? 1 : 0);
+    if (rc) {
+        (void)hipStreamSynchronize(s);  // the H2D from the pinned staging buffer may still be in flight
+        return rc;
+    }
+    bool done = false;
+    if (zc) done = poll_done(hst, B);
+    e = zc ? hipSuccess : hipMemcpyAsync(h->h_sout, h->d_sout, out_d * 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) {  // (the stream wait below covers the extras too)
+        ex.download(s);
+        e = ex.err;
+    }
+    if (e == hipSuccess && !done) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(s);
+        return hip_fail(h, e, "solve");
+    }
+    const double* ho = reinterpret_cast<const double*>(h->h_sout);
+    memcpy(x_out, ho, nxo * 8);
+    memcpy(u_out, ho + nxo, nuo * 8);
+    if (kkt_res) memcpy(kkt_res, ho + nxo + nuo, b * 8);
+    const int* hi = reinterpret_cast<const int*>(ho + nxo + nuo + b);
+    memcpy(status, hi, b * 4);
+    if (iters) memcpy(iters, hi + b, b * 4);
+    return 0;
 }
 
 }  // namespace
@@ -362,12 +551,6 @@ int tt_create(const tt_config* cfg, const double* Q, const double* R, const doub
     return 0;
 }
 
-namespace {
-int solve_device_impl(Handle* h, int B, const double* d_x0, const double* d_xref, const double* d_uref,
-                      const double* d_wq_wr, const double* d_z_guess, double* d_x_out, double* d_u_out, int* d_status,
-                      int* d_iters, double* d_kkt_res, void* stream, int host_done, double* d_dual = nullptr);
-}  // namespace
-
 int tt_solve_batch_device(void* handle, int B, const double* d_x0, const double* d_xref, const double* d_uref,
                           const double* d_wq_wr, const double* d_z_guess, double* d_x_out, double* d_u_out,
                           int* d_status, int* d_iters, double* d_kkt_res, void* stream) {
@@ -375,250 +558,19 @@ int tt_solve_batch_device(void* handle, int B, const double* d_x0, const double*
                              d_u_out, d_status, d_iters, d_kkt_res, stream, 0);
 }
 
-namespace {
-int solve_device_impl(Handle* h, int B, const double* d_x0, const double* d_xref, const double* d_uref,
-                      const double* d_wq_wr, const double* d_z_guess, double* d_x_out, double* d_u_out, int* d_status,
-                      int* d_iters, double* d_kkt_res, void* stream, int host_done, double* d_dual) {
-    void* handle = h;
-    if (!h) return fail(nullptr, -EINVAL, "NULL handle%s");
-    if (B < 0) return fail(h, -EINVAL, "B must be >= 0%s");
-    if (B == 0) return 0;
-    if (B > (1 << 30)) return fail(h, -EINVAL, "B too large%s");
-    if (!d_x0 || !d_xref || !d_uref || !d_x_out || !d_u_out || !d_status)
-        return fail(h, -EINVAL, "NULL device buffer%s");
-    if (h->cfg.variant == TT_VARIANT_OBCA_PLAN)
-        return fail(h, -EINVAL, "plan handles solve through tt_plan_batch / tt_obca_solve_batch%s");
-    if (h->cfg.variant == TT_VARIANT_TRACK_OBCA)
-        return tt_obca_solve_batch_device(handle, B, d_x0, nullptr, d_xref, d_uref, d_z_guess, d_x_out, d_u_out,
-                                          nullptr, d_status, d_iters, d_kkt_res, stream);
-    if (h->cfg.variant == TT_VARIANT_FUZZY && !d_wq_wr)
-        return fail(h, -EINVAL, "fuzzy variant needs per-instance weights (mpc_control_fuzzy.py:54-58)%s");
-    DeviceGuard dg(h->device);
-    hipError_t e = dg.err;
-    if (e != hipSuccess) return hip_fail(h, e, "hipSetDevice");
-    ttmpc::TrackArgs a = make_args(h, B);
-    a.x0 = d_x0;
-    a.xref = d_xref;
-    a.uref = d_uref;
-    a.wqwr = d_wq_wr;
-    a.zg = d_z_guess;
-    a.xout = d_x_out;
-    a.uout = d_u_out;
-    a.kkt = d_kkt_res;
-    a.status = d_status;
-    a.iters = d_iters;
-    a.host_done = host_done;
-    a.dual = d_dual;
-    if (const size_t gb = ttmpc::track_global_bytes(a)) {
-        const int rc = ensure_prow(h, gb);
-        if (rc) return rc;
-        a.prow = h->d_prow;
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    e = ttmpc::launch_track(a, s);
-    if (e != hipSuccess) return hip_fail(h, e, "track kernel launch");
-    return 0;
-}
-}  // namespace
-
-namespace {
-bool wants_sens(const tt_track_extra& x) { return x.gain || x.dxdx0 || x.dudx0 || x.sens_status; }
-bool wants_any(const tt_track_extra* x) { return x && (x->dual || wants_sens(*x)); }
-int ex_device_impl(Handle* h, int B, const double* d_x0, const double* d_xref, const double* d_uref,
-                   const double* d_wq_wr, const double* d_z_guess, double* d_x_out, double* d_u_out, int* d_status,
-                   int* d_iters, double* d_kkt_res, const tt_track_extra& x, void* stream);
-int solve_host(void* handle, int B, const double* x0, const double* xref, const double* uref, const double* wq_wr,
-               const double* z_guess, double* x_out, double* u_out, int* status, int* iters, double* kkt_res,
-               const tt_track_extra* extra);
-}  // namespace
-
 int tt_solve_batch(void* handle, int B, const double* x0, const double* xref, const double* uref,
                    const double* wq_wr, const double* z_guess, double* x_out, double* u_out, int* status,
                    int* iters, double* kkt_res) {
-    return solve_host(handle, B, x0, xref, uref, wq_wr, z_guess, x_out, u_out, status, iters, kkt_res, nullptr);
+    return solve_host(static_cast<Handle*>(handle), B, x0, xref, uref, wq_wr, z_guess, x_out, u_out, status, iters,
+                      kkt_res, nullptr);
 }
-
-namespace {
-int solve_host(void* handle, int B, const double* x0, const double* xref, const double* uref, const double* wq_wr,
-               const double* z_guess, double* x_out, double* u_out, int* status, int* iters, double* kkt_res,
-               const tt_track_extra* extra) {
-    Handle* h = static_cast<Handle*>(handle);
-    if (!h) return fail(nullptr, -EINVAL, "NULL handle%s");
-    if (B < 0) return fail(h, -EINVAL, "B must be >= 0%s");
-    if (B == 0) return 0;
-    if (!x0 || !xref || !uref || !x_out || !u_out || !status) return fail(h, -EINVAL, "NULL host buffer%s");
-    if (h->cfg.variant == TT_VARIANT_OBCA_PLAN)
-        return fail(h, -EINVAL, "plan handles solve through tt_plan_batch / tt_obca_solve_batch%s");
-    if (is_obca(h->cfg)) {  // MPC+OBCA handle: its own host path (workspace, z_guess layout)
-        if (extra) return fail(h, -EINVAL, "multipliers and sensitivities are exported by the tracking variants only%s");
-        return tt_obca_solve_batch(handle, B, x0, nullptr, xref, uref, z_guess, x_out, u_out, nullptr, status, iters,
-                                   kkt_res);
-    }
-    // validate everything tt_solve_batch_device would refuse before the staging buffer is touched
-    if (h->cfg.variant == TT_VARIANT_FUZZY && !wq_wr)
-        return fail(h, -EINVAL, "fuzzy variant needs per-instance weights (mpc_control_fuzzy.py:54-58)%s");
-    if (B > (1 << 30)) return fail(h, -EINVAL, "B too large%s");
-    DeviceGuard dg(h->device);
-    hipError_t e = dg.err;
-    if (e != hipSuccess) return hip_fail(h, e, "hipSetDevice");
-    // packed layout, instance-major within each array: in  = x0 | xref | uref | [wq_wr] | [z_guess]
-    //                                                   out = X | U | kkt | status, iters (int32)
-    const size_t N = h->cfg.N, b = (size_t)B, nz = 8 * N + 6;
-    const size_t sizes[5] = {b * 6, b * (N + 1) * 6, b * N * 2, wq_wr ? b * 8 : 0, z_guess ? b * nz : 0};
-    const double* srcs[5] = {x0, xref, uref, wq_wr, z_guess};
-    size_t in_d = 0;
-    for (size_t v : sizes) in_d += v;
-    const size_t nxo = b * (N + 1) * 6, nuo = b * N * 2, out_d = nxo + nuo + b + b;  // 2 x int32 per instance = 1 double
-    int rc = ensure_stage(h, in_d * 8, out_d * 8);
-    if (rc) return rc;
-    // the extra outputs of tt_solve_batch_ex: one device block, dual | gain | dxdx0 | dudx0 | sens_status (a call that
-    // asks for a sensitivity always has the multipliers in it)
-    tt_track_extra dx = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    const size_t n_dual = b * (N + 1) * ttmpc::kDualPerStage, n_gain = b * 12, n_dxx = b * (N + 1) * 36, n_dux = b * N * 12;
-    if (extra) {
-        const size_t ex_d = n_dual + (extra->gain ? n_gain : 0) + (extra->dxdx0 ? n_dxx : 0) +
-                            (extra->dudx0 ? n_dux : 0) + (extra->sens_status ? (b + 1) / 2 : 0);
-        rc = ensure_block(h, h->d_ex, h->ex_cap, ex_d * 8, "extra-output workspace");
-        if (rc) return rc;
-        double* p = reinterpret_cast<double*>(h->d_ex);
-        dx.dual = p; p += n_dual;
-        if (extra->gain) { dx.gain = p; p += n_gain; }
-        if (extra->dxdx0) { dx.dxdx0 = p; p += n_dxx; }
-        if (extra->dudx0) { dx.dudx0 = p; p += n_dux; }
-        if (extra->sens_status) dx.sens_status = reinterpret_cast<int*>(p);
-    }
-    // zero-copy for small batches (B = 1 latency: the two DMA copies cost more than the kernel's few PCIe reads); a call
-    // with extra outputs always copies (they are not part of the coherent mirror)
-    const bool zc = !extra && B <= zero_copy_max() && N < 64;
-    double* hin = reinterpret_cast<double*>(h->h_sin);
-    const double* dptr[5];
-    size_t off = 0;
-    for (int a = 0; a < 5; ++a) {
-        if (sizes[a]) memcpy(hin + off, srcs[a], sizes[a] * 8);
-        dptr[a] = reinterpret_cast<const double*>(zc ? h->zd_sin : h->d_sin) + off;
-        off += sizes[a];
-    }
-    hipStream_t s = h->stream;
-    if (!zc) {
-        e = hipMemcpyAsync(h->d_sin, h->h_sin, in_d * 8, hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) return hip_fail(h, e, "H2D copy");
-    }
-    double* dxo = reinterpret_cast<double*>(zc ? h->zd_sout : h->d_sout);
-    double* duo = dxo + nxo;
-    double* dkk = duo + nuo;
-    int* dst = reinterpret_cast<int*>(dkk + b);
-    int* dit = dst + b;
-    // zero-copy: status[] in the host block doubles as the instances' completion flags (the kernel writes each last,
-    // behind a system-scope release); a pending sentinel, then a poll of host memory instead of the stream wait
-    volatile int* hst = zc ? reinterpret_cast<volatile int*>(h->h_sout + (nxo + nuo + b) * 8) : nullptr;
-    if (zc)
-        for (int i = 0; i < B; ++i) hst[i] = kStatusPending;
-    if (extra)
-        rc = ex_device_impl(h, B, dptr[0], dptr[1], dptr[2], wq_wr ? dptr[3] : nullptr, z_guess ? dptr[4] : nullptr, dxo,
-                            duo, dst, dit, dkk, dx, s);
-    else
-        rc = solve_device_impl(h, B, dptr[0], dptr[1], dptr[2], wq_wr ? dptr[3] : nullptr, z_guess ? dptr[4] : nullptr,
-                               dxo, duo, dst, dit, dkk, s, zc ? 1 : 0);
-    if (rc) {
-        (void)hipStreamSynchronize(s);  // the H2D from the pinned staging buffer may still be in flight
-        return rc;
-    }
-    bool done = false;
-    if (zc) done = poll_done(hst, B);
-    e = zc ? hipSuccess : hipMemcpyAsync(h->h_sout, h->d_sout, out_d * 8, hipMemcpyDeviceToHost, s);
-    if (extra) {  // straight into the caller's arrays (the stream wait below covers them)
-#define EX_D2H(m, n, t) \
-    if (e == hipSuccess && extra->m) e = hipMemcpyAsync(extra->m, dx.m, (n) * sizeof(t), hipMemcpyDeviceToHost, s)
-        EX_D2H(dual, n_dual, double);
-        EX_D2H(gain, n_gain, double);
-        EX_D2H(dxdx0, n_dxx, double);
-        EX_D2H(dudx0, n_dux, double);
-        EX_D2H(sens_status, b, int);
-#undef EX_D2H
-    }
-    if (e == hipSuccess && !done) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(s);
-        return hip_fail(h, e, "solve");
-    }
-    const double* ho = reinterpret_cast<const double*>(h->h_sout);
-    memcpy(x_out, ho, nxo * 8);
-    memcpy(u_out, ho + nxo, nuo * 8);
-    if (kkt_res) memcpy(kkt_res, ho + nxo + nuo, b * 8);
-    const int* hi = reinterpret_cast<const int*>(ho + nxo + nuo + b);
-    memcpy(status, hi, b * 4);
-    if (iters) memcpy(iters, hi + b, b * 4);
-    return 0;
-}
-
-ttmpc::SensArgs make_sens_args(const Handle* h, int B) {
-    ttmpc::SensArgs a;
-    memset(&a, 0, sizeof a);
-    a.N = h->cfg.N;
-    a.B = B;
-    a.dt = h->cfg.dt;
-    a.L1 = h->cfg.L1;
-    a.L2 = h->cfg.L2;
-    a.Mh = h->cfg.Mh;
-    memcpy(a.Q, h->Q, sizeof a.Q);
-    memcpy(a.R, h->R, sizeof a.R);
-    memcpy(a.xlb, h->xlb, sizeof a.xlb);
-    memcpy(a.xub, h->xub, sizeof a.xub);
-    memcpy(a.ulb, h->ulb, sizeof a.ulb);
-    memcpy(a.uub, h->uub, sizeof a.uub);
-    return a;
-}
-
-// the sensitivity launch behind both entry points; the caller has made the handle's device current
-int sens_launch(Handle* h, int B, const double* d_x, const double* d_u, const double* d_dual, const double* d_wq_wr,
-                const int* d_status, const tt_track_extra& x, void* stream) {
-    ttmpc::SensArgs a = make_sens_args(h, B);
-    a.x = d_x;
-    a.u = d_u;
-    a.dual = d_dual;
-    a.wqwr = d_wq_wr;
-    a.status = d_status;
-    a.gain = x.gain;
-    a.dxdx0 = x.dxdx0;
-    a.dudx0 = x.dudx0;
-    a.sens_status = x.sens_status;
-    const hipError_t e = ttmpc::launch_track_sens(a, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(h, e, "sensitivity kernel launch");
-    return 0;
-}
-
-// solve (+ multiplier export) and, if asked for, the sensitivity launch behind it on the same stream
-int ex_device_impl(Handle* h, int B, const double* d_x0, const double* d_xref, const double* d_uref,
-                   const double* d_wq_wr, const double* d_z_guess, double* d_x_out, double* d_u_out, int* d_status,
-                   int* d_iters, double* d_kkt_res, const tt_track_extra& x, void* stream) {
-    if (!h) return fail(nullptr, -EINVAL, "NULL handle%s");
-    if (is_obca(h->cfg))
-        return fail(h, -EINVAL, "multipliers and sensitivities are exported by the tracking variants only%s");
-    if (B <= 0) return B < 0 ? fail(h, -EINVAL, "B must be >= 0%s") : 0;
-    const bool sens = wants_sens(x);
-    double* d_dual = x.dual;
-    DeviceGuard dg(h->device);
-    if (dg.err != hipSuccess) return hip_fail(h, dg.err, "hipSetDevice");
-    if (sens && !d_dual) {
-        const size_t bytes = (size_t)B * (h->cfg.N + 1) * ttmpc::kDualPerStage * sizeof(double);
-        const int rc = ensure_block(h, h->d_dual, h->dual_cap, bytes, "multiplier workspace");
-        if (rc) return rc;
-        d_dual = h->d_dual;
-    }
-    int rc = solve_device_impl(h, B, d_x0, d_xref, d_uref, d_wq_wr, d_z_guess, d_x_out, d_u_out, d_status, d_iters,
-                               d_kkt_res, stream, 0, d_dual);
-    if (rc || !sens) return rc;
-    return sens_launch(h, B, d_x_out, d_u_out, d_dual, d_wq_wr, d_status, x, stream);
-}
-}  // namespace
 
 int tt_solve_batch_ex(void* handle, int B, const double* x0, const double* xref, const double* uref,
                       const double* wq_wr, const double* z_guess, double* x_out, double* u_out, int* status,
                       int* iters, double* kkt_res, const tt_track_extra* extra) {
     Handle* h = static_cast<Handle*>(handle);
-    if (h && is_obca(h->cfg))
-        return fail(h, -EINVAL, "multipliers and sensitivities are exported by the tracking variants only%s");
-    return solve_host(handle, B, x0, xref, uref, wq_wr, z_guess, x_out, u_out, status, iters, kkt_res,
+    if (const int rc = prelude(h, B, kHandle | kTrackOnly)) return rc;
+    return solve_host(h, B, x0, xref, uref, wq_wr, z_guess, x_out, u_out, status, iters, kkt_res,
                       wants_any(extra) ? extra : nullptr);
 }
 
@@ -627,8 +579,7 @@ int tt_solve_batch_ex_device(void* handle, int B, const double* d_x0, const doub
                              int* d_status, int* d_iters, double* d_kkt_res, const tt_track_extra* d_extra,
                              void* stream) {
     Handle* h = static_cast<Handle*>(handle);
-    if (h && is_obca(h->cfg))
-        return fail(h, -EINVAL, "multipliers and sensitivities are exported by the tracking variants only%s");
+    if (const int rc = prelude(h, B, kHandle | kTrackOnly)) return rc;
     if (!wants_any(d_extra))
         return solve_device_impl(h, B, d_x0, d_xref, d_uref, d_wq_wr, d_z_guess, d_x_out, d_u_out, d_status, d_iters,
                                  d_kkt_res, stream, 0);
@@ -640,15 +591,9 @@ int tt_track_sens_device(void* handle, int B, const double* d_x, const double* d
                          const double* d_wq_wr, const int* d_status, double* d_gain, double* d_dxdx0,
                          double* d_dudx0, int* d_sens_status, void* stream) {
     Handle* h = static_cast<Handle*>(handle);
-    if (!h) return fail(nullptr, -EINVAL, "NULL handle%s");
-    if (is_obca(h->cfg))
-        return fail(h, -EINVAL, "multipliers and sensitivities are exported by the tracking variants only%s");
-    if (B < 0) return fail(h, -EINVAL, "B must be >= 0%s");
-    if (B == 0) return 0;
-    if (B > (1 << 30)) return fail(h, -EINVAL, "B too large%s");
+    if (const int rc = prelude(h, B, kHandle | kTrackOnly | kSign | kEmpty | kRange)) return result(rc);
     if (!d_x || !d_u || !d_dual || !d_status) return fail(h, -EINVAL, "NULL device buffer%s");
-    if (h->cfg.variant == TT_VARIANT_FUZZY && !d_wq_wr)
-        return fail(h, -EINVAL, "fuzzy variant needs per-instance weights (mpc_control_fuzzy.py:54-58)%s");
+    if (const int rc = prelude(h, B, kFuzzy, d_wq_wr)) return rc;
     DeviceGuard dg(h->device);
     if (dg.err != hipSuccess) return hip_fail(h, dg.err, "hipSetDevice");
     const tt_track_extra x = {nullptr, d_gain, d_dxdx0, d_dudx0, d_sens_status};
@@ -659,41 +604,18 @@ int tt_track_vjp_device(void* handle, int B, const double* d_x, const double* d_
                         const double* d_xref, const double* d_uref, const double* d_wq_wr, const int* d_status,
                         const double* d_grad_x, const double* d_grad_u, const tt_track_vjp_out* d_out, void* stream) {
     Handle* h = static_cast<Handle*>(handle);
-    if (!h) return fail(nullptr, -EINVAL, "NULL handle%s");
-    if (is_obca(h->cfg))
-        return fail(h, -EINVAL, "multipliers and sensitivities are exported by the tracking variants only%s");
-    if (B < 0) return fail(h, -EINVAL, "B must be >= 0%s");
+    if (const int rc = prelude(h, B, kHandle | kTrackOnly | kSign)) return rc;
     if (!d_grad_x && !d_grad_u) return fail(h, -EINVAL, "grad_x and grad_u are both NULL: no loss to differentiate%s");
-    if (B == 0) return 0;
-    if (B > (1 << 30)) return fail(h, -EINVAL, "B too large%s");
+    if (const int rc = prelude(h, B, kEmpty | kRange)) return result(rc);
     if (!d_x || !d_u || !d_dual || !d_status || !d_out) return fail(h, -EINVAL, "NULL device buffer%s");
     if (d_out->g_wq_wr && (!d_xref || !d_uref))
         return fail(h, -EINVAL, "the weight gradient needs xref and uref of the solve%s");
-    if (h->cfg.variant == TT_VARIANT_FUZZY && !d_wq_wr)
-        return fail(h, -EINVAL, "fuzzy variant needs per-instance weights (mpc_control_fuzzy.py:54-58)%s");
+    if (const int rc = prelude(h, B, kFuzzy, d_wq_wr)) return rc;
     DeviceGuard dg(h->device);
     if (dg.err != hipSuccess) return hip_fail(h, dg.err, "hipSetDevice");
-    ttmpc::VjpArgs a;
-    memset(&a, 0, sizeof a);
-    a.N = h->cfg.N;
-    a.B = B;
-    a.dt = h->cfg.dt;
-    a.L1 = h->cfg.L1;
-    a.L2 = h->cfg.L2;
-    a.Mh = h->cfg.Mh;
-    memcpy(a.Q, h->Q, sizeof a.Q);
-    memcpy(a.R, h->R, sizeof a.R);
-    memcpy(a.xlb, h->xlb, sizeof a.xlb);
-    memcpy(a.xub, h->xub, sizeof a.xub);
-    memcpy(a.ulb, h->ulb, sizeof a.ulb);
-    memcpy(a.uub, h->uub, sizeof a.uub);
-    a.x = d_x;
-    a.u = d_u;
-    a.dual = d_dual;
+    ttmpc::VjpArgs a = diff_args<ttmpc::VjpArgs>(h, B, d_x, d_u, d_dual, d_wq_wr, d_status);
     a.xref = d_xref;
     a.uref = d_uref;
-    a.wqwr = d_wq_wr;
-    a.status = d_status;
     a.gx = d_grad_x;
     a.gu = d_grad_u;
     a.g_x0 = d_out->g_x0;
@@ -710,60 +632,46 @@ int tt_track_vjp(void* handle, int B, const double* x, const double* u, const do
                  const double* uref, const double* wq_wr, const int* status, const double* grad_x,
                  const double* grad_u, const tt_track_vjp_out* out) {
     Handle* h = static_cast<Handle*>(handle);
-    if (!h) return fail(nullptr, -EINVAL, "NULL handle%s");
-    if (is_obca(h->cfg))
-        return fail(h, -EINVAL, "multipliers and sensitivities are exported by the tracking variants only%s");
-    if (B < 0) return fail(h, -EINVAL, "B must be >= 0%s");
+    if (const int rc = prelude(h, B, kHandle | kTrackOnly | kSign)) return rc;
     if (!grad_x && !grad_u) return fail(h, -EINVAL, "grad_x and grad_u are both NULL: no loss to differentiate%s");
-    if (B == 0) return 0;
-    if (B > (1 << 30)) return fail(h, -EINVAL, "B too large%s");
+    if (const int rc = prelude(h, B, kEmpty | kRange)) return result(rc);
     if (!x || !u || !dual || !status || !out) return fail(h, -EINVAL, "NULL host buffer%s");
     DeviceGuard dg(h->device);
     if (dg.err != hipSuccess) return hip_fail(h, dg.err, "hipSetDevice");
-    // one device block: the eight double inputs, the four outputs, then the two int arrays (status, vjp_status)
     const size_t N = h->cfg.N, b = (size_t)B, nx = b * (N + 1) * 6, nu = b * N * 2;
-    const double* src[8] = {x, u, dual, xref, uref, wq_wr, grad_x, grad_u};
-    const size_t len[8] = {nx, nu, b * (N + 1) * ttmpc::kDualPerStage, nx, nu, b * 8, nx, nu};
-    double* dst[4] = {out->g_x0, out->g_xref, out->g_uref, out->g_wq_wr};
-    const size_t olen[4] = {b * 6, nx, nu, b * 8};
-    size_t tot = b;  // the two int arrays
-    for (int t = 0; t < 8; ++t) tot += src[t] ? len[t] : 0;
-    for (int t = 0; t < 4; ++t) tot += dst[t] ? olen[t] : 0;
-    const int rc0 = ensure_block(h, h->d_ex, h->ex_cap, tot * 8, "adjoint staging");
-    if (rc0) return rc0;
+    Stager st;
+    const double *d_x, *d_u, *d_dual, *d_xref, *d_uref, *d_w, *d_gx, *d_gu;
+    const int* d_st;
+    tt_track_vjp_out dout;
+    st.in(x, nx, &d_x);
+    st.in(u, nu, &d_u);
+    st.in(dual, b * (N + 1) * ttmpc::kDualPerStage, &d_dual);
+    st.in(xref, nx, &d_xref);
+    st.in(uref, nu, &d_uref);
+    st.in(wq_wr, b * 8, &d_w);
+    st.in(grad_x, nx, &d_gx);
+    st.in(grad_u, nu, &d_gu);
+    st.in(status, b, &d_st);
+    st.out(out->g_x0, b * 6, &dout.g_x0);
+    st.out(out->g_xref, nx, &dout.g_xref);
+    st.out(out->g_uref, nu, &dout.g_uref);
+    st.out(out->g_wq_wr, b * 8, &dout.g_wq_wr);
+    st.out(out->vjp_status, b, &dout.vjp_status);
+    if (!st.carve(h->xfer)) return no_memory(h, "adjoint staging");
     hipStream_t s = h->stream;
-    double* p = reinterpret_cast<double*>(h->d_ex);
-    const double* din[8];
-    hipError_t e = hipSuccess;
-    for (int t = 0; t < 8; ++t) {
-        din[t] = src[t] ? p : nullptr;
-        if (src[t] && e == hipSuccess) e = hipMemcpyAsync(p, src[t], len[t] * 8, hipMemcpyHostToDevice, s);
-        if (src[t]) p += len[t];
-    }
-    tt_track_vjp_out dout = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    double** dmem[4] = {&dout.g_x0, &dout.g_xref, &dout.g_uref, &dout.g_wq_wr};
-    for (int t = 0; t < 4; ++t) {
-        if (dst[t]) { *dmem[t] = p; p += olen[t]; }
-    }
-    int* dst_st = reinterpret_cast<int*>(p);
-    if (out->vjp_status) dout.vjp_status = dst_st + b;
-    if (e == hipSuccess) e = hipMemcpyAsync(dst_st, status, b * sizeof(int), hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) {
+    st.upload(s);
+    if (st.err != hipSuccess) {
         (void)hipStreamSynchronize(s);
-        return hip_fail(h, e, "H2D copy");
+        return hip_fail(h, st.err, "H2D copy");
     }
-    const int rc = tt_track_vjp_device(handle, B, din[0], din[1], din[2], din[3], din[4], din[5], dst_st, din[6], din[7],
-                                       &dout, s);
+    const int rc = tt_track_vjp_device(handle, B, d_x, d_u, d_dual, d_xref, d_uref, d_w, d_st, d_gx, d_gu, &dout, s);
     if (rc) {
         (void)hipStreamSynchronize(s);
         return rc;
     }
-    for (int t = 0; t < 4; ++t)
-        if (dst[t] && e == hipSuccess) e = hipMemcpyAsync(dst[t], *dmem[t], olen[t] * 8, hipMemcpyDeviceToHost, s);
-    if (out->vjp_status && e == hipSuccess)
-        e = hipMemcpyAsync(out->vjp_status, dout.vjp_status, b * sizeof(int), hipMemcpyDeviceToHost, s);
+    st.download(s);
     const hipError_t es = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = es;
+    const hipError_t e = st.err != hipSuccess ? st.err : es;
     if (e != hipSuccess) return hip_fail(h, e, "adjoint");
     return 0;
 }
@@ -777,7 +685,8 @@ int ttx_solve_stamped(void* handle, int B, const double* d_x0, const double* d_x
                       void* stream) {
     Handle* h = static_cast<Handle*>(handle);
     if (!h || B <= 0 || !d_stamps) return -EINVAL;
-    ttmpc::TrackArgs a = make_args(h, B);
+    ttmpc::TrackArgs a;
+    if (const int rc = make_track_args(h, B, a)) return rc;
     a.x0 = d_x0;
     a.xref = d_xref;
     a.uref = d_uref;
@@ -786,33 +695,17 @@ int ttx_solve_stamped(void* handle, int B, const double* d_x0, const double* d_x
     a.status = d_status;
     a.iters = d_iters;
     a.stamps = d_stamps;
-    if (const size_t gb = ttmpc::track_global_bytes(a)) {
-        const int rc = ensure_prow(h, gb);
-        if (rc) return rc;
-        a.prow = h->d_prow;
-    }
     hipError_t e = ttmpc::launch_track(a, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? 0 : hip_fail(h, e, "stamped launch");
 }
 #endif
-
-int tt_obca_solve_batch_device(void* handle, int B, const double* d_x0, const double* d_xgoal, const double* d_xref,
-                               const double* d_uref, const double* d_z_guess, double* d_x_out, double* d_u_out,
-                               double* d_z_out, int* d_status, int* d_iters, double* d_kkt_res, void* stream) {
-    return tt_obca_solve_batch_iterate_device(handle, B, d_x0, d_xgoal, d_xref, d_uref, d_z_guess, d_x_out, d_u_out,
-                                              d_z_out, d_status, d_iters, d_kkt_res, nullptr, stream);
-}
 
 int tt_obca_solve_batch_iterate_device(void* handle, int B, const double* d_x0, const double* d_xgoal,
                                        const double* d_xref, const double* d_uref, const double* d_z_guess,
                                        double* d_x_out, double* d_u_out, double* d_z_out, int* d_status, int* d_iters,
                                        double* d_kkt_res, double* d_iterate_out, void* stream) {
     Handle* h = static_cast<Handle*>(handle);
-    if (!h) return fail(nullptr, -EINVAL, "NULL handle%s");
-    if (!is_obca(h->cfg)) return fail(h, -EINVAL, "handle is not an OBCA variant%s");
-    if (B < 0) return fail(h, -EINVAL, "B must be >= 0%s");
-    if (B == 0) return 0;
-    if (B > (1 << 24)) return fail(h, -EINVAL, "B too large%s");
+    if (const int rc = prelude(h, B, kHandle | kObcaOnly | kSign | kEmpty | kRange, nullptr, 1 << 24)) return result(rc);
     const bool plan = h->cfg.variant == TT_VARIANT_OBCA_PLAN;
     if (!d_x0 || !d_x_out || !d_u_out || !d_status) return fail(h, -EINVAL, "NULL device buffer%s");
     if (plan && !d_xgoal) return fail(h, -EINVAL, "plan variant needs the goal states%s");
@@ -820,8 +713,9 @@ int tt_obca_solve_batch_iterate_device(void* handle, int B, const double* d_x0, 
     DeviceGuard dg(h->device);
     hipError_t e = dg.err;
     if (e != hipSuccess) return hip_fail(h, e, "hipSetDevice");
-    int rc = ensure_ows(h, B);
-    if (rc) return rc;
+    const size_t board_bytes = ((size_t)B + 1) * ttmpc::kObcaBoardStride * 8;
+    if (!h->ows.ensure((size_t)B * ttmpc::obca_ws_doubles(h->cfg.N, h->cfg.M) * 8) || !h->board.ensure(board_bytes))
+        return fail(h, -ENOMEM, "OBCA workspace allocation failed for B=%s", std::to_string(B).c_str());
     ttmpc::ObcaArgs a;
     memset(&a, 0, sizeof a);
     a.N = h->cfg.N;
@@ -831,10 +725,6 @@ int tt_obca_solve_batch_iterate_device(void* handle, int B, const double* d_x0, 
     a.max_iter = h->cfg.max_iter;
     a.acc_iter = h->cfg.acc_iter;
     a.dual_init = h->cfg.dual_init;
-    a.dt = h->cfg.dt;
-    a.L1 = h->cfg.L1;
-    a.L2 = h->cfg.L2;
-    a.Mh = h->cfg.Mh;
     a.W1 = h->cfg.W1;
     a.W2 = h->cfg.W2;
     a.tol = h->cfg.tol;
@@ -843,12 +733,7 @@ int tt_obca_solve_batch_iterate_device(void* handle, int B, const double* d_x0, 
     a.eq_tol = 1e-5;   // trajectory_optimization.py:136-139
     a.fin_tol = 1e-2;  // trajectory_optimization.py:172-173
     a.tfac = plan ? 100.0 : 1.0;  // trajectory_optimization.py:180 / mpc_control_obs.py:39
-    memcpy(a.Q, h->Q, sizeof a.Q);
-    memcpy(a.R, h->R, sizeof a.R);
-    memcpy(a.xlb, h->xlb, sizeof a.xlb);
-    memcpy(a.xub, h->xub, sizeof a.xub);
-    memcpy(a.ulb, h->ulb, sizeof a.ulb);
-    memcpy(a.uub, h->uub, sizeof a.uub);
+    fill_model(a, h);
     memcpy(a.obs, h->obs, sizeof a.obs);
     a.x0 = d_x0;
     a.xgoal = d_xgoal;
@@ -862,7 +747,7 @@ int tt_obca_solve_batch_iterate_device(void* handle, int B, const double* d_x0, 
     a.iters = d_iters;
     a.kkt = d_kkt_res;
     a.itout = d_iterate_out;
-    a.ws = h->d_ows;
+    a.ws = static_cast<double*>(h->ows.p);
     a.stamps = h->obca_stamps;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (h->nhelp < 0) {  // one helper workgroup per CU: they run while CUs are idle (the batch's tail)
@@ -871,14 +756,70 @@ int tt_obca_solve_batch_iterate_device(void* handle, int B, const double* d_x0, 
         if (e != hipSuccess) return hip_fail(h, e, "hipDeviceGetAttribute");
         h->nhelp = cus;
     }
-    a.board = h->d_board;
+    a.board = static_cast<unsigned long long*>(h->board.p);
     a.nhelp = h->nhelp;
     a.spin_ticks = h->spin_ticks;
     a.fail_b = h->fail_b;
-    e = hipMemsetAsync(h->d_board, 0, ((size_t)B + 1) * ttmpc::kObcaBoardStride * 8, s);
+    e = hipMemsetAsync(a.board, 0, board_bytes, s);
     if (e != hipSuccess) return hip_fail(h, e, "hipMemsetAsync (OBCA board)");
     e = ttmpc::launch_obca(a, s);
     if (e != hipSuccess) return hip_fail(h, e, "OBCA kernel launch");
+    return 0;
+}
+
+int tt_obca_solve_batch_device(void* handle, int B, const double* d_x0, const double* d_xgoal, const double* d_xref,
+                               const double* d_uref, const double* d_z_guess, double* d_x_out, double* d_u_out,
+                               double* d_z_out, int* d_status, int* d_iters, double* d_kkt_res, void* stream) {
+    return tt_obca_solve_batch_iterate_device(handle, B, d_x0, d_xgoal, d_xref, d_uref, d_z_guess, d_x_out, d_u_out,
+                                              d_z_out, d_status, d_iters, d_kkt_res, nullptr, stream);
+}
+
+int tt_obca_solve_batch_iterate(void* handle, int B, const double* x0, const double* xgoal, const double* xref,
+                                const double* uref, const double* z_guess, double* x_out, double* u_out, double* z_out,
+                                int* status, int* iters, double* kkt_res, double* iterate_out) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (const int rc = prelude(h, B, kHandle | kObcaOnly | kSign | kEmpty)) return result(rc);
+    const bool plan = h->cfg.variant == TT_VARIANT_OBCA_PLAN;
+    if (!x0 || !status || (plan && !xgoal) || (!plan && (!xref || !uref)))
+        return fail(h, -EINVAL, "NULL host buffer%s");
+    DeviceGuard dg(h->device);
+    if (dg.err != hipSuccess) return hip_fail(h, dg.err, "hipSetDevice");
+    const size_t N = h->cfg.N, nz = ttmpc::obca_n(h->cfg.N, h->cfg.M), b = (size_t)B;
+    // the launch writes X, U, status, iters and kkt whether or not the caller wants them back
+    Stager st;
+    const double *d_x0, *d_xg, *d_xr, *d_ur, *d_zg;
+    double *d_xo, *d_uo, *d_zo, *d_kkt, *d_itout;
+    int *d_st, *d_it;
+    st.in(x0, b * 6, &d_x0);
+    st.in(plan ? xgoal : nullptr, b * 6, &d_xg);
+    st.in(plan ? nullptr : xref, b * (N + 1) * 6, &d_xr);
+    st.in(plan ? nullptr : uref, b * N * 2, &d_ur);
+    st.in(z_guess, b * nz, &d_zg);
+    st.out(iterate_out, b * ttmpc::obca_iterate_len(h->cfg.N, h->cfg.M), &d_itout);  // (the diagnostic export)
+    st.out(x_out, b * (N + 1) * 6, &d_xo, true);
+    st.out(u_out, b * N * 2, &d_uo, true);
+    st.out(z_out, b * nz, &d_zo);
+    st.out(status, b, &d_st, true);
+    st.out(iters, b, &d_it, true);
+    st.out(kkt_res, b, &d_kkt, true);
+    if (!st.carve(h->xfer))
+        return fail(h, -ENOMEM, "device workspace allocation failed for B=%s", std::to_string(B).c_str());
+    hipStream_t s = h->stream;
+    st.upload(s);
+    if (st.err != hipSuccess) {
+        (void)hipStreamSynchronize(s);
+        return hip_fail(h, st.err, "H2D copy");
+    }
+    const int rc = tt_obca_solve_batch_iterate_device(h, B, d_x0, d_xg, d_xr, d_ur, d_zg, d_xo, d_uo, d_zo, d_st, d_it,
+                                                      d_kkt, d_itout, s);
+    if (rc) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    st.download(s);
+    const hipError_t es = hipStreamSynchronize(s);
+    const hipError_t e = st.err != hipSuccess ? st.err : es;
+    if (e != hipSuccess) return hip_fail(h, e, "OBCA solve");
     return 0;
 }
 
@@ -887,70 +828,6 @@ int tt_obca_solve_batch(void* handle, int B, const double* x0, const double* xgo
                         int* status, int* iters, double* kkt_res) {
     return tt_obca_solve_batch_iterate(handle, B, x0, xgoal, xref, uref, z_guess, x_out, u_out, z_out, status, iters,
                                        kkt_res, nullptr);
-}
-
-int tt_obca_solve_batch_iterate(void* handle, int B, const double* x0, const double* xgoal, const double* xref,
-                                const double* uref, const double* z_guess, double* x_out, double* u_out, double* z_out,
-                                int* status, int* iters, double* kkt_res, double* iterate_out) {
-    Handle* h = static_cast<Handle*>(handle);
-    if (!h) return fail(nullptr, -EINVAL, "NULL handle%s");
-    if (!is_obca(h->cfg)) return fail(h, -EINVAL, "handle is not an OBCA variant%s");
-    if (B < 0) return fail(h, -EINVAL, "B must be >= 0%s");
-    if (B == 0) return 0;
-    const bool plan = h->cfg.variant == TT_VARIANT_OBCA_PLAN;
-    if (!x0 || !status || (plan && !xgoal) || (!plan && (!xref || !uref)))
-        return fail(h, -EINVAL, "NULL host buffer%s");
-    DeviceGuard dg(h->device);
-    hipError_t e = dg.err;
-    if (e != hipSuccess) return hip_fail(h, e, "hipSetDevice");
-    int rc = ensure_ws(h, B);
-    if (rc == 0) rc = ensure_ows(h, B);
-    if (rc) return rc;
-    const size_t N = h->cfg.N, nz = ttmpc::obca_n(h->cfg.N, h->cfg.M), b = (size_t)B;
-    hipStream_t s = h->stream;
-#define H2D(d, hp, bytes) \
-    if (e == hipSuccess) e = hipMemcpyAsync((d), (hp), (bytes), hipMemcpyHostToDevice, s)
-#define D2H(hp, d, bytes) \
-    if (e == hipSuccess) e = hipMemcpyAsync((hp), (d), (bytes), hipMemcpyDeviceToHost, s)
-    H2D(h->d_x0, x0, b * 6 * 8);
-    if (plan) H2D(h->d_oxg, xgoal, b * 6 * 8);
-    if (!plan) {
-        H2D(h->d_xref, xref, b * (N + 1) * 6 * 8);
-        H2D(h->d_uref, uref, b * N * 2 * 8);
-    }
-    if (z_guess) H2D(h->d_ozg, z_guess, b * nz * 8);
-    if (e != hipSuccess) return hip_fail(h, e, "H2D copy");
-    // the diagnostic iterate export gets a buffer of its own for this call (it is not a hot-path output)
-    const size_t it_bytes = b * ttmpc::obca_iterate_len(h->cfg.N, h->cfg.M) * 8;
-    double* d_itout = nullptr;
-    if (iterate_out) {
-        e = hipMalloc((void**)&d_itout, it_bytes);
-        if (e != hipSuccess) return fail(h, -ENOMEM, "iterate export allocation failed for B=%s", std::to_string(B).c_str());
-    }
-    rc = tt_obca_solve_batch_iterate_device(h, B, h->d_x0, plan ? h->d_oxg : nullptr, plan ? nullptr : h->d_xref,
-                                            plan ? nullptr : h->d_uref, z_guess ? h->d_ozg : nullptr, h->d_xo, h->d_uo,
-                                            z_out ? h->d_ozo : nullptr, h->d_st, h->d_it, h->d_kkt, d_itout, s);
-    if (rc) {
-        (void)hipStreamSynchronize(s);
-        if (d_itout) (void)hipFree(d_itout);
-        return rc;
-    }
-    if (iterate_out) D2H(iterate_out, d_itout, it_bytes);
-    if (x_out) D2H(x_out, h->d_xo, b * (N + 1) * 6 * 8);
-    if (u_out) D2H(u_out, h->d_uo, b * N * 2 * 8);
-    if (z_out) D2H(z_out, h->d_ozo, b * nz * 8);
-    D2H(status, h->d_st, b * 4);
-    if (iters) D2H(iters, h->d_it, b * 4);
-    if (kkt_res) D2H(kkt_res, h->d_kkt, b * 8);
-#undef H2D
-#undef D2H
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (d_itout) {
-        if (e != hipSuccess) (void)hipStreamSynchronize(s);
-        (void)hipFree(d_itout);
-    }
-    if (e != hipSuccess) return hip_fail(h, e, "OBCA solve");
-    return 0;
 }
 
 /* diagnostics only (not part of include/ttmpc.h): per-instance phase cycle sums of the handle's next OBCA
@@ -985,8 +862,7 @@ static_assert(TT_HANDOFF_TIMEOUT == 6, "tt_obca.hip kStatusHandoffTimeout");
 int tt_plan_batch(void* handle, int B, const double* x0, const double* xgoal, const double* z_guess, double* x_out,
                   double* u_out, int* status, int* iters) {
     Handle* h = static_cast<Handle*>(handle);
-    if (!h) return fail(nullptr, -EINVAL, "NULL handle%s");
-    if (h->cfg.variant != TT_VARIANT_OBCA_PLAN) return fail(h, -EINVAL, "tt_plan_batch needs a TT_VARIANT_OBCA_PLAN handle%s");
+    if (const int rc = prelude(h, B, kHandle | kPlanOnly)) return rc;
     if (!x_out || !u_out) return fail(h, -EINVAL, "NULL host buffer%s");
     return tt_obca_solve_batch(handle, B, x0, xgoal, nullptr, nullptr, z_guess, x_out, u_out, nullptr, status, iters,
                                nullptr);
@@ -997,14 +873,9 @@ void tt_destroy(void* handle) {
     if (!h) return;
     DeviceGuard dg(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    free_ws(h);
-    free_ows(h);
     free_stage(h);
-    if (h->d_prow) (void)hipFree(h->d_prow);
-    if (h->d_dual) (void)hipFree(h->d_dual);
-    if (h->d_ex) (void)hipFree(h->d_ex);
     if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h;  // (its device buffers go with it, under the handle's device)
 }
 
 const char* tt_last_error(void* handle) {

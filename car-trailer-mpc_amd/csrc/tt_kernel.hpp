@@ -62,9 +62,10 @@ hipError_t launch_track(const TrackArgs& a, hipStream_t stream);
 // the exporting twins of the same builds (tt_track_dual.hip); launch_track forwards to it when a.dual is set
 hipError_t launch_track_dual(const TrackArgs& a, hipStream_t stream);
 
-// ---------------- sensitivity of a tracking solution to x_init (tt_sens.hip) ----------------
+// ---------------- derivatives of a tracking solution (tt_sens.hip, tt_vjp.hip, tt_sens_stage.hpp) ----------------
 constexpr int kDualPerStage = 22;  // y 6 | z_L 8 | z_U 8: the stage rows rY .. rZU + 7 of tt_track.hip, in that order
-struct SensArgs {
+// what both derivative kernels read: the model and the primal-dual point of the solve they differentiate
+struct DiffArgs {
     int N, B;
     double dt, L1, L2, Mh;
     double Q[36], R[4];
@@ -72,8 +73,13 @@ struct SensArgs {
     const double* x;      // [B][N+1][6]
     const double* u;      // [B][N][2]
     const double* dual;   // [B][N+1][kDualPerStage]
-    const double* wqwr;   // [B][8] or nullptr
     const int* status;    // [B] of the solve
+    const double* wqwr;   // [B][8] or nullptr  (last: with wqwr before status the adjoint kernel's SGPR spills, which
+                          //  otherwise all fit VGPR lanes, leave it a 36-byte private segment)
+};
+
+// sensitivity to x_init (tt_sens.hip)
+struct SensArgs : DiffArgs {
     double* gain;         // [B][2][6] or nullptr
     double* dxdx0;        // [B][N+1][6][6] or nullptr
     double* dudx0;        // [B][N][2][6] or nullptr
@@ -83,19 +89,10 @@ struct SensArgs {
 inline int sens_lds_doubles(int N) { return 24 * (N + 1) + 12 * N + 192; }
 hipError_t launch_track_sens(const SensArgs& a, hipStream_t stream);
 
-// ---------------- adjoint of a tracking solution: dL/d(x_init, xref, uref, weights) (tt_vjp.hip) ----------------
-struct VjpArgs {
-    int N, B;
-    double dt, L1, L2, Mh;
-    double Q[36], R[4];
-    double xlb[6], xub[6], ulb[2], uub[2];  // raw bounds (relaxed in-kernel as track_kernel relaxes them)
-    const double* x;      // [B][N+1][6]
-    const double* u;      // [B][N][2]
-    const double* dual;   // [B][N+1][kDualPerStage]
+// adjoint: dL/d(x_init, xref, uref, weights) (tt_vjp.hip)
+struct VjpArgs : DiffArgs {
     const double* xref;   // [B][N+1][6]; read for g_wqwr only
     const double* uref;   // [B][N][2];   read for g_wqwr only
-    const double* wqwr;   // [B][8] or nullptr
-    const int* status;    // [B] of the solve
     const double* gx;     // [B][N+1][6] upstream dL/dX, or nullptr (zeros)
     const double* gu;     // [B][N][2]   upstream dL/dU, or nullptr (zeros)
     double* g_x0;         // [B][6] or nullptr

@@ -15,13 +15,13 @@
 #include <errno.h>
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdio.h>
 
+#include "tt_lqr_model.hpp"
 #include "ttmpc.h"
 
-namespace {
+using namespace ttmpc;
 
-constexpr int kMaxDoublings = 64;
+namespace {
 
 struct LqrVjpArgs {
     tt_plant p;
@@ -36,21 +36,7 @@ struct LqrVjpArgs {
     int B;
 };
 
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-}
-
 __device__ __forceinline__ bool wave_any(bool v) { return __ballot(v) != 0ull; }
-
-// (X Y)[i][j] over 6x6 row-major LDS matrices; lanes < 36
-__device__ __forceinline__ double mm(const double* X, const double* Y, int i, int j) {
-    double s = 0.0;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) s += X[i * 6 + k] * Y[k * 6 + j];
-    return s;
-}
 
 // (X Y')[i][j]
 __device__ __forceinline__ double mmt(const double* X, const double* Y, int i, int j) {
@@ -80,23 +66,12 @@ __global__ void __launch_bounds__(64) lqr_vjp_kernel(LqrVjpArgs a) {
     const double* xg = a.xg + b6;
     const double* xc = a.xc + b6;
     const double gs = a.gs ? a.gs[b] : 0.0;
-    const double ps = xg[3], v = xg[5];
-    const double sth = sin(xg[2]), cth = cos(xg[2]), sps = sin(ps), cps = cos(ps);
-    const double c2 = 1.0 / (cos(xg[4]) * cos(xg[4])), t = tan(xg[4]);
+    const GoalTrig gt(xg);
+    const double v = gt.v, sth = gt.sth, cth = gt.cth, sps = gt.sps, cps = gt.cps, c2 = gt.c2, t = gt.t;
     bool bad = !isfinite(gs);
     // A = I + dt J(x_goal), the forward's expressions; P; G = gs dx dx' + (GP + GP') / 2
     if (own) {
-        double J = 0.0;
-        if (i == 0 && j == 2) J = -v * sth;
-        if (i == 0 && j == 5) J = cth;
-        if (i == 1 && j == 2) J = v * cth;
-        if (i == 1 && j == 5) J = sth;
-        if (i == 2 && j == 4) J = v * c2 / L1;
-        if (i == 2 && j == 5) J = t / L1;
-        if (i == 3 && j == 3) J = v * t * Mh * sps / (L1 * L2) - v * cps / L2;
-        if (i == 3 && j == 4) J = -v * c2 / L1 * (1 + Mh / L2 * cps);
-        if (i == 3 && j == 5) J = -t / L1 * (1 + Mh / L2 * cps) - sps / L2;
-        const double Aij = (i == j ? 1.0 : 0.0) + dt * J, Pij = a.P[b36 + lane];
+        const double Aij = (i == j ? 1.0 : 0.0) + dt * goal_jacobian(i, j, gt, L1, L2, Mh), Pij = a.P[b36 + lane];
         double Gij = gs * (xc[i] - xg[i]) * (xc[j] - xg[j]);
         if (a.GP) Gij += 0.5 * (a.GP[b36 + lane] + a.GP[b36 + j * 6 + i]);
         sA[lane] = Aij;
@@ -232,10 +207,5 @@ extern "C" int tt_lqr_score_vjp_device(int B, const tt_plant* p, const double* R
     a.out = *out;
     a.B = B;
     hipLaunchKernelGGL(lqr_vjp_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        fprintf(stderr, "ttmpc: lqr_vjp_kernel launch failed: %s\n", hipGetErrorString(e));
-        return -EIO;
-    }
-    return 0;
+    return launched("lqr_vjp_kernel");
 }

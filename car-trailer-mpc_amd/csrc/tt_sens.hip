@@ -1,15 +1,8 @@
 // Sensitivity of a tracking solution to x_init on gfx950 (tt_solve_batch_ex, tt_track_sens_device).
 //
-// At the returned primal-dual point (x, u, y, z_L, z_U) of the tracking NLP (tt_track.hip) the Newton matrix of the
-// barrier problem with the bound multipliers eliminated is the KKT matrix of an equality-constrained LQ problem:
-//   stage Hessians  W_k + Sigma_x,k  (states)  and  R_k = 2 R_w + Sigma_u,k  (inputs),
-//     W_k = 2 Q_w - dt sum_i y_{k+1,i} d2f_i/dx2 (x_k)  (k < N; the 7 curvature entries of tt_track.hip),  W_N = 2 Q_w,
-//     Sigma = z_L / (v - lb) + z_U / (ub - v) with the relaxed bounds of the solver,
-//   dynamics  dx_{k+1} = A_k dx_k + B du_k,  A_k = I + dt J_f(x_k),  B = dt B_F  (B[5][0] = B[4][1] = dt).
-// A unit perturbation of the x_0 - x_init row (sIPOPT's parametric step) is therefore one un-iterated, un-regularised
-// Riccati pass:
-//   P_N = W_N + Sigma_x,N;  G_k = R_k + B' P_{k+1} B;  K_k = G_k^-1 B' P_{k+1} A_k;
-//   P_k = W_k + Sigma_x,k + A_k' P_{k+1} (A_k - B K_k)            (P_0 is not needed: x_0 is pinned)
+// The Newton matrix at the returned primal-dual point and the backward Riccati sweep over it (P_k, G_k, K_k) are
+// described where they live, in tt_sens_stage.hpp.  A unit perturbation of the x_0 - x_init row (sIPOPT's parametric
+// step) is that sweep followed by
 //   Phi_0 = I;  dU_k = -K_k Phi_k;  Phi_{k+1} = A_k Phi_k + B dU_k.
 // gain = dU_0 = -K_0.
 //
@@ -31,13 +24,14 @@ namespace {
 
 using sens::W;
 using sens::sAJ;
-using sens::sWC;
-using sens::sSG;
 using sens::d_idx;
-using sens::w_idx;
-constexpr int kStage = 24;  // per stage: dt*J (9) | curvature (7) | Sigma (8), tt_sens_stage.hpp
 // tiles behind the stage and gain records: P, M = P A, A, two Phi buffers, 2 R_w  (sens_lds_doubles: 24 S + 12 N + 192)
-constexpr int tP = 0, tM = 36, tA = 72, tF0 = 108, tF1 = 144, tRW = 180;
+struct Layout {
+    static constexpr bool kVec = false;
+    static constexpr int kStage = 24;  // per stage: dt*J (9) | curvature (7) | Sigma (8), tt_sens_stage.hpp
+    static constexpr int tP = 0, tM = 36, tA = 72, tF0 = 108, tF1 = 144, tRW = 180;
+};
+constexpr int kStage = Layout::kStage, tM = Layout::tM, tF0 = Layout::tF0, tF1 = Layout::tF1;
 
 __device__ __forceinline__ void zero_outputs(const SensArgs& a, int b, int lane) {
     const int N = a.N, S = N + 1;
@@ -70,65 +64,12 @@ __global__ __launch_bounds__(W) void track_sens_kernel(SensArgs a) {
     // ---- stage-parallel pre-pass ----
     for (int k = lane; k <= N; k += W)
         sens::linearise_stage(a, stg + k * kStage, x + k * 6, u + k * 2, dl + k * kDualPerStage, k == N);
-    // ---- entry-parallel roles ----
-    const bool ent = lane < 36, gl = lane >= 36 && lane < 48;
-    const int i = ent ? lane / 6 : 0, j = ent ? lane % 6 : 0;
-    const int gr = gl ? (lane - 36) / 6 : 0, gc = gl ? (lane - 36) % 6 : 0;
-    const int wi = w_idx(i, j);
-    double q2 = 0.0;  // 2 Q_w (i, j)
-    if (ent) {
-        const double q = 0.5 * (a.Q[i * 6 + j] + a.Q[j * 6 + i]);
-        q2 = 2.0 * (wq ? q * wq[i] * wq[j] : q);
-    }
-    if (lane < 4) {  // 2 R_w
-        const int ri = lane / 2, rj = lane % 2;
-        const double rr = 0.5 * (a.R[ri * 2 + rj] + a.R[rj * 2 + ri]);
-        T[tRW + lane] = 2.0 * (wq ? rr * wq[6 + ri] * wq[6 + rj] : rr);
-    }
-    __syncthreads();
+    // ---- backward sweep (entry-parallel) ----
+    const sens::Roles ro(lane);
+    const bool ent = ro.ent, gl = ro.gl;
+    const int i = ro.i, j = ro.j, gr = ro.gr, gc = ro.gc;
     bool bad = false;
-    if (ent) {
-        const double p = q2 + (i == j ? stg[N * kStage + sSG + i] : 0.0);
-        T[tP + lane] = p;
-        bad |= !isfinite(p);
-    }
-    __syncthreads();
-    // ---- backward sweep ----
-    for (int k = N - 1; k >= 0; --k) {
-        const double* r = stg + k * kStage;
-        if (ent) {
-            const int di = d_idx(i, j);
-            T[tA + lane] = (i == j ? 1.0 : 0.0) + (di >= 0 ? r[sAJ + di] : 0.0);
-        }
-        __syncthreads();
-        if (ent) {  // M = P A
-            double m = 0.0;
-            for (int l = 0; l < 6; ++l) m += T[tP + i * 6 + l] * T[tA + l * 6 + j];
-            T[tM + lane] = m;
-        }
-        __syncthreads();
-        if (gl) {  // K = G^-1 B' M, G = R_k + B' P B
-            const double g00 = T[tRW + 0] + r[sSG + 6] + dt * dt * T[tP + 5 * 6 + 5];
-            const double g01 = T[tRW + 1] + dt * dt * T[tP + 5 * 6 + 4];
-            const double g11 = T[tRW + 3] + r[sSG + 7] + dt * dt * T[tP + 4 * 6 + 4];
-            const double det = g00 * g11 - g01 * g01;
-            const double h0 = dt * T[tM + 5 * 6 + gc], h1 = dt * T[tM + 4 * 6 + gc];
-            const double kv = gr == 0 ? (g11 * h0 - g01 * h1) / det : (g00 * h1 - g01 * h0) / det;
-            if (!(g00 > 0.0) || !(det > 0.0) || !isfinite(g00) || !isfinite(det) || !isfinite(kv)) bad = true;
-            Ks[k * 12 + gr * 6 + gc] = kv;
-        }
-        __syncthreads();
-        if (ent && k > 0) {  // P_k = W_k + Sigma_x + A' M - H' K,  H = B' M
-            double p = q2 + (wi >= 0 ? r[sWC + wi] : 0.0) + (i == j ? r[sSG + i] : 0.0);
-            double am = 0.0;
-            for (int l = 0; l < 6; ++l) am += T[tA + l * 6 + i] * T[tM + l * 6 + j];
-            const double hk = dt * T[tM + 5 * 6 + i] * Ks[k * 12 + j] + dt * T[tM + 4 * 6 + i] * Ks[k * 12 + 6 + j];
-            p = p + (am - hk);
-            bad |= !isfinite(p);
-            T[tP + lane] = p;  // (the reads of P of this stage are behind the barriers above)
-        }
-        __syncthreads();
-    }
+    sens::backward_sweep<Layout>(a, ro, wq, stg, Ks, T, lane, bad);
     if (__ballot(bad) != 0ull) {
         zero_outputs(a, b, lane);
         if (a.sens_status && lane == 0) a.sens_status[b] = 1;

@@ -14,15 +14,13 @@
 #include <errno.h>
 #include <math.h>
 #include <hip/hip_runtime.h>
-#include <stdio.h>
 
+#include "tt_launch.hpp"
 #include "ttmpc.h"
 
+using namespace ttmpc;
+
 namespace {
-
-constexpr int kThreads = 256;
-
-__host__ __device__ inline int grid_for(long long n) { return (int)((n + kThreads - 1) / kThreads); }
 
 // ---- reference window + measured state, one thread per (instance, stage) --------------------------
 // xr[j] = plan_x[min(k+j, Np)] in all three branches of simulation.py:486-501; ur[j] = plan_u[min(k+j,
@@ -423,15 +421,6 @@ __global__ void __launch_bounds__(kThreads) interp_kernel(int B, int Np, int n, 
     double* Du = du + ((size_t)b * Nn + c) * 2;
     Du[0] = Su[0];
     Du[1] = Su[1];
-}
-
-int launched(const char* where) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        fprintf(stderr, "ttmpc: %s launch failed: %s\n", where, hipGetErrorString(e));
-        return -EIO;
-    }
-    return 0;
 }
 
 }  // namespace

@@ -10,15 +10,13 @@
 #include <errno.h>
 #include <math.h>
 #include <hip/hip_runtime.h>
-#include <stdio.h>
 
+#include "tt_launch.hpp"
 #include "ttmpc.h"
 
+using namespace ttmpc;
+
 namespace {
-
-constexpr int kThreads = 256;
-
-inline int grid_for(long long n) { return (int)((n + kThreads - 1) / kThreads); }
 
 __device__ __forceinline__ double sign0(double x) { return x > 0.0 ? 1.0 : (x < 0.0 ? -1.0 : 0.0); }
 
@@ -191,15 +189,6 @@ __global__ void __launch_bounds__(kThreads) sim_window_vjp_kernel(
 #pragma unroll
             for (int i = 0; i < 8; ++i) g_w_acc[(size_t)b * 8 + i] += g_w[(size_t)b * 8 + i];
     }
-}
-
-int launched(const char* where) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        fprintf(stderr, "ttmpc: %s launch failed: %s\n", where, hipGetErrorString(e));
-        return -EIO;
-    }
-    return 0;
 }
 
 }  // namespace

@@ -3,19 +3,16 @@
 // For a scalar loss L(X, U) with upstream gradient g = (gX, gU), the gradient with respect to the parameters of the
 // solve comes from ONE solve with the Newton matrix K of tt_sens.hip (it is symmetric):
 //   K (lam_z, lam_y) = (g, 0),   dL/dtheta = -lam' dF/dtheta,   F = (grad f + J' y - z_L + z_U, c).
-// With P_k, G_k, K_k exactly as track_sens_kernel forms them, the right-hand side adds two vector sweeps:
-//   p_N = gX_N;  kappa_k = G_k^-1 (gU_k + B' p_{k+1});  p_k = gX_k + A_k' (p_{k+1} - P_{k+1} B kappa_k)     k = N-1 .. 0
+// The backward sweep (tt_sens_stage.hpp: P_k, G_k, K_k as track_sens_kernel forms them, with p_k and kappa_k of the
+// right-hand side g beside them) is followed by one vector sweep forward:
 //   lx_0 = 0;    lu_k = -K_k lx_k + kappa_k;            lx_{k+1} = A_k lx_k + B lu_k                        k = 0 .. N-1
 // and the gradients are (Q_w = D_q Q_s D_q, R_w likewise, e_k = x_k - xref_k, f_k = u_k - uref_k):
 //   dL/dx_init = p_0;   dL/dxref_k = 2 Q_w lx_k;   dL/duref_k = 2 R_w lu_k;
 //   dL/dwq_i = -2 sum_k ( lx_k,i (Q_s D_q e_k)_i + (Q_s D_q lx_k)_i e_k,i ),   dL/dwr_i likewise with lu, R_s, D_r, f.
 //
 // Mapping: one 64-lane wavefront per instance.  The pre-pass is stage-parallel and shared with track_sens_kernel
-// (tt_sens_stage.hpp); lane k also brings g_k into its stage record.  The backward sweep is the entry-parallel 6x6
-// sweep of track_sens_kernel between the same four barriers per stage, with lanes 48..53 carrying p and lanes 54, 55
-// kappa next to the matrix lanes: kappa's division runs beside K's, and p_k is formed beside P_k as
-// gX_k + A' p_{k+1} - (B' M)' kappa (M = P A; A' P B = M' B because P is symmetric), so the vector recursion needs no
-// barrier of its own (its branches still issue behind the matrix lanes': DESIGN.md has the times).
+// (tt_sens_stage.hpp); lane k also brings g_k into its stage record.  The backward sweep is the shared one with its
+// vector lanes switched on (lanes 48..53 carry p, lanes 54, 55 kappa): the same four barriers per stage.
 // The forward sweep is six lanes and one barrier per stage.  The output phase is
 // stage-parallel again, and the eight weight gradients are butterfly reductions over the lanes.
 // LDS: lx_k | lu_k overlay Sigma_k (dead once the backward sweep is through) and kappa_k overlays gU_k (dead once
@@ -33,15 +30,17 @@ namespace {
 
 using sens::W;
 using sens::sAJ;
-using sens::sWC;
 using sens::sSG;
 using sens::d_idx;
-using sens::w_idx;
-constexpr int kStage = kVjpStage;  // the sensitivity record (24) | g: gX 6, gU 2 (then kappa) | pad
-constexpr int sG = 24;
 // tiles behind the stage and gain records: P, M = P A, A, 2 Q_w, 2 R_w, two p buffers, kappa
-constexpr int tP = 0, tM = 36, tA = 72, tQW = 108, tRW = 144, tPV0 = 148, tPV1 = 154, tKP = 160;
-static_assert(tKP + 2 <= kVjpTiles, "tiles");
+struct Layout {
+    static constexpr bool kVec = true;
+    static constexpr int kStage = kVjpStage;  // the sensitivity record (24) | g: gX 6, gU 2 (then kappa) | pad
+    static constexpr int sG = 24;
+    static constexpr int tP = 0, tM = 36, tA = 72, tQW = 108, tRW = 144, tPV0 = 148, tPV1 = 154, tKP = 160;
+};
+constexpr int kStage = Layout::kStage, sG = Layout::sG, tQW = Layout::tQW, tRW = Layout::tRW;
+static_assert(Layout::tKP + 2 <= kVjpTiles, "tiles");
 
 __device__ __forceinline__ void zero_outputs(const VjpArgs& a, int b, int lane) {
     const int N = a.N, S = N + 1;
@@ -96,80 +95,9 @@ __global__ __launch_bounds__(W) void track_vjp_kernel(VjpArgs a) {
             r[sG + v] = g;
         }
     }
-    // ---- roles of the serial sweeps ----
-    const bool ent = lane < 36, gl = lane >= 36 && lane < 48, pl = lane >= 48 && lane < 54, kl = lane >= 54 && lane < 56;
-    const int i = ent ? lane / 6 : 0, j = ent ? lane % 6 : 0;
-    const int gr = gl ? (lane - 36) / 6 : 0, gc = gl ? (lane - 36) % 6 : 0;
-    const int pi = pl ? lane - 48 : 0, kr = kl ? lane - 54 : 0;
-    const int wi = w_idx(i, j);
-    double q2 = 0.0;  // 2 Q_w (i, j)
-    if (ent) {
-        const double q = 0.5 * (a.Q[i * 6 + j] + a.Q[j * 6 + i]);
-        q2 = 2.0 * (wq ? q * wq[i] * wq[j] : q);
-        T[tQW + lane] = q2;
-    }
-    if (lane < 4) {  // 2 R_w
-        const int ri = lane / 2, rj = lane % 2;
-        const double rr = 0.5 * (a.R[ri * 2 + rj] + a.R[rj * 2 + ri]);
-        T[tRW + lane] = 2.0 * (wq ? rr * wq[6 + ri] * wq[6 + rj] : rr);
-    }
-    __syncthreads();
-    if (ent) {
-        const double p = q2 + (i == j ? stg[N * kStage + sSG + i] : 0.0);
-        T[tP + lane] = p;
-        bad |= !isfinite(p);
-    }
-    int pc = tPV0, pn = tPV1;  // p_{k+1} and p_k: every p lane reads all of the one while it writes its entry of the other
-    if (pl) T[pc + pi] = stg[N * kStage + sG + pi];  // p_N = gX_N
-    __syncthreads();
-    // ---- backward sweep ----
-    for (int k = N - 1; k >= 0; --k) {
-        double* r = stg + k * kStage;
-        if (ent) {
-            const int di = d_idx(i, j);
-            T[tA + lane] = (i == j ? 1.0 : 0.0) + (di >= 0 ? r[sAJ + di] : 0.0);
-        }
-        __syncthreads();
-        if (ent) {  // M = P A
-            double m = 0.0;
-            for (int l = 0; l < 6; ++l) m += T[tP + i * 6 + l] * T[tA + l * 6 + j];
-            T[tM + lane] = m;
-        }
-        __syncthreads();
-        if (gl || kl) {  // K = G^-1 B' M and kappa = G^-1 (gU + B' p), G = R_k + B' P B: the two divisions side by side
-            const double g00 = T[tRW + 0] + r[sSG + 6] + dt * dt * T[tP + 5 * 6 + 5];
-            const double g01 = T[tRW + 1] + dt * dt * T[tP + 5 * 6 + 4];
-            const double g11 = T[tRW + 3] + r[sSG + 7] + dt * dt * T[tP + 4 * 6 + 4];
-            const double det = g00 * g11 - g01 * g01;
-            const double h0 = gl ? dt * T[tM + 5 * 6 + gc] : r[sG + 6] + dt * T[pc + 5];
-            const double h1 = gl ? dt * T[tM + 4 * 6 + gc] : r[sG + 7] + dt * T[pc + 4];
-            const double kv = (gl ? gr : kr) == 0 ? (g11 * h0 - g01 * h1) / det : (g00 * h1 - g01 * h0) / det;
-            if (!(g00 > 0.0) || !(det > 0.0) || !isfinite(g00) || !isfinite(det) || !isfinite(kv)) bad = true;
-            if (gl) Ks[k * 12 + gr * 6 + gc] = kv;
-            else T[tKP + kr] = kv;
-        }
-        __syncthreads();
-        if (ent && k > 0) {  // P_k = W_k + Sigma_x + A' M - H' K,  H = B' M
-            double p = q2 + (wi >= 0 ? r[sWC + wi] : 0.0) + (i == j ? r[sSG + i] : 0.0);
-            double am = 0.0;
-            for (int l = 0; l < 6; ++l) am += T[tA + l * 6 + i] * T[tM + l * 6 + j];
-            const double hk = dt * T[tM + 5 * 6 + i] * Ks[k * 12 + j] + dt * T[tM + 4 * 6 + i] * Ks[k * 12 + 6 + j];
-            p = p + (am - hk);
-            bad |= !isfinite(p);
-            T[tP + lane] = p;  // (the reads of P of this stage are behind the barriers above)
-        }
-        if (pl) {  // p_k = gX_k + A' p_{k+1} - (B' M)' kappa   (A' P B = M' B; M outlives this phase, P does not)
-            double s = 0.0;
-            for (int l = 0; l < 6; ++l) s += T[tA + l * 6 + pi] * T[pc + l];
-            const double hk = dt * T[tM + 5 * 6 + pi] * T[tKP + 0] + dt * T[tM + 4 * 6 + pi] * T[tKP + 1];
-            s = r[sG + pi] + (s - hk);
-            bad |= !isfinite(s);
-            T[pn + pi] = s;
-        }
-        if (kl) r[sG + 6 + kr] = T[tKP + kr];  // kappa_k takes gU_k's place for the forward sweep
-        __syncthreads();
-        const int t = pc; pc = pn; pn = t;
-    }
+    // ---- backward sweep (entry-parallel, p and kappa beside the matrix lanes) ----
+    const sens::Roles ro(lane);
+    const int pc = sens::backward_sweep<Layout>(a, ro, wq, stg, Ks, T, lane, bad);  // T[pc ..]: p_0
     // ---- forward sweep: lx_k | lu_k into the Sigma slots of stage k ----
     if (lane < 6) stg[sSG + lane] = 0.0;
     __syncthreads();
@@ -203,7 +131,7 @@ __global__ __launch_bounds__(W) void track_vjp_kernel(VjpArgs a) {
         return;
     }
     // ---- outputs ----
-    if (a.g_x0 && pl) a.g_x0[(size_t)b * 6 + pi] = T[pc + pi];
+    if (a.g_x0 && ro.pl) a.g_x0[(size_t)b * 6 + ro.pi] = T[pc + ro.pi];
     const double* xr = a.xref ? a.xref + (size_t)b * S * 6 : nullptr;
     const double* ur = a.uref ? a.uref + (size_t)b * N * 2 : nullptr;
     const bool wgrad = a.g_wqwr && xr && ur;

@@ -233,19 +233,19 @@ def default_device() -> int:
     return 0
 
 
-class BatchSolver:
-    """One library handle = one compiled NLP (the reference's CasADi ``nlpsol`` object) on one GPU."""
+class _Solver:
+    """What the two solver classes share: the library handle made from a config, its release and its error text."""
 
-    def __init__(self, N, params, Q, R, xlb, xub, ulb, uub, variant=TT_VARIANT_TRACK, tol=0.0, acc_tol=0.0,
-                 max_iter=0, acc_iter=0, device=None):
+    def __init__(self, N, params, W1, W2, Q, R, xlb, xub, ulb, uub, obstacles, variant, tol, acc_tol, max_iter,
+                 acc_iter, dual_init, device):
         cfg = TTConfig()
-        cfg.nx, cfg.nu, cfg.N, cfg.M = 6, 2, int(N), 0
+        cfg.nx, cfg.nu, cfg.N, cfg.M = 6, 2, int(N), 0 if obstacles is None else int(obstacles.shape[0])
         cfg.dt, cfg.L1, cfg.L2, cfg.Mh = float(params["dt"]), float(params["L1"]), float(params["L2"]), float(params["M"])
-        cfg.W1, cfg.W2 = float(params.get("W1", 0.0)), float(params.get("W2", 0.0))
+        cfg.W1, cfg.W2 = float(W1), float(W2)
         cfg.variant = int(variant)
         cfg.tol, cfg.acc_tol, cfg.max_iter, cfg.acc_iter = float(tol), float(acc_tol), int(max_iter), int(acc_iter)
         cfg.warm_shift_compat = 0
-        cfg.dual_init = 0
+        cfg.dual_init = int(bool(dual_init))
         self.N = int(N)
         self.variant = int(variant)
         self.Q = _f64(Q, (6, 6))
@@ -254,7 +254,7 @@ class BatchSolver:
         self.device = default_device() if device is None else int(device)
         h = C.c_void_p()
         L = lib()
-        rc = L.tt_create(C.byref(cfg), _ptr(self.Q), _ptr(self.R), *[_ptr(b) for b in self.bounds], None,
+        rc = L.tt_create(C.byref(cfg), _ptr(self.Q), _ptr(self.R), *[_ptr(b) for b in self.bounds], _ptr(obstacles),
                          self.device, C.byref(h))
         if rc != 0:
             raise TTError(f"tt_create failed ({rc}): {L.tt_last_error(None).decode()}")
@@ -274,6 +274,23 @@ class BatchSolver:
 
     def _err(self, rc, what):
         raise TTError(f"{what} failed ({rc}): {self._L.tt_last_error(self._h).decode()}")
+
+
+def _track_inputs(N, x0, xref, uref, wq_wr, z_guess):
+    """B and the contiguous float64 inputs of a tracking host call: (B, x0, xref, uref, wq_wr|None, z_guess|None)."""
+    x0 = _f64(x0)
+    B = x0.shape[0] if x0.ndim == 2 else 1
+    return (B, x0.reshape(B, 6), _f64(xref, (B, N + 1, 6)), _f64(uref, (B, N, 2)),
+            None if wq_wr is None else _f64(wq_wr, (B, 8)), None if z_guess is None else _f64(z_guess, (B, 8 * N + 6)))
+
+
+class BatchSolver(_Solver):
+    """One library handle = one compiled NLP (the reference's CasADi ``nlpsol`` object) on one GPU."""
+
+    def __init__(self, N, params, Q, R, xlb, xub, ulb, uub, variant=TT_VARIANT_TRACK, tol=0.0, acc_tol=0.0,
+                 max_iter=0, acc_iter=0, device=None):
+        super().__init__(N, params, params.get("W1", 0.0), params.get("W2", 0.0), Q, R, xlb, xub, ulb, uub, None,
+                         variant, tol, acc_tol, max_iter, acc_iter, False, device)
 
     # Small host calls (the reference's one-instance-per-step controllers) reuse per-shape arrays whose ctypes pointers
     # were made once: building ten pointers per call cost more wall clock than the copies they avoid.
@@ -324,13 +341,7 @@ class BatchSolver:
             r = self._small_call(B, x0a, xref, uref, wq_wr, z_guess)
             if r is not None:
                 return r
-        x0 = _f64(x0)
-        B = x0.shape[0] if x0.ndim == 2 else 1
-        x0 = x0.reshape(B, 6)
-        xref = _f64(xref, (B, N + 1, 6))
-        uref = _f64(uref, (B, N, 2))
-        w = None if wq_wr is None else _f64(wq_wr, (B, 8))
-        zg = None if z_guess is None else _f64(z_guess, (B, 8 * N + 6))
+        B, x0, xref, uref, w, zg = _track_inputs(N, x0, xref, uref, wq_wr, z_guess)
         X = np.empty((B, N + 1, 6))
         U = np.empty((B, N, 2))
         st = np.empty(B, dtype=np.int32)
@@ -355,13 +366,7 @@ class BatchSolver:
         dU/dx0 (B,N,2,6).  sens_status comes with either sensitivity.  Returns a ``TrackExResult``; X, U, status, iters
         and kkt are bitwise those of ``solve``."""
         N = self.N
-        x0 = _f64(x0)
-        B = x0.shape[0] if x0.ndim == 2 else 1
-        x0 = x0.reshape(B, 6)
-        xref = _f64(xref, (B, N + 1, 6))
-        uref = _f64(uref, (B, N, 2))
-        w = None if wq_wr is None else _f64(wq_wr, (B, 8))
-        zg = None if z_guess is None else _f64(z_guess, (B, 8 * N + 6))
+        B, x0, xref, uref, w, zg = _track_inputs(N, x0, xref, uref, wq_wr, z_guess)
         r = TrackExResult(X=np.empty((B, N + 1, 6)), U=np.empty((B, N, 2)), status=np.empty(B, dtype=np.int32),
                           iters=np.empty(B, dtype=np.int32), kkt=np.empty(B))
         if duals:
@@ -450,40 +455,18 @@ def _warn_handoff(st):
                       "partial iterates (status TT_HANDOFF_TIMEOUT)", RuntimeWarning, stacklevel=3)
 
 
-class ObcaSolver:
+class ObcaSolver(_Solver):
     """Handle for the OBCA NLPs: TT_VARIANT_OBCA_PLAN (TrajectoryOptimization) or TT_VARIANT_TRACK_OBCA
     (MPCTrackingControlObs).  obstacles: (M,4) array of (cx, cy, w, h)."""
 
     def __init__(self, N, params, Q, R, xlb, xub, ulb, uub, obstacles, variant=TT_VARIANT_OBCA_PLAN, tol=0.0,
                  acc_tol=0.0, max_iter=0, acc_iter=0, dual_init=False, device=None):
         ob = _f64(obstacles).reshape(-1, 4)
-        cfg = TTConfig()
-        cfg.nx, cfg.nu, cfg.N, cfg.M = 6, 2, int(N), int(ob.shape[0])
-        cfg.dt, cfg.L1, cfg.L2, cfg.Mh = float(params["dt"]), float(params["L1"]), float(params["L2"]), float(params["M"])
-        cfg.W1, cfg.W2 = float(params["W1"]), float(params["W2"])
-        cfg.variant = int(variant)
-        cfg.tol, cfg.acc_tol, cfg.max_iter, cfg.acc_iter = float(tol), float(acc_tol), int(max_iter), int(acc_iter)
-        cfg.warm_shift_compat = 0
-        cfg.dual_init = int(bool(dual_init))
-        self.N, self.M, self.variant = int(N), int(ob.shape[0]), int(variant)
-        self.n = obca_n(self.N, self.M)
+        self.M = int(ob.shape[0])
+        self.n = obca_n(int(N), self.M)
         self.obstacles = ob
-        self.Q = _f64(Q, (6, 6))
-        self.R = _f64(R, (2, 2))
-        self.bounds = tuple(_bounds(b, n) for b, n in ((xlb, 6), (xub, 6), (ulb, 2), (uub, 2)))
-        self.device = default_device() if device is None else int(device)
-        h = C.c_void_p()
-        L = lib()
-        rc = L.tt_create(C.byref(cfg), _ptr(self.Q), _ptr(self.R), *[_ptr(b) for b in self.bounds], _ptr(ob),
-                         self.device, C.byref(h))
-        if rc != 0:
-            raise TTError(f"tt_create failed ({rc}): {L.tt_last_error(None).decode()}")
-        self._h = h
-        self._L = L
-
-    close = BatchSolver.close
-    __del__ = BatchSolver.__del__
-    _err = BatchSolver._err
+        super().__init__(N, params, params["W1"], params["W2"], Q, R, xlb, xub, ulb, uub, ob, variant, tol, acc_tol,
+                         max_iter, acc_iter, dual_init, device)
 
     def solve(self, x0, x_goal=None, xref=None, uref=None, z_guess=None, iterate=False):
         """Host arrays -> (X (B,N+1,6), U (B,N,2), z (B,n), status, iters, kkt); with ``iterate=True`` also the final
