@@ -20,4 +20,12 @@ inline int launched(const char* where) {
     return 0;
 }
 
+// A flat elementwise launch: one thread per element of n, kThreads per block, on `stream`.  0 or -EIO as launched();
+// the caller has validated its arguments and dealt with an empty batch.
+template <typename... P, typename... A>
+inline int launch_flat(void (*kernel)(P...), const char* name, long long n, void* stream, A... args) {
+    hipLaunchKernelGGL(kernel, dim3(grid_for(n)), dim3(kThreads), 0, (hipStream_t)stream, args...);
+    return launched(name);
+}
+
 }  // namespace ttmpc

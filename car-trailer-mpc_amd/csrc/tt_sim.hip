@@ -24,20 +24,18 @@ namespace {
 
 // ---- reference window + measured state, one thread per (instance, stage) --------------------------
 // xr[j] = plan_x[min(k+j, Np)] in all three branches of simulation.py:486-501; ur[j] = plan_u[min(k+j,
-// Np-1)] while k < Np, else 0 (the k >= N branch zeroes the inputs).
-__global__ void __launch_bounds__(kThreads) sim_window_kernel(int B, int N, int k, int Np, const double* __restrict__ px,
-                                                              const double* __restrict__ pu, int per_instance,
-                                                              const double* __restrict__ state,
-                                                              const double* __restrict__ noise,
-                                                              double* __restrict__ xmeas, double* __restrict__ xr,
-                                                              double* __restrict__ ur) {
+// Np-1)] while k < Np, else 0 (the k >= N branch zeroes the inputs).  The thread of stage N also writes the
+// measured state xmeas = state [+ noise] (xmeas / noise may be null).
+__device__ __forceinline__ void window_row(int B, int N, int k, int Np, const double* __restrict__ px,
+                                           const double* __restrict__ pu, int per_instance,
+                                           const double* __restrict__ state, const double* __restrict__ noise,
+                                           double* __restrict__ xmeas, double* __restrict__ xr,
+                                           double* __restrict__ ur) {
     const long long t = (long long)blockIdx.x * kThreads + threadIdx.x;
-    const long long total = (long long)B * (N + 1);
-    if (t >= total) return;
+    if (t >= (long long)B * (N + 1)) return;
     const int b = (int)(t / (N + 1)), j = (int)(t % (N + 1));
     const size_t pb = per_instance ? (size_t)b : 0;
-    const int sx = min(k + j, Np);
-    const double* src = px + (pb * (Np + 1) + sx) * 6;
+    const double* src = px + (pb * (Np + 1) + min(k + j, Np)) * 6;
     double* dst = xr + ((size_t)b * (N + 1) + j) * 6;
 #pragma unroll
     for (int i = 0; i < 6; ++i) dst[i] = src[i];
@@ -60,6 +58,15 @@ __global__ void __launch_bounds__(kThreads) sim_window_kernel(int B, int N, int 
     }
 }
 
+__global__ void __launch_bounds__(kThreads) sim_window_kernel(int B, int N, int k, int Np, const double* __restrict__ px,
+                                                              const double* __restrict__ pu, int per_instance,
+                                                              const double* __restrict__ state,
+                                                              const double* __restrict__ noise,
+                                                              double* __restrict__ xmeas, double* __restrict__ xr,
+                                                              double* __restrict__ ur) {
+    window_row(B, N, k, Np, px, pu, per_instance, state, noise, xmeas, xr, ur);
+}
+
 // ---- the same window for a step index read from the device (hipGraph replay of a closed-loop step):
 // k = ks[*step] (the reference's float-accumulated clock, precomputed), noise = noise_all[*step]
 __global__ void __launch_bounds__(kThreads) sim_window_indexed_kernel(int B, int N, const int* __restrict__ ks,
@@ -71,33 +78,8 @@ __global__ void __launch_bounds__(kThreads) sim_window_indexed_kernel(int B, int
                                                                       double* __restrict__ xmeas,
                                                                       double* __restrict__ xr, double* __restrict__ ur) {
     const int j = *step;
-    const int k = ks[j];
-    const double* noise = noise_all ? noise_all + (size_t)j * B * 6 : nullptr;
-    const long long t = (long long)blockIdx.x * kThreads + threadIdx.x;
-    if (t >= (long long)B * (N + 1)) return;
-    const int b = (int)(t / (N + 1)), jj = (int)(t % (N + 1));
-    const size_t pb = per_instance ? (size_t)b : 0;
-    const double* src = px + (pb * (Np + 1) + min(k + jj, Np)) * 6;
-    double* dst = xr + ((size_t)b * (N + 1) + jj) * 6;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) dst[i] = src[i];
-    if (jj < N) {
-        double* du = ur + ((size_t)b * N + jj) * 2;
-        if (k < Np) {
-            const double* su = pu + (pb * Np + min(k + jj, Np - 1)) * 2;
-            du[0] = su[0];
-            du[1] = su[1];
-        } else {
-            du[0] = 0.0;
-            du[1] = 0.0;
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            const double v = state[(size_t)b * 6 + i];
-            xmeas[(size_t)b * 6 + i] = noise ? v + noise[(size_t)b * 6 + i] : v;
-        }
-    }
+    window_row(B, N, ks[j], Np, px, pu, per_instance, state, noise_all ? noise_all + (size_t)j * B * 6 : nullptr, xmeas,
+               xr, ur);
 }
 
 // closed-loop logs at the device step index: S[step+1] = state, Ua[step] = applied control, status /
@@ -257,21 +239,30 @@ __device__ __forceinline__ void plant_apply(const tt_plant& p, double* q, double
     }
 }
 
+// the common tail of the two plant kernels for instance b: report the applied control, then, unless the instance has
+// stopped, state[b] <- update(state[b], (a, om)) in place
+__device__ __forceinline__ void plant_step(const tt_plant& p, int b, double* __restrict__ state, double a, double om,
+                                           const double* __restrict__ noise, double* __restrict__ u_applied,
+                                           bool go = true) {
+    if (u_applied) { u_applied[(size_t)b * 2] = a; u_applied[(size_t)b * 2 + 1] = om; }
+    if (!go) return;
+    double q[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) q[i] = state[(size_t)b * 6 + i];
+    plant_apply(p, q, a, om, noise ? noise + (size_t)b * 6 : nullptr);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) state[(size_t)b * 6 + i] = q[i];
+}
+
 __global__ void __launch_bounds__(kThreads) plant_kernel(int B, tt_plant p, double* __restrict__ state,
                                                          const double* __restrict__ u, long long u_stride,
                                                          const int* __restrict__ status, int zero_on_fail,
                                                          const double* __restrict__ noise, double* __restrict__ u_applied) {
     const int b = blockIdx.x * kThreads + threadIdx.x;
     if (b >= B) return;
-    double q[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) q[i] = state[(size_t)b * 6 + i];
     double a = u[b * u_stride], om = u[b * u_stride + 1];
     if (zero_on_fail && status && status[b] > TT_ACCEPTABLE) { a = 0.0; om = 0.0; }   // simulation_nmpc.py:208-214
-    if (u_applied) { u_applied[(size_t)b * 2] = a; u_applied[(size_t)b * 2 + 1] = om; }
-    plant_apply(p, q, a, om, noise ? noise + (size_t)b * 6 : nullptr);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) state[(size_t)b * 6 + i] = q[i];
+    plant_step(p, b, state, a, om, noise, u_applied);
 }
 
 // ---- closed-loop failure policies of the three drivers, fused with the plant update ----------------------
@@ -317,14 +308,7 @@ __global__ void __launch_bounds__(kThreads) policy_plant_kernel(int B, tt_plant 
         }
         if (!go) { a = 0.0; om = 0.0; active[b] = 0; }
     }
-    if (u_applied) { u_applied[(size_t)b * 2] = a; u_applied[(size_t)b * 2 + 1] = om; }
-    if (!go) return;
-    double q[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) q[i] = state[(size_t)b * 6 + i];
-    plant_apply(p, q, a, om, noise ? noise + (size_t)b * 6 : nullptr);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) state[(size_t)b * 6 + i] = q[i];
+    plant_step(p, b, state, a, om, noise, u_applied, go);
 }
 
 // ---- fuzzy weights (mpc_control_fuzzy.py:90-119) from the measured state and the window's first reference
@@ -351,6 +335,13 @@ __global__ void __launch_bounds__(kThreads) fuzzy_kernel(int B, int N, const dou
     o[7] = clip(fmax(1.0, steer_rate));
 }
 
+// element e = 8k + r of pack(X, U) = [x_0, u_0, ..., x_{N-1}, u_{N-1}, x_N] for instance b (stage N has r < 6 only)
+__device__ __forceinline__ double pack_elem(const double* __restrict__ X, const double* __restrict__ U, int N, int b,
+                                            int e) {
+    const int k = e / 8, r = e % 8;
+    return r < 6 ? X[((size_t)b * (N + 1) + k) * 6 + r] : U[((size_t)b * N + k) * 2 + (r - 6)];
+}
+
 // ---- NMPC warm start: z_guess = have ? shift(last) : [xr_0, ur_0, ..., xr_N] ----------------------------
 // shift (mpc_control_nmpc.py:69-88): stages 1..N-1 move to 0..N-2; the last stage is built from
 // last[-8:-2] / last[-2:] (bug_compatible: [u_{N-1}, x_N[0:4]] and x_N[4:6]) or the intended x_N / u_{N-1}.
@@ -365,9 +356,7 @@ __global__ void __launch_bounds__(kThreads) warm_kernel(int B, int N, const doub
     const double* L = last + (size_t)b * n;
     double v;
     if (!have[b]) {
-        const int k = e / 8, r = e % 8;   // reference-copy guess (mpc_control_nmpc.py:60-67)
-        v = k == N ? xr[((size_t)b * (N + 1) + N) * 6 + r]
-                   : (r < 6 ? xr[((size_t)b * (N + 1) + k) * 6 + r] : ur[((size_t)b * N + k) * 2 + (r - 6)]);
+        v = pack_elem(xr, ur, N, b, e);   // reference-copy guess (mpc_control_nmpc.py:60-67)
     } else if (e < 8 * (N - 1)) {
         v = L[e + 8];
     } else {
@@ -391,9 +380,7 @@ __global__ void __launch_bounds__(kThreads) record_kernel(int B, int N, const do
     if (t >= (long long)B * n) return;
     const int b = (int)(t / n), e = (int)(t % n);
     if (status[b] > TT_ACCEPTABLE) return;
-    const int k = e / 8, r = e % 8;
-    last[t] = k == N ? X[((size_t)b * (N + 1) + N) * 6 + r]
-                     : (r < 6 ? X[((size_t)b * (N + 1) + k) * 6 + r] : U[((size_t)b * N + k) * 2 + (r - 6)]);
+    last[t] = pack_elem(X, U, N, b, e);
     if (e == 0) have[b] = 1;
 }
 
@@ -433,10 +420,8 @@ int tt_sim_window_device(int B, int N, int k, int Np, const double* plan_x, cons
     if (B < 0 || N < 1 || Np < 1 || k < 0 || !plan_x || !plan_u || !xref || !uref || (x_meas && !state))
         return -EINVAL;
     if (B == 0) return 0;
-    const long long tot = (long long)B * (N + 1);
-    hipLaunchKernelGGL(sim_window_kernel, dim3(grid_for(tot)), dim3(kThreads), 0, (hipStream_t)stream, B, N, k, Np,
-                       plan_x, plan_u, per_instance, state, meas_noise, x_meas, xref, uref);
-    return launched("sim_window_kernel");
+    return launch_flat(sim_window_kernel, "sim_window_kernel", (long long)B * (N + 1), stream, B, N, k, Np, plan_x,
+                       plan_u, per_instance, state, meas_noise, x_meas, xref, uref);
 }
 
 int tt_sim_window_indexed_device(int B, int N, const int* ks, const int* step, int Np, const double* plan_x,
@@ -445,10 +430,8 @@ int tt_sim_window_indexed_device(int B, int N, const int* ks, const int* step, i
     if (B < 0 || N < 1 || Np < 1 || !ks || !step || !plan_x || !plan_u || !state || !x_meas || !xref || !uref)
         return -EINVAL;
     if (B == 0) return 0;
-    const long long tot = (long long)B * (N + 1);
-    hipLaunchKernelGGL(sim_window_indexed_kernel, dim3(grid_for(tot)), dim3(kThreads), 0, (hipStream_t)stream, B, N,
-                       ks, step, Np, plan_x, plan_u, per_instance, state, noise_all, x_meas, xref, uref);
-    return launched("sim_window_indexed_kernel");
+    return launch_flat(sim_window_indexed_kernel, "sim_window_indexed_kernel", (long long)B * (N + 1), stream, B, N, ks,
+                       step, Np, plan_x, plan_u, per_instance, state, noise_all, x_meas, xref, uref);
 }
 
 int tt_sim_log_advance_device(int B, int* step, const double* state, const double* u_applied, const int* status,
@@ -456,9 +439,8 @@ int tt_sim_log_advance_device(int B, int* step, const double* state, const doubl
                               void* stream) {
     if (B < 0 || !step || !state || !u_applied || !status || !S || !Ua || !Ss || !Si || !Sc) return -EINVAL;
     if (B > 0) {
-        hipLaunchKernelGGL(sim_log_kernel, dim3(grid_for(B)), dim3(kThreads), 0, (hipStream_t)stream, B, step, state,
-                           u_applied, status, iters, flag, S, Ua, Ss, Si, Sc);
-        const int rc = launched("sim_log_kernel");
+        const int rc = launch_flat(sim_log_kernel, "sim_log_kernel", B, stream, B, (const int*)step, state, u_applied,
+                                   status, iters, flag, S, Ua, Ss, Si, Sc);
         if (rc) return rc;
     }
     hipLaunchKernelGGL(sim_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step);
@@ -479,9 +461,8 @@ int tt_plant_update_noise_device(int B, const tt_plant* p, double* state, const 
                                  void* stream) {
     if (B < 0 || !p || !state || !u || u_stride < 2) return -EINVAL;
     if (B == 0) return 0;
-    hipLaunchKernelGGL(plant_kernel, dim3(grid_for(B)), dim3(kThreads), 0, (hipStream_t)stream, B, *p, state, u,
-                       u_stride, status, zero_on_fail, state_noise, u_applied);
-    return launched("plant_kernel");
+    return launch_flat(plant_kernel, "plant_kernel", B, stream, B, *p, state, u, u_stride, status, zero_on_fail,
+                       state_noise, u_applied);
 }
 
 int tt_plant_update_device(int B, const tt_plant* p, double* state, const double* u, long long u_stride,
@@ -496,9 +477,8 @@ int tt_policy_plant_noise_device(int B, const tt_plant* p, int policy, double* s
         policy < TT_POLICY_TRACK || policy > TT_POLICY_FUZZY)
         return -EINVAL;
     if (B == 0) return 0;
-    hipLaunchKernelGGL(policy_plant_kernel, dim3(grid_for(B)), dim3(kThreads), 0, (hipStream_t)stream, B, *p, policy,
-                       state, u, u_stride, status, u_last, consecutive, failures, active, state_noise, u_applied);
-    return launched("policy_plant_kernel");
+    return launch_flat(policy_plant_kernel, "policy_plant_kernel", B, stream, B, *p, policy, state, u, u_stride, status,
+                       u_last, consecutive, failures, active, state_noise, u_applied);
 }
 
 int tt_policy_plant_device(int B, const tt_plant* p, int policy, double* state, const double* u, long long u_stride,
@@ -511,35 +491,31 @@ int tt_policy_plant_device(int B, const tt_plant* p, int policy, double* state, 
 int tt_fuzzy_weights_device(int B, int N, const double* x, const double* xref, double* wq_wr, void* stream) {
     if (B < 0 || N < 1 || !x || !xref || !wq_wr) return -EINVAL;
     if (B == 0) return 0;
-    hipLaunchKernelGGL(fuzzy_kernel, dim3(grid_for(B)), dim3(kThreads), 0, (hipStream_t)stream, B, N, x, xref, wq_wr);
-    return launched("fuzzy_kernel");
+    return launch_flat(fuzzy_kernel, "fuzzy_kernel", B, stream, B, N, x, xref, wq_wr);
 }
 
 int tt_warm_start_device(int B, int N, const double* last, const int* have, const double* xref, const double* uref,
                          int bug_compatible, double* z_guess, void* stream) {
     if (B < 0 || N < 1 || !last || !have || !xref || !uref || !z_guess) return -EINVAL;
     if (B == 0) return 0;
-    hipLaunchKernelGGL(warm_kernel, dim3(grid_for((long long)B * (8 * N + 6))), dim3(kThreads), 0,
-                       (hipStream_t)stream, B, N, last, have, xref, uref, bug_compatible, z_guess);
-    return launched("warm_kernel");
+    return launch_flat(warm_kernel, "warm_kernel", (long long)B * (8 * N + 6), stream, B, N, last, have, xref, uref,
+                       bug_compatible, z_guess);
 }
 
 int tt_record_solution_device(int B, int N, const double* x_out, const double* u_out, const int* status, double* last,
                               int* have, void* stream) {
     if (B < 0 || N < 1 || !x_out || !u_out || !status || !last || !have) return -EINVAL;
     if (B == 0) return 0;
-    hipLaunchKernelGGL(record_kernel, dim3(grid_for((long long)B * (8 * N + 6))), dim3(kThreads), 0,
-                       (hipStream_t)stream, B, N, x_out, u_out, status, last, have);
-    return launched("record_kernel");
+    return launch_flat(record_kernel, "record_kernel", (long long)B * (8 * N + 6), stream, B, N, x_out, u_out, status,
+                       last, have);
 }
 
 int tt_interpolate_device(int B, int Np, int factor, const double* state_traj, const double* input_traj,
                           double* state_out, double* input_out, void* stream) {
     if (B < 0 || Np < 1 || factor < 1 || !state_traj || !input_traj || !state_out || !input_out) return -EINVAL;
     if (B == 0) return 0;
-    hipLaunchKernelGGL(interp_kernel, dim3(grid_for((long long)B * (factor * Np + 1))), dim3(kThreads), 0,
-                       (hipStream_t)stream, B, Np, factor, state_traj, input_traj, state_out, input_out);
-    return launched("interp_kernel");
+    return launch_flat(interp_kernel, "interp_kernel", (long long)B * (factor * Np + 1), stream, B, Np, factor,
+                       state_traj, input_traj, state_out, input_out);
 }
 
 }  // extern "C"

@@ -202,20 +202,18 @@ int tt_policy_plant_vjp_device(int B, int N, const tt_plant* p, int policy, cons
     if (B <= 0 || N < 1 || N > tt_max_horizon() || !p || !state || !status || !active_after || !consecutive ||
         !adj_state || !adj_u_last || !grad_u || policy < TT_POLICY_TRACK || policy > TT_POLICY_FUZZY)
         return -EINVAL;
-    hipLaunchKernelGGL(policy_plant_vjp_kernel, dim3(grid_for(B)), dim3(kThreads), 0, (hipStream_t)stream, B, N, *p,
-                       policy, state, status, active_before, active_after, consecutive, grad_u_applied,
-                       adj_state, adj_u_last, grad_u, g_state_noise);
-    return launched("policy_plant_vjp_kernel");
+    return launch_flat(policy_plant_vjp_kernel, "policy_plant_vjp_kernel", B, stream, B, N, *p, policy, state, status,
+                       active_before, active_after, consecutive, grad_u_applied, adj_state, adj_u_last, grad_u,
+                       g_state_noise);
 }
 
 int tt_sim_window_vjp_device(int B, int N, int k, int Np, const double* g_xref, const double* g_uref, double* g_plan_x,
                              double* g_plan_u, const double* g_x0, const double* grad_state, double* adj_state,
                              const double* g_wq_wr, double* g_wq_wr_acc, double* g_meas_noise, void* stream) {
     if (B <= 0 || N < 1 || N > tt_max_horizon() || Np < 1 || k < 0) return -EINVAL;
-    hipLaunchKernelGGL(sim_window_vjp_kernel, dim3(grid_for((long long)B * (N + 1))), dim3(kThreads), 0,
-                       (hipStream_t)stream, B, N, k, Np, g_xref, g_uref, g_plan_x, g_plan_u, g_x0, grad_state, adj_state,
-                       g_wq_wr, g_wq_wr_acc, g_meas_noise);
-    return launched("sim_window_vjp_kernel");
+    return launch_flat(sim_window_vjp_kernel, "sim_window_vjp_kernel", (long long)B * (N + 1), stream, B, N, k, Np,
+                       g_xref, g_uref, g_plan_x, g_plan_u, g_x0, grad_state, adj_state, g_wq_wr, g_wq_wr_acc,
+                       g_meas_noise);
 }
 
 }  // extern "C"

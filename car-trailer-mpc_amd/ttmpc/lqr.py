@@ -17,8 +17,8 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import TTError, TTLqrVjpOut, lib
-from .simulation import plant
+from ._lib import TTLqrVjpOut, lib
+from .simulation import _check, _ptr, _stream, plant
 
 
 def lqr_scores(x_cur, x_goal, params, Q, R, u_goal=None, stream=None):
@@ -35,13 +35,10 @@ def lqr_scores(x_cur, x_goal, params, Q, R, u_goal=None, stream=None):
     q = np.ascontiguousarray(np.asarray(Q, dtype=np.float64).reshape(36))
     r = np.ascontiguousarray(np.asarray(R, dtype=np.float64).reshape(4))
     dp = C.POINTER(C.c_double)
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
     p = plant(params)
-    rc = lib().tt_lqr_score_device(B, C.byref(p), q.ctypes.data_as(dp), r.ctypes.data_as(dp), xc.data_ptr(),
-                                   xg.data_ptr(), None, P.data_ptr(), score.data_ptr(), it.data_ptr(),
-                                   C.c_void_p(s.cuda_stream))
-    if rc != 0:
-        raise TTError(f"tt_lqr_score_device failed ({rc})")
+    _check(lib().tt_lqr_score_device(B, C.byref(p), q.ctypes.data_as(dp), r.ctypes.data_as(dp), xc.data_ptr(),
+                                     xg.data_ptr(), None, P.data_ptr(), score.data_ptr(), it.data_ptr(),
+                                     _stream(stream, dev)), "tt_lqr_score_device")
     return score, P, it
 
 
@@ -93,14 +90,10 @@ def lqr_scores_vjp(x_cur, x_goal, params, R, P, grad_score=None, grad_P=None, fw
            "doublings": torch.empty(B, dtype=torch.int32, device=dev)}
     o = TTLqrVjpOut(*[out[k].data_ptr() or None for k in ("g_x_cur", "g_x_goal", "g_Q", "g_R", "vjp_status",
                                                          "doublings")])
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
     p = plant(params)
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    rc = lib().tt_lqr_score_vjp_device(B, C.byref(p), r.ctypes.data_as(C.POINTER(C.c_double)), xc.data_ptr(),
-                                       xg.data_ptr(), Pm.data_ptr(), ptr(fwd_iters), ptr(gs), ptr(gP), C.byref(o),
-                                       C.c_void_p(s.cuda_stream))
-    if rc != 0:
-        raise TTError(f"tt_lqr_score_vjp_device failed ({rc})")
+    _check(lib().tt_lqr_score_vjp_device(B, C.byref(p), r.ctypes.data_as(C.POINTER(C.c_double)), xc.data_ptr(),
+                                         xg.data_ptr(), Pm.data_ptr(), _ptr(fwd_iters), _ptr(gs), _ptr(gP), C.byref(o),
+                                         _stream(stream, dev)), "tt_lqr_score_vjp_device")
     return out
 
 

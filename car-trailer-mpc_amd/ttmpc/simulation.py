@@ -69,8 +69,22 @@ def _check(rc, what):
         raise TTError(f"{what} failed ({rc})")
 
 
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
 def _dev(a, dev, dtype=torch.float64):
     return torch.as_tensor(np.ascontiguousarray(a) if not torch.is_tensor(a) else a, dtype=dtype).to(dev).contiguous()
+
+
+def _run_noise(noise, K, B, dev):
+    """A whole run's noise draws (host or device, or None) as a (steps, B, 6) float64 tensor on the device."""
+    if noise is None:
+        return None
+    nz = _dev(noise.detach() if isinstance(noise, torch.Tensor) else noise, dev)
+    if tuple(nz.shape) != (K, B, 6):
+        raise ValueError(f"noise must have shape (steps, B, 6) = {(K, B, 6)}, got {tuple(nz.shape)}")
+    return nz
 
 
 # ---------------------------------------------------------------- single-kernel device entry points
@@ -87,9 +101,8 @@ def window(plan_x, plan_u, k, N, state=None, noise=None, x_meas=None, xref=None,
     per = int(plan_x.shape[0] != 1)
     if per and plan_x.shape[0] != B:
         raise ValueError("per-instance plans need one plan per instance")
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     _check(lib().tt_sim_window_device(B, int(N), int(k), int(Np), plan_x.data_ptr(), plan_u.data_ptr(), per,
-                                      ptr(state), ptr(noise), ptr(x_meas), xref.data_ptr(), uref.data_ptr(),
+                                      _ptr(state), _ptr(noise), _ptr(x_meas), xref.data_ptr(), uref.data_ptr(),
                                       _stream(stream, dev)), "tt_sim_window_device")
     return x_meas, xref, uref
 
@@ -122,10 +135,8 @@ def plant_update(state, u, params, disturbance_params=None, status=None, zero_on
     if state_noise is not None and (state_noise.shape != state.shape or not state_noise.is_contiguous()):
         raise ValueError("state_noise must be a contiguous (B, 6) tensor")
     _check(lib().tt_plant_update_noise_device(state.shape[0], C.byref(p), state.data_ptr(), u.data_ptr(), stride,
-                                              None if status is None else status.data_ptr(), int(bool(zero_on_fail)),
-                                              None if state_noise is None else state_noise.data_ptr(),
-                                              None if u_applied is None else u_applied.data_ptr(), _stream(stream, dev)),
-           "tt_plant_update_noise_device")
+                                              _ptr(status), int(bool(zero_on_fail)), _ptr(state_noise), _ptr(u_applied),
+                                              _stream(stream, dev)), "tt_plant_update_noise_device")
     return state
 
 
@@ -166,12 +177,11 @@ def policy_plant_vjp(state, status, active_after, consecutive, adj_state, adj_u_
     if policy not in POLICIES:
         raise ValueError(f"policy must be one of {sorted(POLICIES)}")
     p = plant(params, disturbance_params)
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     _check(lib().tt_policy_plant_vjp_device(state.shape[0], grad_u.shape[1], C.byref(p), POLICIES[policy],
-                                            state.data_ptr(), status.data_ptr(), ptr(active_before),
-                                            active_after.data_ptr(), consecutive.data_ptr(), ptr(grad_u_applied),
+                                            state.data_ptr(), status.data_ptr(), _ptr(active_before),
+                                            active_after.data_ptr(), consecutive.data_ptr(), _ptr(grad_u_applied),
                                             adj_state.data_ptr(), adj_u_last.data_ptr(), grad_u.data_ptr(),
-                                            ptr(g_state_noise), _stream(stream, dev)), "tt_policy_plant_vjp_device")
+                                            _ptr(g_state_noise), _stream(stream, dev)), "tt_policy_plant_vjp_device")
     return adj_state, adj_u_last, grad_u
 
 
@@ -187,10 +197,9 @@ def window_vjp(g_xref, g_uref, k, Np, g_plan_x=None, g_plan_u=None, shared=False
     z = lambda *sh: torch.zeros(sh, dtype=torch.float64, device=dev)  # noqa: E731
     g_plan_x = z(B, Np + 1, 6) if g_plan_x is None else g_plan_x
     g_plan_u = z(B, Np, 2) if g_plan_u is None else g_plan_u
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     _check(lib().tt_sim_window_vjp_device(B, N, int(k), int(Np), g_xref.data_ptr(), g_uref.data_ptr(),
-                                          g_plan_x.data_ptr(), g_plan_u.data_ptr(), ptr(g_x0), ptr(grad_state),
-                                          ptr(adj_state), ptr(g_wq_wr), ptr(g_wq_wr_acc), ptr(g_meas_noise),
+                                          g_plan_x.data_ptr(), g_plan_u.data_ptr(), _ptr(g_x0), _ptr(grad_state),
+                                          _ptr(adj_state), _ptr(g_wq_wr), _ptr(g_wq_wr_acc), _ptr(g_meas_noise),
                                           _stream(stream, dev)), "tt_sim_window_vjp_device")
     if shared:
         with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
@@ -199,15 +208,49 @@ def window_vjp(g_xref, g_uref, k, Np, g_plan_x=None, g_plan_u=None, shared=False
 
 
 class LoopTape:
-    """What ``ClosedLoop.run_tape`` keeps on the device for ``ClosedLoop.backward``: the step indices ks, the logs S
-    (K+1,B,6), Ua (K,B,2), status / active / consec (K,B) (active and the consecutive-failure count after each step),
-    each step's solve X (K,B,N+1,6), U (K,B,N,2), dual (K,B,N+1,22), the noise it used (K,B,6) or None, the weights
-    wq_wr (B,8) or None, and the plan the run saw."""
-    __slots__ = ("ks", "S", "Ua", "status", "active", "consec", "X", "U", "dual", "noise", "wq_wr", "plan_x", "plan_u")
+    """The device log of an eager run.  Every recorded run has the step indices ks and the logs S (K+1,B,6), Ua
+    (K,B,2), status / iters / collide / active (K,B) (active: after each step).  ``ClosedLoop.run_tape`` also keeps
+    what ``ClosedLoop.backward`` needs, None in a plain ``run``: consec (K,B), the consecutive-failure count after each
+    step, each step's solve X (K,B,N+1,6), U (K,B,N,2), dual (K,B,N+1,22) and the noise it used (K,B,6) or None.
+    wq_wr (B,8) or None are the run's weights, plan_x / plan_u the plan it saw."""
+    __slots__ = ("ks", "S", "Ua", "status", "iters", "collide", "active", "consec", "X", "U", "dual", "noise", "wq_wr",
+                 "plan_x", "plan_u")
+    # (log field, the loop's buffer a step leaves it in), in the order record() copies them; the solve writes dual
+    STEP = (("S", "state"), ("Ua", "u_applied"), ("status", "st"), ("iters", "it"), ("collide", "flag"),
+            ("active", "active"), ("consec", "consec"), ("X", "X"), ("U", "U"))
 
     def __init__(self, **kw):
         for k in self.__slots__:
             setattr(self, k, kw.get(k))
+
+    @classmethod
+    def alloc(cls, loop, ks, record=True, taped=False, **kw):
+        """The log of a run of ``loop`` over the steps ks: the logs if record, the backward's fields too if taped."""
+        K, B, N = len(ks), loop.B, loop.N
+        new = lambda *sh, dtype=torch.float64: torch.empty(sh, dtype=dtype, device=loop.dev)  # noqa: E731
+        log = cls(ks=list(ks), plan_x=loop.plan_x, plan_u=loop.plan_u, **kw)
+        if record:
+            log.S, log.Ua = new(K + 1, B, 6), new(K, B, 2)
+            log.status, log.iters, log.collide, log.active = (new(K, B, dtype=torch.int32) for _ in range(4))
+        if taped:
+            log.consec = new(K, B, dtype=torch.int32)
+            log.X, log.U, log.dual = new(K, B, N + 1, 6), new(K, B, N, 2), new(K, B, N + 1, 22)
+        return log
+
+    def record(self, j, loop):
+        """Copy what step j left in the loop's buffers into every allocated field, on the current stream."""
+        for name, src in self.STEP:
+            dst = getattr(self, name)
+            if dst is not None:
+                dst[j + 1 if name == "S" else j].copy_(getattr(loop, src))
+
+    def result(self):
+        """The logs as the numpy dict ``run`` returns (after a synchronisation)."""
+        st, act = self.status.cpu().numpy(), self.active.cpu().numpy()
+        stop = np.where((act == 0).any(axis=0), (act == 0).argmax(axis=0), -1)
+        return dict(k=np.array(self.ks), states=self.S.cpu().numpy(), controls=self.Ua.cpu().numpy(), status=st,
+                    iters=self.iters.cpu().numpy(), collide=self.collide.cpu().numpy().astype(bool),
+                    success=st <= TT_ACCEPTABLE, active=act.astype(bool), stop_step=stop)
 
     def nbytes(self):
         return sum(t.numel() * t.element_size() for t in (getattr(self, k) for k in self.__slots__)
@@ -325,50 +368,69 @@ class ClosedLoop:
         noise, or with noise_in_plant -- the default of the "nmpc" / "fuzzy" policies -- the plant's process noise
         before its dt factor).  dual (B,N+1,22): also export the solve's multipliers (run_tape; the solve is bitwise
         the plain one); wq_wr (B,8): per-instance weights of a solver that is not TT_VARIANT_FUZZY."""
+        s, N = self.stream, self.N
+        if noise is not None:
+            self._check_noise(noise, (self.B, 6))
+        with torch.cuda.stream(s):
+            if noise is None and self._noisy:
+                noise = self._draw()
+            meas = noise if self.measurement_noise else None
+            self._enqueue_step(lambda: window(self.plan_x, self.plan_u, k, N, self.state, meas, self.x_meas, self.xref,
+                                              self.uref, stream=s),
+                               self.first, noise if self.noise_in_plant else None, dual, wq_wr)
+        self.first = False
+
+    @property
+    def _noisy(self):
+        """Whether a run without given noise draws its own."""
+        return (self.measurement_noise or self.noise_in_plant) and self.dist is not None
+
+    def _draw(self, *steps, out=None):
+        """process_noise_std * N(0, 1) of shape (*steps, B, 6) from the loop's generator, on the current stream; copied
+        to ``out`` before the scaling if given."""
+        nz = torch.randn((*steps, self.B, 6), generator=self.gen, dtype=torch.float64, device=self.dev)
+        if out is not None:
+            nz = out.copy_(nz)
+        return nz.mul_(float(self.dist.get("process_noise_std", 0.0)))
+
+    def _enqueue_step(self, enqueue_window, first, plant_noise, dual=None, wq_wr=None):
+        """The one statement of a closed-loop step, enqueued on the loop's stream (the caller has made it current):
+        enqueue_window() -> collision check (first: of the first window, else of the previous prediction) -> [warm
+        start] -> [fuzzy weights] -> solve [-> fuzzy retry] [-> switch solve] -> [record] -> policy + plant.
+        plant_noise: the plant's process noise (B,6), None, or a callable that enqueues its selection on the device
+        right before the plant and returns it (the replayed step).  dual, wq_wr: as ``step`` takes them."""
         L, s, B, N = lib(), self.stream, self.B, self.N
         sp = C.c_void_p(s.cuda_stream)
-        if noise is not None:
-            self._check_noise(noise, (B, 6))
-        with torch.cuda.stream(s):
-            if (self.measurement_noise or self.noise_in_plant) and noise is None and self.dist is not None:
-                noise = torch.randn((B, 6), generator=self.gen, dtype=torch.float64, device=self.dev)
-                noise.mul_(float(self.dist.get("process_noise_std", 0.0)))
-            window(self.plan_x, self.plan_u, k, N, self.state, noise if self.measurement_noise else None,
-                   self.x_meas, self.xref, self.uref, stream=s)
-            if self.check_collision:
-                collision_flags(self.xref if self.first else self.X, self.obstacles, self.params, self.flag, stream=s)
-            zg = 0
-            if self.warm:
-                _check(L.tt_warm_start_device(B, N, self.last.data_ptr(), self.have.data_ptr(), self.xref.data_ptr(),
-                                              self.uref.data_ptr(), int(self.bug_compatible), self.zg.data_ptr(), sp),
-                       "tt_warm_start_device")
-                zg = self.zg.data_ptr()
-            wq = 0
-            if self.fuzzy:
-                _check(L.tt_fuzzy_weights_device(B, N, self.x_meas.data_ptr(), self.xref.data_ptr(), self.wq.data_ptr(),
-                                                 sp), "tt_fuzzy_weights_device")
-                wq = self.wq.data_ptr()
-            elif wq_wr is not None:
-                wq = wq_wr.data_ptr()
-            if dual is None:
-                self.solver.solve_device(B, self.x_meas.data_ptr(), self.xref.data_ptr(), self.uref.data_ptr(),
-                                         self.X.data_ptr(), self.U.data_ptr(), self.st.data_ptr(), self.it.data_ptr(),
-                                         self.kkt.data_ptr(), wq_wr=wq, z_guess=zg, stream=s.cuda_stream)
-            else:
-                self.solver.solve_ex_device(B, self.x_meas.data_ptr(), self.xref.data_ptr(), self.uref.data_ptr(),
-                                            self.X.data_ptr(), self.U.data_ptr(), self.st.data_ptr(),
-                                            self.it.data_ptr(), self.kkt.data_ptr(), wq_wr=wq, z_guess=zg,
-                                            dual=dual.data_ptr(), stream=s.cuda_stream)
-            if self.fuzzy:
-                self._fuzzy_retry(s)
-            if self.switch is not None and self.check_collision:
-                self._switch_solve(s)
-            if self.warm:
-                _check(L.tt_record_solution_device(B, N, self.X.data_ptr(), self.U.data_ptr(), self.st.data_ptr(),
-                                                   self.last.data_ptr(), self.have.data_ptr(), sp),
-                       "tt_record_solution_device")
-            self._policy_plant(sp, noise if self.noise_in_plant else None)
-        self.first = False
+        enqueue_window()
+        if self.check_collision:
+            collision_flags(self.xref if first else self.X, self.obstacles, self.params, self.flag, stream=s)
+        zg = 0
+        if self.warm:
+            _check(L.tt_warm_start_device(B, N, self.last.data_ptr(), self.have.data_ptr(), self.xref.data_ptr(),
+                                          self.uref.data_ptr(), int(self.bug_compatible), self.zg.data_ptr(), sp),
+                   "tt_warm_start_device")
+            zg = self.zg.data_ptr()
+        wq = 0
+        if self.fuzzy:
+            _check(L.tt_fuzzy_weights_device(B, N, self.x_meas.data_ptr(), self.xref.data_ptr(), self.wq.data_ptr(),
+                                             sp), "tt_fuzzy_weights_device")
+            wq = self.wq.data_ptr()
+        elif wq_wr is not None:
+            wq = wq_wr.data_ptr()
+        io = [t.data_ptr() for t in (self.x_meas, self.xref, self.uref, self.X, self.U, self.st, self.it, self.kkt)]
+        if dual is None:
+            self.solver.solve_device(B, *io, wq_wr=wq, z_guess=zg, stream=s.cuda_stream)
+        else:
+            self.solver.solve_ex_device(B, *io, wq_wr=wq, z_guess=zg, dual=dual.data_ptr(), stream=s.cuda_stream)
+        if self.fuzzy:
+            self._fuzzy_retry(s)
+        if self.switch is not None and self.check_collision:
+            self._switch_solve(s)
+        if self.warm:
+            _check(L.tt_record_solution_device(B, N, self.X.data_ptr(), self.U.data_ptr(), self.st.data_ptr(),
+                                               self.last.data_ptr(), self.have.data_ptr(), sp),
+                   "tt_record_solution_device")
+        self._policy_plant(sp, plant_noise() if callable(plant_noise) else plant_noise)
 
     def _policy_plant(self, sp, state_noise=None):
         p = plant(self.params, self.dist)
@@ -387,57 +449,53 @@ class ClosedLoop:
     def _fuzzy_retry(self, s):
         """mpc_control_fuzzy.py:145-159: failed instances re-solve once with unit weights, same guess."""
         idx = torch.nonzero((self.st > TT_ACCEPTABLE) & (self.active != 0), as_tuple=True)[0]
-        n = int(idx.numel())          # host sync: the compaction size decides the retry launch
+
+        def solve(n, *io):
+            w = torch.ones((n, 8), dtype=torch.float64, device=self.dev)
+            zg = self.zg[idx].contiguous() if self.warm else None
+            self.solver.solve_device(n, *io, wq_wr=w.data_ptr(), z_guess=0 if zg is None else zg.data_ptr(),
+                                     stream=s.cuda_stream)
+        self._resolve(idx, solve)
+
+    def _switch_solve(self, s):
+        """USE_SWITCH_MPC: instances whose check collided use MPCTrackingControlObs (simulation.py:506-512)."""
+        self._resolve(torch.nonzero(self.flag, as_tuple=True)[0],
+                      lambda n, x0, xr, ur, X, U, st, it, kk: self.switch.solve_device(
+                          n, x0, 0, xr, ur, 0, X, U, 0, st, it, kk, stream=s.cuda_stream))
+
+    def _resolve(self, idx, solve):
+        """Solve the instances idx again as a compacted batch and put the results in their places: gathers x_meas,
+        xref, uref, calls solve(n, x0, xref, uref, X, U, status, iters, kkt) with device pointers of n-instance buffers
+        (it launches on the loop's stream, which is current), scatters the five outputs back."""
+        n = int(idx.numel())          # host sync: the compaction size decides the launch
         if n == 0:
             return
         N = self.N
+        new = lambda *sh, dtype=torch.float64: torch.empty(sh, dtype=dtype, device=self.dev)  # noqa: E731
         x0, xr, ur = self.x_meas[idx].contiguous(), self.xref[idx].contiguous(), self.uref[idx].contiguous()
-        w = torch.ones((n, 8), dtype=torch.float64, device=self.dev)
-        zg = self.zg[idx].contiguous() if self.warm else None
-        X = torch.empty((n, N + 1, 6), dtype=torch.float64, device=self.dev)
-        U = torch.empty((n, N, 2), dtype=torch.float64, device=self.dev)
-        st = torch.empty(n, dtype=torch.int32, device=self.dev)
-        it = torch.empty(n, dtype=torch.int32, device=self.dev)
-        kk = torch.empty(n, dtype=torch.float64, device=self.dev)
-        self.solver.solve_device(n, x0.data_ptr(), xr.data_ptr(), ur.data_ptr(), X.data_ptr(), U.data_ptr(),
-                                 st.data_ptr(), it.data_ptr(), kk.data_ptr(), wq_wr=w.data_ptr(),
-                                 z_guess=0 if zg is None else zg.data_ptr(), stream=s.cuda_stream)
+        X, U, st, it, kk = new(n, N + 1, 6), new(n, N, 2), new(n, dtype=torch.int32), new(n, dtype=torch.int32), new(n)
+        solve(n, *(t.data_ptr() for t in (x0, xr, ur, X, U, st, it, kk)))
         self.X[idx], self.U[idx], self.st[idx], self.it[idx], self.kkt[idx] = X, U, st, it, kk
 
     # ---------------- hipGraph replay of the closed loop ----------------
     def _graph_step(self, first, d_ks, d_step, noise_all, logs):
-        """Enqueue one closed-loop step whose step index lives on the device (replayable)."""
-        L, s, B, N = lib(), self.stream, self.B, self.N
+        """Enqueue one closed-loop step whose step index lives on the device (replayable): the step at k = d_ks[*d_step]
+        with the noise noise_all[*d_step], its logs written at *d_step, then *d_step += 1."""
+        L, s, B = lib(), self.stream, self.B
         sp = C.c_void_p(s.cuda_stream)
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        Np = self.plan_u.shape[-2]
-        per = int(self.plan_x.shape[0] != 1)
         meas_all = None if self.noise_in_plant else noise_all
-        _check(L.tt_sim_window_indexed_device(B, N, d_ks.data_ptr(), d_step.data_ptr(), int(Np),
-                                              self.plan_x.data_ptr(), self.plan_u.data_ptr(), per,
-                                              self.state.data_ptr(), ptr(meas_all), self.x_meas.data_ptr(),
-                                              self.xref.data_ptr(), self.uref.data_ptr(), sp),
-               "tt_sim_window_indexed_device")
-        if self.check_collision:
-            collision_flags(self.xref if first else self.X, self.obstacles, self.params, self.flag, stream=s)
-        zg = 0
-        if self.warm:
-            _check(L.tt_warm_start_device(B, N, self.last.data_ptr(), self.have.data_ptr(), self.xref.data_ptr(),
-                                          self.uref.data_ptr(), int(self.bug_compatible), self.zg.data_ptr(), sp),
-                   "tt_warm_start_device")
-            zg = self.zg.data_ptr()
-        self.solver.solve_device(B, self.x_meas.data_ptr(), self.xref.data_ptr(), self.uref.data_ptr(),
-                                 self.X.data_ptr(), self.U.data_ptr(), self.st.data_ptr(), self.it.data_ptr(),
-                                 self.kkt.data_ptr(), z_guess=zg, stream=s.cuda_stream)
-        if self.warm:
-            _check(L.tt_record_solution_device(B, N, self.X.data_ptr(), self.U.data_ptr(), self.st.data_ptr(),
-                                               self.last.data_ptr(), self.have.data_ptr(), sp),
-                   "tt_record_solution_device")
-        sn = None
-        if self.noise_in_plant and noise_all is not None:  # this step's process noise, selected on the device
-            sn = self._sn_buf
-            sn.copy_(torch.index_select(noise_all, 0, d_step.long()).view(B, 6))
-        self._policy_plant(sp, sn)
+
+        def enqueue_window():
+            _check(L.tt_sim_window_indexed_device(B, self.N, d_ks.data_ptr(), d_step.data_ptr(),
+                                                  int(self.plan_u.shape[-2]), self.plan_x.data_ptr(),
+                                                  self.plan_u.data_ptr(), int(self.plan_x.shape[0] != 1),
+                                                  self.state.data_ptr(), _ptr(meas_all), self.x_meas.data_ptr(),
+                                                  self.xref.data_ptr(), self.uref.data_ptr(), sp),
+                   "tt_sim_window_indexed_device")
+
+        def select():   # this step's process noise, selected on the device
+            return self._sn_buf.copy_(torch.index_select(noise_all, 0, d_step.long()).view(B, 6))
+        self._enqueue_step(enqueue_window, first, select if self.noise_in_plant and noise_all is not None else None)
         S, Ua, Ss, Si, Sc = logs
         _check(L.tt_sim_log_advance_device(B, d_step.data_ptr(), self.state.data_ptr(), self.u_applied.data_ptr(),
                                            self.st.data_ptr(), self.it.data_ptr(),
@@ -461,15 +519,8 @@ class ClosedLoop:
         d_step = torch.zeros(1, dtype=torch.int32, device=d)
         noise_all = None
         self._sn_buf = torch.empty((B, 6), dtype=torch.float64, device=d)
-        if (self.measurement_noise or self.noise_in_plant) and self.dist is not None:
-            if noise is None:
-                noise_all = torch.randn((K, B, 6), generator=self.gen, dtype=torch.float64, device=d)
-                noise_all.mul_(float(self.dist.get("process_noise_std", 0.0)))
-            else:
-                arr = noise if isinstance(noise, torch.Tensor) else np.asarray(noise, dtype=np.float64)
-                if tuple(arr.shape) != (K, B, 6):
-                    raise ValueError(f"noise must have shape (steps, B, 6) = {(K, B, 6)}, got {tuple(arr.shape)}")
-                noise_all = _dev(arr, d)
+        if self._noisy:   # one (K, B, 6) draw for the whole run: not the numbers of run()'s K draws of (B, 6)
+            noise_all = self._draw(K) if noise is None else _run_noise(noise, K, B, d)
         logs = (torch.empty((K + 1, B, 6), dtype=torch.float64, device=d),
                 torch.empty((K, B, 2), dtype=torch.float64, device=d),
                 torch.zeros((K, B), dtype=torch.int32, device=d), torch.zeros((K, B), dtype=torch.int32, device=d),
@@ -491,61 +542,53 @@ class ClosedLoop:
         return dict(self._policy_logs(), k=np.array(ks), states=S, controls=Ua, status=Ss, iters=Si,
                     collide=Sc.astype(bool), success=Ss <= TT_ACCEPTABLE)
 
-    def _switch_solve(self, s):
-        """USE_SWITCH_MPC: instances whose check collided use MPCTrackingControlObs (simulation.py:506-512)."""
-        idx = torch.nonzero(self.flag, as_tuple=True)[0]
-        n = int(idx.numel())          # host sync: the compaction size decides the OBCA launch
-        if n == 0:
-            return
-        o, N = self.switch, self.N
-        x0, xr, ur = self.x_meas[idx].contiguous(), self.xref[idx].contiguous(), self.uref[idx].contiguous()
-        X = torch.empty((n, N + 1, 6), dtype=torch.float64, device=self.dev)
-        U = torch.empty((n, N, 2), dtype=torch.float64, device=self.dev)
-        st = torch.empty(n, dtype=torch.int32, device=self.dev)
-        it = torch.empty(n, dtype=torch.int32, device=self.dev)
-        kk = torch.empty(n, dtype=torch.float64, device=self.dev)
-        o.solve_device(n, x0.data_ptr(), 0, xr.data_ptr(), ur.data_ptr(), 0, X.data_ptr(), U.data_ptr(), 0,
-                       st.data_ptr(), it.data_ptr(), kk.data_ptr(), stream=s.cuda_stream)
-        self.X[idx], self.U[idx], self.st[idx], self.it[idx], self.kkt[idx] = X, U, st, it, kk
+    # ---------------- eager runs: plain and taped, one log ----------------
+    def _begin(self, x_init, T_sim, noise=None, wq_wr=None, record=True, taped=False):
+        """reset() and the log of an eager run to T_sim: -> (log, whether the run draws its noise step by step into
+        log.noise).  noise (steps, B, 6) and wq_wr (B, 8): host or device, checked and moved to the device."""
+        ks = step_indices(T_sim, float(self.params["dt"]))
+        if isinstance(x_init, torch.Tensor):
+            x_init = x_init.detach().cpu().numpy()
+        self.reset(x_init)
+        B, K, d = self.B, len(ks), self.dev
+        w = None if wq_wr is None else _dev(wq_wr.detach() if isinstance(wq_wr, torch.Tensor) else wq_wr, d)
+        if w is not None and tuple(w.shape) != (B, 8):
+            raise ValueError(f"wq_wr must have shape (B, 8) = {(B, 8)}, got {tuple(w.shape)}")
+        nz = _run_noise(noise, K, B, d)
+        drawn = taped and nz is None and self._noisy
+        if drawn:
+            nz = torch.empty((K, B, 6), dtype=torch.float64, device=d)
+        log = LoopTape.alloc(self, ks, record, taped, noise=nz, wq_wr=w)
+        if record:
+            log.S[0].copy_(self.state)
+        # noise and weights may just have been converted on the current stream; the steps read them on self.stream
+        self.stream.wait_stream(torch.cuda.current_stream(d))
+        return log, drawn
+
+    def _steps(self, log, drawn=False):
+        """Enqueue the steps of an eager run on the loop's stream (no host synchronisation): step(), with the multiplier
+        export if the log is a tape, then the step's copies into the log."""
+        for j, k in enumerate(log.ks):
+            noise = None if log.noise is None else log.noise[j]
+            if drawn:   # the draw step() would make, kept
+                with torch.cuda.stream(self.stream):
+                    self._draw(out=noise)
+            self.step(k, noise, dual=None if log.dual is None else log.dual[j], wq_wr=log.wq_wr)
+            if log.S is not None:
+                with torch.cuda.stream(self.stream):
+                    log.record(j, self)
 
     def run(self, x_init, T_sim, noise=None, record=True):
         """Run the reference's loop to T_sim.  noise: optional (steps, B, 6) measurement-noise draws (with
         noise_in_plant: the plant's process-noise draws).
         Returns numpy logs: states (steps+1,B,6), controls (steps,B,2) as applied, status / iters /
-        collide (steps,B), and the step indices k."""
-        ks = step_indices(T_sim, float(self.params["dt"]))
-        self.reset(x_init)
-        B, K = self.B, len(ks)
-        if record:
-            S = torch.empty((K + 1, B, 6), dtype=torch.float64, device=self.dev)
-            Ua = torch.empty((K, B, 2), dtype=torch.float64, device=self.dev)
-            Ss = torch.empty((K, B), dtype=torch.int32, device=self.dev)
-            Si = torch.empty((K, B), dtype=torch.int32, device=self.dev)
-            Sc = torch.empty((K, B), dtype=torch.int32, device=self.dev)
-            Sa = torch.empty((K, B), dtype=torch.int32, device=self.dev)
-            S[0].copy_(self.state)
-        nz = None if noise is None else _dev(noise, self.dev)
-        if nz is not None and tuple(nz.shape) != (K, B, 6):
-            raise ValueError(f"noise must have shape (steps, B, 6) = {(K, B, 6)}, got {tuple(nz.shape)}")
-        for j, k in enumerate(ks):
-            self.step(k, None if nz is None else nz[j])
-            if record:
-                with torch.cuda.stream(self.stream):
-                    S[j + 1].copy_(self.state)
-                    Ua[j].copy_(self.u_applied)
-                    Ss[j].copy_(self.st)
-                    Si[j].copy_(self.it)
-                    Sc[j].copy_(self.flag)
-                    Sa[j].copy_(self.active)
+        collide (steps,B), and the step indices k; with record=False only the final state and the policy logs."""
+        log, _ = self._begin(x_init, T_sim, noise, record=record)
+        self._steps(log)
         torch.cuda.synchronize(self.dev)
-        pol = self._policy_logs()
         if not record:
-            return dict(pol, k=np.array(ks), state=self.state.cpu().numpy())
-        act = Sa.cpu().numpy()
-        stop = np.where((act == 0).any(axis=0), (act == 0).argmax(axis=0), -1)
-        return dict(pol, k=np.array(ks), states=S.cpu().numpy(), controls=Ua.cpu().numpy(), status=Ss.cpu().numpy(),
-                    iters=Si.cpu().numpy(), collide=Sc.cpu().numpy().astype(bool),
-                    success=Ss.cpu().numpy() <= TT_ACCEPTABLE, active=act.astype(bool), stop_step=stop)
+            return dict(self._policy_logs(), k=np.array(log.ks), state=self.state.cpu().numpy())
+        return dict(self._policy_logs(), **log.result())
 
     # ---------------- reverse mode: taped run and backward sweep ----------------
     def _check_differentiable(self):
@@ -560,63 +603,11 @@ class ClosedLoop:
         (solve_ex_device: bitwise the plain solve) and each step's X, U, dual copied to a ``LoopTape`` on the device,
         (30 (N+1) - 2) * 8 bytes per instance and step.  wq_wr: constant per-instance weights (B,8), host or device.
         Returns run()'s dict plus "tape".  Solver variants TT_VARIANT_TRACK and TT_VARIANT_NMPC; no switch solver."""
-        tape, Si, Sc, drawn = self._tape_begin(x_init, T_sim, noise, wq_wr)
-        self._tape_steps(tape, Si, Sc, drawn)
-        torch.cuda.synchronize(self.dev)
-        act, Ss = tape.active.cpu().numpy(), tape.status.cpu().numpy()
-        stop = np.where((act == 0).any(axis=0), (act == 0).argmax(axis=0), -1)
-        return dict(self._policy_logs(), k=np.array(tape.ks), states=tape.S.cpu().numpy(),
-                    controls=tape.Ua.cpu().numpy(), status=Ss, iters=Si.cpu().numpy(),
-                    collide=Sc.cpu().numpy().astype(bool), success=Ss <= TT_ACCEPTABLE, active=act.astype(bool),
-                    stop_step=stop, tape=tape)
-
-    def _tape_begin(self, x_init, T_sim, noise=None, wq_wr=None):
-        """reset() and the tape of a run of T_sim: -> (tape, iteration log, collision log, whether the noise is drawn)."""
         self._check_differentiable()
-        ks = step_indices(T_sim, float(self.params["dt"]))
-        if isinstance(x_init, torch.Tensor):
-            x_init = x_init.detach().cpu().numpy()
-        self.reset(x_init)
-        B, K, N, d, f = self.B, len(ks), self.N, self.dev, torch.float64
-        new = lambda *sh, dtype=f: torch.empty(sh, dtype=dtype, device=d)  # noqa: E731
-        w = None if wq_wr is None else _dev(wq_wr.detach() if isinstance(wq_wr, torch.Tensor) else wq_wr, d)
-        if w is not None and tuple(w.shape) != (B, 8):
-            raise ValueError(f"wq_wr must have shape (B, 8) = {(B, 8)}, got {tuple(w.shape)}")
-        nz = None if noise is None else _dev(noise.detach() if isinstance(noise, torch.Tensor) else noise, d)
-        if nz is not None and tuple(nz.shape) != (K, B, 6):
-            raise ValueError(f"noise must have shape (steps, B, 6) = {(K, B, 6)}, got {tuple(nz.shape)}")
-        drawn = nz is None and (self.measurement_noise or self.noise_in_plant) and self.dist is not None
-        if drawn:
-            nz = new(K, B, 6)
-        tape = LoopTape(ks=list(ks), S=new(K + 1, B, 6), Ua=new(K, B, 2), status=new(K, B, dtype=torch.int32),
-                        active=new(K, B, dtype=torch.int32), consec=new(K, B, dtype=torch.int32),
-                        X=new(K, B, N + 1, 6), U=new(K, B, N, 2), dual=new(K, B, N + 1, 22), noise=nz, wq_wr=w,
-                        plan_x=self.plan_x, plan_u=self.plan_u)
-        Si, Sc = new(K, B, dtype=torch.int32), new(K, B, dtype=torch.int32)
-        tape.S[0].copy_(self.state)
-        self.stream.wait_stream(torch.cuda.current_stream(d))
-        return tape, Si, Sc, drawn
-
-    def _tape_steps(self, tape, Si, Sc, drawn=False):
-        """Enqueue the K steps of a taped run on the loop's stream (no host synchronisation): step() with the multiplier
-        export, then the step's logs and its X, U copied to the tape."""
-        B, d, f, nz = self.B, self.dev, torch.float64, tape.noise
-        for j, k in enumerate(tape.ks):
-            if drawn:   # the draw step() would make, kept
-                with torch.cuda.stream(self.stream):
-                    nz[j].copy_(torch.randn((B, 6), generator=self.gen, dtype=f, device=d))
-                    nz[j].mul_(float(self.dist.get("process_noise_std", 0.0)))
-            self.step(k, None if nz is None else nz[j], dual=tape.dual[j], wq_wr=tape.wq_wr)
-            with torch.cuda.stream(self.stream):
-                tape.S[j + 1].copy_(self.state)
-                tape.Ua[j].copy_(self.u_applied)
-                tape.status[j].copy_(self.st)
-                Si[j].copy_(self.it)
-                Sc[j].copy_(self.flag)
-                tape.active[j].copy_(self.active)
-                tape.consec[j].copy_(self.consec)
-                tape.X[j].copy_(self.X)
-                tape.U[j].copy_(self.U)
+        tape, drawn = self._begin(x_init, T_sim, noise, wq_wr, taped=True)
+        self._steps(tape, drawn)
+        torch.cuda.synchronize(self.dev)
+        return dict(self._policy_logs(), **tape.result(), tape=tape)
 
     def backward(self, tape, GS, GU):
         """The adjoint of a taped run for a scalar loss L(S, Ua): GS = dL/dS (K+1,B,6), GU = dL/dUa (K,B,2), float64
@@ -627,10 +618,9 @@ class ClosedLoop:
         (shaped as the loop's plan: summed over B for a shared one), g_noise (K,B,6): of the measurement noise, or with
         noise_in_plant of the plant's process noise; zeros where the run had no noise)."""
         self._check_differentiable()
-        L, s, d, N = lib(), self.stream, self.dev, self.N
+        s, d, N = self.stream, self.dev, self.N
         K, B = tape.status.shape
         Np = tape.plan_u.shape[-2]
-        per = int(tape.plan_x.shape[0] != 1)
         for name, t, shape in (("GS", GS, (K + 1, B, 6)), ("GU", GU, (K, B, 2))):
             if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.device == d and
                     tuple(t.shape) == shape):
@@ -643,8 +633,10 @@ class ClosedLoop:
         g_x0, g_xr, g_ur, g_ws = z(B, 6), z(B, N + 1, 6), z(B, N, 2), z(B, 8)
         in_plant = self.noise_in_plant and tape.noise is not None
         meas = self.measurement_noise and tape.noise is not None
-        p = plant(self.params, self.dist)
-        sp = C.c_void_p(s.cuda_stream)
+        # the raw entries, not the module-level wrappers: a backward step is four short launches the host only just
+        # keeps ahead of, and the wrappers' per-call tt_plant and stream lookups cost it about 1 %
+        L, p, sp = lib(), plant(self.params, self.dist), C.c_void_p(s.cuda_stream)
+        per = int(tape.plan_x.shape[0] != 1)
         wq = 0 if tape.wq_wr is None else tape.wq_wr.data_ptr()
         s.wait_stream(torch.cuda.current_stream(d))
         for t in range(K - 1, -1, -1):

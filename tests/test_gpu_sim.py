@@ -68,6 +68,44 @@ def test_window_kernel_per_instance_plans(plan):
         assert np.array_equal(xr.cpu().numpy()[b], Xr.T) and np.array_equal(ur.cpu().numpy()[b], Ur.T)
 
 
+@pytest.mark.parametrize("per_instance", [False, True])
+def test_indexed_window_equals_plain_window(plan, per_instance):
+    """tt_sim_window_indexed_device (k = ks[*step] and the noise row noise_all[*step], both resolved on the device) is
+    sim.window at that k with that row, bit for bit, at every edge of the end padding; the step index sits at each
+    position of ks in turn, the non-zero ones included."""
+    import ctypes as C
+    from ttmpc import lib
+    from ttmpc import simulation as sim
+    S, U = plan
+    N, Np = 20, U.shape[1]
+    ks = (0, 17, Np - N, Np - N + 3, Np - 1, Np, Np + 9)
+    K = len(ks)
+    if per_instance:
+        B = 3
+        shift = np.arange(B)[:, None, None] * 1.5
+        px, pu = _t(S.T[None] + shift), _t(U.T[None] * (1 + shift[:, :, :2]))
+    else:
+        B = 5
+        px, pu = _t(S.T[None]), _t(U.T[None])
+    rng = np.random.default_rng(7)
+    state, noise_all = _t(rng.normal(size=(B, 6))), _t(rng.normal(scale=0.02, size=(K, B, 6)))
+    d_ks = _t(np.array(ks), torch.int32)
+    s0 = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    for step in range(K):
+        d_step = _t(np.array([step]), torch.int32)
+        xm, xr, ur = (torch.full(sh, float("nan"), dtype=torch.float64, device="cuda")
+                      for sh in ((B, 6), (B, N + 1, 6), (B, N, 2)))
+        assert lib().tt_sim_window_indexed_device(B, N, d_ks.data_ptr(), d_step.data_ptr(), Np, px.data_ptr(),
+                                                  pu.data_ptr(), int(per_instance), state.data_ptr(),
+                                                  noise_all.data_ptr(), xm.data_ptr(), xr.data_ptr(), ur.data_ptr(),
+                                                  s0) == 0
+        em, er, eu = sim.window(px, pu, ks[step], N, state, noise_all[step])
+        torch.cuda.synchronize()
+        for got, exp in ((xm, em), (xr, er), (ur, eu)):
+            assert np.array_equal(got.cpu().numpy(), exp.cpu().numpy()), (step, ks[step])
+        assert np.array_equal(xm.cpu().numpy(), (state + noise_all[step]).cpu().numpy())
+
+
 def test_collision_kernel_reproduces_reference_outputs(golden_ref):
     """simulation.check_state_collision executed by the reference on 256 poses (make_golden.py)."""
     from ttmpc import simulation as sim
@@ -289,6 +327,26 @@ def test_graph_replay_equals_eager_loop(plan, golden_ref, warm):
     graph = sim.ClosedLoop(mk(), S, U, P, sim.DISTURBANCE_PARAMS, **kw).run_graph(x0, T, noise=noise)
     for key in ("states", "controls", "status", "iters", "collide"):
         assert np.array_equal(eager[key], graph[key]), key
+
+
+def test_unrecorded_run_ends_where_the_recorded_one_does(plan, golden_ref):
+    """run(record=False) makes the steps of run() without the log: the same final state, byte for byte, and the same
+    policy logs."""
+    import ttmpc
+    from oracle import ttmpc_oracle as to
+    from ttmpc import simulation as sim
+    S, U = plan
+    N, B, T = 20, 6, 0.5
+    rng = np.random.default_rng(13)
+    x0 = S[:, 0][None] + rng.normal(scale=[0.3, 0.3, 0.02, 0.02, 0.0, 0.0], size=(B, 6))
+    noise = rng.normal(scale=0.002, size=(len(to.step_indices(T, 0.05)), B, 6))
+    mk = lambda: sim.ClosedLoop(  # noqa: E731
+        ttmpc.BatchSolver(N, P, to.DEFAULT_Q, to.DEFAULT_R, to.MPC_XLB, to.MPC_XUB, to.MPC_ULB, to.MPC_UUB), S, U, P,
+        sim.DISTURBANCE_PARAMS, obstacles=golden_ref["obstacles"])
+    full, last = mk().run(x0, T, noise=noise), mk().run(x0, T, noise=noise, record=False)
+    assert "states" not in last and np.array_equal(last["k"], full["k"])
+    assert last["state"].tobytes() == full["states"][-1].tobytes()
+    assert np.array_equal(last["failures"], full["failures"]) and np.array_equal(last["running"], full["running"])
 
 
 def _oracle_solver_cfg(N, tol, acc_tol, max_iter, acc_iter):

@@ -61,40 +61,25 @@ def main():
         e1.synchronize()
         return 1e3 * e0.elapsed_time(e1) / K, out
 
-    def taped():
-        tape, Si, Sc, drawn = cl._tape_begin(x0, T, noise, w)
-        us, _ = timed(cl.stream, lambda: cl._tape_steps(tape, Si, Sc, drawn))
-        return us, tape
-
-    def plain():
-        """run()'s loop body (step + its six log copies) without run()'s host copies at the end."""
-        cl.reset(x0)
-        f, i = torch.float64, torch.int32
-        logs = [torch.empty((K + 1, B, 6), dtype=f, device=dev), torch.empty((K, B, 2), dtype=f, device=dev)] + \
-               [torch.empty((K, B), dtype=i, device=dev) for _ in range(4)]
-        cl.stream.wait_stream(torch.cuda.current_stream(dev))
-
-        def steps():
-            for j, k in enumerate(sim.step_indices(T, params["dt"])):
-                cl.step(k, noise[j], wq_wr=w)
-                with torch.cuda.stream(cl.stream):
-                    for dst, src in zip(logs, (cl.state, cl.u_applied, cl.st, cl.it, cl.flag, cl.active)):
-                        dst[j + 1 if dst is logs[0] else j].copy_(src)
-        return timed(cl.stream, steps)[0]
+    def forward(taped):
+        """run_tape()'s / run()'s steps (step + the nine / six log copies) without the host copies at the end."""
+        log, drawn = cl._begin(x0, T, noise, w, taped=taped)
+        us, _ = timed(cl.stream, lambda: cl._steps(log, drawn))
+        return us, log
 
     def backward(tape):
         return timed(torch.cuda.current_stream(dev), lambda: cl.backward(tape, GS, GU))
 
-    _, tape = taped()
-    plain()
+    _, tape = forward(True)
+    forward(False)
     _, grads = backward(tape)
     torch.cuda.synchronize()
     ok = int((tape.status <= 1).sum())
     times = {"taped forward step": [], "plain forward step": [], "backward step": []}
     for _ in range(args.rounds):
-        us, tape = taped()
+        us, tape = forward(True)
         times["taped forward step"].append(us)
-        times["plain forward step"].append(plain())
+        times["plain forward step"].append(forward(False)[0])
         times["backward step"].append(backward(tape)[0])
     assert bool(torch.isfinite(grads["g_x_init"]).all())
     print(f"B = {B}, N = {N}, K = {K} ({ok} of {K * B} solves succeeded), {args.rounds} rounds, us per step; tape "
