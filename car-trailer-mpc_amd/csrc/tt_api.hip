@@ -157,6 +157,11 @@ class Stager {
     void out(T* host, size_t count, T** dev, bool device_only = false) {
         add(nullptr, host, count * sizeof(T), host != nullptr || device_only, (void**)dev);
     }
+    // an accumulator: copied to the device and back if the host has it
+    template <class T>
+    void inout(T* host, size_t count, T** dev) {
+        add(host, host, count * sizeof(T), host != nullptr, (void**)dev);
+    }
     bool carve(DevBuf& buf) {
         if (!buf.ensure(total_)) return false;
         for (int t = 0; t < n_; ++t)
@@ -600,9 +605,10 @@ int tt_track_sens_device(void* handle, int B, const double* d_x, const double* d
     return sens_launch(h, B, d_x, d_u, d_dual, d_wq_wr, d_status, x, stream);
 }
 
-int tt_track_vjp_device(void* handle, int B, const double* d_x, const double* d_u, const double* d_dual,
-                        const double* d_xref, const double* d_uref, const double* d_wq_wr, const int* d_status,
-                        const double* d_grad_x, const double* d_grad_u, const tt_track_vjp_out* d_out, void* stream) {
+int tt_track_vjp_model_device(void* handle, int B, const double* d_x, const double* d_u, const double* d_dual,
+                              const double* d_xref, const double* d_uref, const double* d_wq_wr, const int* d_status,
+                              const double* d_grad_x, const double* d_grad_u, const tt_track_vjp_model_out* d_out,
+                              int accumulate, void* stream) {
     Handle* h = static_cast<Handle*>(handle);
     if (const int rc = prelude(h, B, kHandle | kTrackOnly | kSign)) return rc;
     if (!d_grad_x && !d_grad_u) return fail(h, -EINVAL, "grad_x and grad_u are both NULL: no loss to differentiate%s");
@@ -613,7 +619,7 @@ int tt_track_vjp_device(void* handle, int B, const double* d_x, const double* d_
     if (const int rc = prelude(h, B, kFuzzy, d_wq_wr)) return rc;
     DeviceGuard dg(h->device);
     if (dg.err != hipSuccess) return hip_fail(h, dg.err, "hipSetDevice");
-    ttmpc::VjpArgs a = diff_args<ttmpc::VjpArgs>(h, B, d_x, d_u, d_dual, d_wq_wr, d_status);
+    ttmpc::VjpModelArgs a = diff_args<ttmpc::VjpModelArgs>(h, B, d_x, d_u, d_dual, d_wq_wr, d_status);
     a.xref = d_xref;
     a.uref = d_uref;
     a.gx = d_grad_x;
@@ -623,14 +629,30 @@ int tt_track_vjp_device(void* handle, int B, const double* d_x, const double* d_
     a.g_uref = d_out->g_uref;
     a.g_wqwr = d_out->g_wq_wr;
     a.vjp_status = d_out->vjp_status;
-    const hipError_t e = ttmpc::launch_track_vjp(a, static_cast<hipStream_t>(stream));
+    a.g_model = d_out->g_model;
+    a.accumulate = accumulate != 0;
+    // without g_model the plain instantiation, on the VjpArgs head of the same block
+    const hipError_t e = a.g_model ? ttmpc::launch_track_vjp_model(a, static_cast<hipStream_t>(stream))
+                                   : ttmpc::launch_track_vjp(a, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail(h, e, "adjoint kernel launch");
     return 0;
 }
 
-int tt_track_vjp(void* handle, int B, const double* x, const double* u, const double* dual, const double* xref,
-                 const double* uref, const double* wq_wr, const int* status, const double* grad_x,
-                 const double* grad_u, const tt_track_vjp_out* out) {
+int tt_track_vjp_device(void* handle, int B, const double* d_x, const double* d_u, const double* d_dual,
+                        const double* d_xref, const double* d_uref, const double* d_wq_wr, const int* d_status,
+                        const double* d_grad_x, const double* d_grad_u, const tt_track_vjp_out* d_out, void* stream) {
+    if (!d_out)
+        return tt_track_vjp_model_device(handle, B, d_x, d_u, d_dual, d_xref, d_uref, d_wq_wr, d_status, d_grad_x,
+                                         d_grad_u, nullptr, 0, stream);
+    const tt_track_vjp_model_out o = {d_out->g_x0, d_out->g_xref, d_out->g_uref, d_out->g_wq_wr, nullptr,
+                                      d_out->vjp_status};
+    return tt_track_vjp_model_device(handle, B, d_x, d_u, d_dual, d_xref, d_uref, d_wq_wr, d_status, d_grad_x,
+                                     d_grad_u, &o, 0, stream);
+}
+
+int tt_track_vjp_model(void* handle, int B, const double* x, const double* u, const double* dual, const double* xref,
+                       const double* uref, const double* wq_wr, const int* status, const double* grad_x,
+                       const double* grad_u, const tt_track_vjp_model_out* out, int accumulate) {
     Handle* h = static_cast<Handle*>(handle);
     if (const int rc = prelude(h, B, kHandle | kTrackOnly | kSign)) return rc;
     if (!grad_x && !grad_u) return fail(h, -EINVAL, "grad_x and grad_u are both NULL: no loss to differentiate%s");
@@ -642,7 +664,7 @@ int tt_track_vjp(void* handle, int B, const double* x, const double* u, const do
     Stager st;
     const double *d_x, *d_u, *d_dual, *d_xref, *d_uref, *d_w, *d_gx, *d_gu;
     const int* d_st;
-    tt_track_vjp_out dout;
+    tt_track_vjp_model_out dout;
     st.in(x, nx, &d_x);
     st.in(u, nu, &d_u);
     st.in(dual, b * (N + 1) * ttmpc::kDualPerStage, &d_dual);
@@ -657,6 +679,10 @@ int tt_track_vjp(void* handle, int B, const double* x, const double* u, const do
     st.out(out->g_uref, nu, &dout.g_uref);
     st.out(out->g_wq_wr, b * 8, &dout.g_wq_wr);
     st.out(out->vjp_status, b, &dout.vjp_status);
+    if (accumulate)
+        st.inout(out->g_model, b * 3, &dout.g_model);
+    else
+        st.out(out->g_model, b * 3, &dout.g_model);
     if (!st.carve(h->xfer)) return no_memory(h, "adjoint staging");
     hipStream_t s = h->stream;
     st.upload(s);
@@ -664,7 +690,8 @@ int tt_track_vjp(void* handle, int B, const double* x, const double* u, const do
         (void)hipStreamSynchronize(s);
         return hip_fail(h, st.err, "H2D copy");
     }
-    const int rc = tt_track_vjp_device(handle, B, d_x, d_u, d_dual, d_xref, d_uref, d_w, d_st, d_gx, d_gu, &dout, s);
+    const int rc = tt_track_vjp_model_device(handle, B, d_x, d_u, d_dual, d_xref, d_uref, d_w, d_st, d_gx, d_gu, &dout,
+                                             accumulate, s);
     if (rc) {
         (void)hipStreamSynchronize(s);
         return rc;
@@ -673,6 +700,38 @@ int tt_track_vjp(void* handle, int B, const double* x, const double* u, const do
     const hipError_t es = hipStreamSynchronize(s);
     const hipError_t e = st.err != hipSuccess ? st.err : es;
     if (e != hipSuccess) return hip_fail(h, e, "adjoint");
+    return 0;
+}
+
+int tt_track_vjp(void* handle, int B, const double* x, const double* u, const double* dual, const double* xref,
+                 const double* uref, const double* wq_wr, const int* status, const double* grad_x,
+                 const double* grad_u, const tt_track_vjp_out* out) {
+    if (!out)
+        return tt_track_vjp_model(handle, B, x, u, dual, xref, uref, wq_wr, status, grad_x, grad_u, nullptr, 0);
+    const tt_track_vjp_model_out o = {out->g_x0, out->g_xref, out->g_uref, out->g_wq_wr, nullptr, out->vjp_status};
+    return tt_track_vjp_model(handle, B, x, u, dual, xref, uref, wq_wr, status, grad_x, grad_u, &o, 0);
+}
+
+int tt_set_model(void* handle, double L1, double L2, double Mh) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (!h) return fail(nullptr, -EINVAL, "NULL handle%s");
+    if (is_obca(h->cfg))
+        return fail(h, -EINVAL, "the geometry of an OBCA handle also enters its H-representations: create a new handle%s");
+    if (!(L1 > 0) || !(L2 > 0) || !isfinite(L1) || !isfinite(L2) || !isfinite(Mh))
+        return fail(h, -EINVAL, "params L1, L2 must be > 0 and M finite%s");
+    // every launch path fills its kernel arguments from cfg (fill_model): nothing on the device holds the old values
+    h->cfg.L1 = L1;
+    h->cfg.L2 = L2;
+    h->cfg.Mh = Mh;
+    return 0;
+}
+
+int tt_get_model(void* handle, double* L1, double* L2, double* Mh) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (!h) return fail(nullptr, -EINVAL, "NULL handle%s");
+    if (L1) *L1 = h->cfg.L1;
+    if (L2) *L2 = h->cfg.L2;
+    if (Mh) *Mh = h->cfg.Mh;
     return 0;
 }
 

@@ -106,6 +106,13 @@ struct VjpArgs : DiffArgs {
 constexpr int kVjpStage = 33, kVjpTiles = 164;
 inline int vjp_lds_doubles(int N) { return kVjpStage * (N + 1) + 12 * N + kVjpTiles; }
 hipError_t launch_track_vjp(const VjpArgs& a, hipStream_t stream);
+// the same adjoint plus dL/d(L1, L2, Mh): the kernel's model instantiation (the same LDS record).  The two members
+// sit behind VjpArgs so that the plain instantiation's argument block, and with it its code, stays what it was
+struct VjpModelArgs : VjpArgs {
+    double* g_model;      // [B][3], never nullptr here
+    int accumulate;       // != 0: g_model[b] += (a failed instance adds nothing); 0: g_model[b] = (zeros if failed)
+};
+hipError_t launch_track_vjp_model(const VjpModelArgs& a, hipStream_t stream);
 
 }  // namespace ttmpc
 

@@ -65,13 +65,37 @@ __device__ __forceinline__ void plant_vjp(const tt_plant& p, const double* q, do
     a[5] = a[5] + g_v * dt;
 }
 
+// a' dS_{t+1}/d(L1, L2, Mh) of plant_apply at the pre-update state q, a taken before the J_q product: only rows 2 and 3
+// of the Euler step depend on the geometry, dt slip (a_2 df_2/dtheta + a_3 df_3/dtheta) with the forward's slip factor;
+// the lateral-slip and friction terms do not.
+__device__ __forceinline__ void plant_model_vjp(const tt_plant& p, const double* q, const double* a, double* gm) {
+#pragma clang fp contract(off)
+    const double ps = q[3], ph = q[4], v = q[5];
+    const double cps = cos(ps), sps = sin(ps), tph = tan(ph);
+    const double hk = 1 + p.Mh / p.L2 * cps;
+    const double f2 = v * tph / p.L1;
+    double slip = 1.0;
+    if (p.enable) slip = 1.0 - fmin(fabs(ph) * fabs(v) * p.slip_angle_max, 0.3);
+    const double f2_L1 = -(f2 / p.L1);
+    const double f3_L1 = f2 * hk / p.L1;
+    const double f3_L2 = f2 * (p.Mh / p.L2 * cps) / p.L2 + v * sps / p.L2 / p.L2;
+    const double f3_Mh = -f2 * (cps / p.L2);
+    const double s = p.dt * slip;
+    gm[0] = s * (a[2] * f2_L1 + a[3] * f3_L1);
+    gm[1] = s * (a[3] * f3_L2);
+    gm[2] = s * (a[3] * f3_Mh);
+}
+
 // The branch of policy_plant_kernel an instance took is read from the logs: active before / after the step, the
 // step's status and the consecutive-failure count after the step (include/ttmpc.h has the table).
-__global__ void __launch_bounds__(kThreads) policy_plant_vjp_kernel(
-    int B, int N, tt_plant p, int policy, const double* __restrict__ state, const int* __restrict__ status,
+// kModel: also g_model_acc [B][3] += a' dS_{t+1}/d(L1, L2, Mh) for every instance that moved; the plain instantiation
+// behind policy_plant_vjp_kernel is the kernel as it was.
+template <bool kModel>
+__device__ __forceinline__ void policy_plant_vjp_body(
+    int B, int N, const tt_plant& p, int policy, const double* __restrict__ state, const int* __restrict__ status,
     const int* __restrict__ act_before, const int* __restrict__ act_after, const int* __restrict__ consec,
     const double* __restrict__ grad_ua, double* __restrict__ adj, double* __restrict__ adj_last,
-    double* __restrict__ grad_u, double* __restrict__ g_noise) {
+    double* __restrict__ grad_u, double* __restrict__ g_noise, double* __restrict__ g_model_acc) {
 #pragma clang fp contract(off)
     const int b = blockIdx.x * kThreads + threadIdx.x;
     if (b >= B) return;
@@ -95,6 +119,12 @@ __global__ void __launch_bounds__(kThreads) policy_plant_vjp_kernel(
     if (g_noise)
 #pragma unroll
         for (int i = 0; i < 6; ++i) g_noise[(size_t)b * 6 + i] = p.dt * a[i];
+    if constexpr (kModel) {
+        double gm[3];
+        plant_model_vjp(p, q, a, gm);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) g_model_acc[(size_t)b * 3 + i] += gm[i];
+    }
     plant_vjp(p, q, a, c);
     if (grad_ua) {
         c[0] = c[0] + grad_ua[(size_t)b * 2];
@@ -123,6 +153,24 @@ __global__ void __launch_bounds__(kThreads) policy_plant_vjp_kernel(
     adj_last[(size_t)b * 2 + 1] = l1;
 #pragma unroll
     for (int i = 0; i < 6; ++i) adj[(size_t)b * 6 + i] = a[i];
+}
+
+__global__ void __launch_bounds__(kThreads) policy_plant_vjp_kernel(
+    int B, int N, tt_plant p, int policy, const double* __restrict__ state, const int* __restrict__ status,
+    const int* __restrict__ act_before, const int* __restrict__ act_after, const int* __restrict__ consec,
+    const double* __restrict__ grad_ua, double* __restrict__ adj, double* __restrict__ adj_last,
+    double* __restrict__ grad_u, double* __restrict__ g_noise) {
+    policy_plant_vjp_body<false>(B, N, p, policy, state, status, act_before, act_after, consec, grad_ua, adj, adj_last,
+                                 grad_u, g_noise, nullptr);
+}
+
+__global__ void __launch_bounds__(kThreads) policy_plant_vjp_model_kernel(
+    int B, int N, tt_plant p, int policy, const double* __restrict__ state, const int* __restrict__ status,
+    const int* __restrict__ act_before, const int* __restrict__ act_after, const int* __restrict__ consec,
+    const double* __restrict__ grad_ua, double* __restrict__ adj, double* __restrict__ adj_last,
+    double* __restrict__ grad_u, double* __restrict__ g_noise, double* __restrict__ g_model_acc) {
+    policy_plant_vjp_body<true>(B, N, p, policy, state, status, act_before, act_after, consec, grad_ua, adj, adj_last,
+                                grad_u, g_noise, g_model_acc);
 }
 
 // Adjoint of sim_window_kernel, one thread per (instance, window row j).  State row j went to plan row min(k+j, Np),
@@ -205,6 +253,22 @@ int tt_policy_plant_vjp_device(int B, int N, const tt_plant* p, int policy, cons
     return launch_flat(policy_plant_vjp_kernel, "policy_plant_vjp_kernel", B, stream, B, N, *p, policy, state, status,
                        active_before, active_after, consecutive, grad_u_applied, adj_state, adj_u_last, grad_u,
                        g_state_noise);
+}
+
+int tt_policy_plant_vjp_model_device(int B, int N, const tt_plant* p, int policy, const double* state,
+                                     const int* status, const int* active_before, const int* active_after,
+                                     const int* consecutive, const double* grad_u_applied, double* adj_state,
+                                     double* adj_u_last, double* grad_u, double* g_state_noise, double* g_model_acc,
+                                     void* stream) {
+    if (!g_model_acc)
+        return tt_policy_plant_vjp_device(B, N, p, policy, state, status, active_before, active_after, consecutive,
+                                          grad_u_applied, adj_state, adj_u_last, grad_u, g_state_noise, stream);
+    if (B <= 0 || N < 1 || N > tt_max_horizon() || !p || !state || !status || !active_after || !consecutive ||
+        !adj_state || !adj_u_last || !grad_u || policy < TT_POLICY_TRACK || policy > TT_POLICY_FUZZY)
+        return -EINVAL;
+    return launch_flat(policy_plant_vjp_model_kernel, "policy_plant_vjp_model_kernel", B, stream, B, N, *p, policy,
+                       state, status, active_before, active_after, consecutive, grad_u_applied, adj_state, adj_u_last,
+                       grad_u, g_state_noise, g_model_acc);
 }
 
 int tt_sim_window_vjp_device(int B, int N, int k, int Np, const double* g_xref, const double* g_uref, double* g_plan_x,

@@ -18,6 +18,13 @@
 // LDS: lx_k | lu_k overlay Sigma_k (dead once the backward sweep is through) and kappa_k overlays gU_k (dead once
 // kappa_k is formed), so a stage costs the sensitivity record plus g: 61.3 KB at the horizon limit, below the 64 KB a
 // launch gets without asking.  Plain IEEE arithmetic, no contraction: tests/vjp_reference.py is the numpy model.
+//
+// The model instantiation (tt_track_vjp_model_device, kModel) adds the gradient in the geometry theta = (L1, L2, Mh).
+// Only the dynamics rows and the -A_k' y_{k+1} part of the stationarity rows depend on theta:
+//   dL/dtheta = dt sum_{k<N} [ lx_k' (dJ_f(x_k)/dtheta)' y_{k+1} + ly_{k+1}' df(x_k, u_k)/dtheta ]
+// and lam_y comes from the x-rows of K, one more six-lane sweep (model_gradient below): ly_N = gX_N - H_N lx_N,
+// ly_k = gX_k - H_k lx_k + A_k' ly_{k+1}, H_k = W_k + Sigma_x,k.  ly overlays gX, so the LDS record is the same; the
+// plain instantiation's code is what it was.  tests/model_vjp_reference.py is the numpy model.
 #include <math.h>
 
 #include "tt_kernel.hpp"
@@ -59,12 +66,116 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
-__global__ __launch_bounds__(W) void track_vjp_kernel(VjpArgs a) {
+// g_model of an instance that gives no gradient: zeros, or with `accumulate` the accumulator as it is
+__device__ __forceinline__ void zero_model(const VjpModelArgs& a, int b, int lane) {
+    if (!a.accumulate && lane < 3) a.g_model[(size_t)b * 3 + lane] = 0.0;
+}
+
+// Sigma_x,k entry v (< 6) again, with linearise_stage's own expressions: lam_x | lam_u have overwritten the record's
+__device__ __forceinline__ double sigma_x(const DiffArgs& a, double val, const double* dk, int v) {
+    double sg = 0.0;
+    const double l = a.xlb[v], ub = a.xub[v];
+    if (isfinite(l) && l > -1e19) sg += dk[6 + v] / (val - (l - 1e-8 * fmax(1.0, fabs(l))));
+    if (isfinite(ub) && ub < 1e19) sg += dk[14 + v] / ((ub + 1e-8 * fmax(1.0, fabs(ub))) - val);
+    return sg;
+}
+
+// The model instantiation's three phases, behind the forward sweep (the record holds lam_x | lam_u in the Sigma slots,
+// gX in sG .. sG + 5, dt*J and the curvature untouched; T[tQW ..] = 2 Q_w):
+//   1. stage-parallel: r_k = gX_k - H_k lam_x,k over gX_k,  H_k = 2 Q_w + curvature_k (k < N) + Sigma_x,k
+//   2. serial, six lanes, one barrier per stage: lam_y,k = r_k + A_k' lam_y,k+1 in place, k = N - 1 .. 0
+//   3. stage-parallel: lane k < N forms lam_x,k' (dJ_f/dtheta)' y_{k+1} + lam_y,k+1' df/dtheta for theta = L1, L2, Mh;
+//      three butterflies, every lane leaves with dt * sum in m[]
+__device__ __forceinline__ void model_gradient(const DiffArgs& a, double* stg, const double* T, const double* x,
+                                               const double* dl, int lane, bool& bad, double* m) {
+    const int N = a.N;
+    for (int k = lane; k <= N; k += W) {
+        double* r = stg + k * kStage;
+        const double* xk = x + k * 6;
+        const double* dk = dl + k * kDualPerStage;
+        double lx[6], h[6];
+        for (int l = 0; l < 6; ++l) lx[l] = r[sSG + l];
+        for (int i = 0; i < 6; ++i) {
+            double s = 0.0;
+            for (int l = 0; l < 6; ++l) s += T[tQW + i * 6 + l] * lx[l];
+            if (k < N)
+                for (int l = 0; l < 6; ++l) {
+                    const int wi = sens::w_idx(i, l);
+                    if (wi >= 0) s += r[sens::sWC + wi] * lx[l];
+                }
+            h[i] = s + sigma_x(a, xk[i], dk, i) * lx[i];
+        }
+        for (int i = 0; i < 6; ++i) {
+            const double v = r[sG + i] - h[i];
+            bad |= !isfinite(v);
+            r[sG + i] = v;
+        }
+    }
+    __syncthreads();
+    for (int k = N - 1; k >= 0; --k) {
+        double* r = stg + k * kStage;
+        if (lane < 6) {
+            const double* ln = r + kStage + sG;  // lam_y,k+1
+            double s = ln[lane];
+            for (int l = 0; l < 6; ++l) {
+                const int di = d_idx(l, lane);
+                if (di >= 0) s += r[sAJ + di] * ln[l];
+            }
+            s = r[sG + lane] + s;
+            bad |= !isfinite(s);
+            r[sG + lane] = s;
+        }
+        __syncthreads();
+    }
+    const double iL1 = 1.0 / a.L1, iL2 = 1.0 / a.L2, iL1L2 = iL1 * iL2, Mh = a.Mh;
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int k = lane; k < N; k += W) {
+        const double* r = stg + k * kStage;
+        const double* xk = x + k * 6;
+        const double* y = dl + (k + 1) * kDualPerStage;  // y_{k+1}
+        const double* ly = r + kStage + sG;               // lam_y,k+1
+        const double lx3 = r[sSG + 3], lx4 = r[sSG + 4], lx5 = r[sSG + 5];
+        double sps, cps, sph, cph;
+        sincos(xk[3], &sps, &cps);
+        sincos(xk[4], &sph, &cph);
+        const double v = xk[5], ic = 1.0 / cph, t = sph * ic, c2 = ic * ic;
+        const double kk = 1.0 + Mh * iL2 * cps;
+        // rows 2 and 3 of f and the entries (2,4) (2,5) (3,3) (3,4) (3,5) of J_f, differentiated
+        const double y2 = y[2], y3 = y[3], l2 = ly[2], l3 = ly[3];
+        const double a24 = v * c2 * iL1, a25 = t * iL1, vt = v * t * iL1;
+        acc[0] += y2 * (-(a24 * iL1) * lx4 + -(a25 * iL1) * lx5)
+                + y3 * (-(vt * Mh * sps * iL1L2) * lx3 + (a24 * kk * iL1) * lx4 + (a25 * kk * iL1) * lx5)
+                + (l2 * -(vt * iL1) + l3 * (vt * kk * iL1));
+        const double mc = Mh * cps * iL2 * iL2, s2 = sps * iL2 * iL2;
+        acc[1] += y3 * ((v * cps * iL2 * iL2 - vt * Mh * sps * iL2 * iL2) * lx3 + (a24 * mc) * lx4 + (a25 * mc + s2) * lx5)
+                + l3 * (vt * mc + v * s2);
+        acc[2] += y3 * ((vt * sps * iL2) * lx3 + -(a24 * cps * iL2) * lx4 + -(a25 * cps * iL2) * lx5)
+                + l3 * -(vt * cps * iL2);
+    }
+    for (int t = 0; t < 3; ++t) {
+        m[t] = a.dt * wave_sum(acc[t]);
+        bad |= !isfinite(m[t]);
+    }
+}
+
+template <bool kModel>
+struct KernelArgs {
+    using type = VjpArgs;
+};
+template <>
+struct KernelArgs<true> {
+    using type = VjpModelArgs;
+};
+
+// kModel: also dL/d(L1, L2, Mh) into a.g_model (VjpModelArgs); the plain instantiation is the kernel as it was
+template <bool kModel>
+__global__ __launch_bounds__(W) void track_vjp_kernel(typename KernelArgs<kModel>::type a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int b = blockIdx.x, lane = threadIdx.x;
     const int N = a.N, S = N + 1;
     if (a.status[b] > 1) {  // > TT_ACCEPTABLE: no optimum to differentiate
         zero_outputs(a, b, lane);
+        if constexpr (kModel) zero_model(a, b, lane);
         if (a.vjp_status && lane == 0) a.vjp_status[b] = 2;
         return;
     }
@@ -127,9 +238,13 @@ __global__ __launch_bounds__(W) void track_vjp_kernel(VjpArgs a) {
     }
     if (__ballot(bad) != 0ull) {
         zero_outputs(a, b, lane);
+        if constexpr (kModel) zero_model(a, b, lane);
         if (a.vjp_status && lane == 0) a.vjp_status[b] = 1;
         return;
     }
+    // ---- model geometry: lam_y over gX, then the stage sums (p_0 stays in T, lam_x | lam_u in the records) ----
+    double gm[3] = {0.0, 0.0, 0.0};
+    if constexpr (kModel) model_gradient(a, stg, T, x, dl, lane, bad, gm);
     // ---- outputs ----
     if (a.g_x0 && ro.pl) a.g_x0[(size_t)b * 6 + ro.pi] = T[pc + ro.pi];
     const double* xr = a.xref ? a.xref + (size_t)b * S * 6 : nullptr;
@@ -207,6 +322,15 @@ __global__ __launch_bounds__(W) void track_vjp_kernel(VjpArgs a) {
         __syncthreads();  // the zeros below go behind the stores above
         zero_outputs(a, b, lane);
     }
+    if constexpr (kModel) {  // one writer per instance: lanes 0 .. 2 of its only wavefront
+        if (late) {
+            zero_model(a, b, lane);
+        } else if (lane < 3) {
+            double* g = a.g_model + (size_t)b * 3 + lane;
+            const double v = lane == 0 ? gm[0] : lane == 1 ? gm[1] : gm[2];
+            *g = a.accumulate ? *g + v : v;
+        }
+    }
     if (a.vjp_status && lane == 0) a.vjp_status[b] = late ? 1 : 0;
 }
 
@@ -215,7 +339,14 @@ __global__ __launch_bounds__(W) void track_vjp_kernel(VjpArgs a) {
 hipError_t launch_track_vjp(const VjpArgs& a, hipStream_t stream) {
     const int bytes = 8 * vjp_lds_doubles(a.N);
     if (bytes > 64 * 1024) return hipErrorInvalidValue;  // (the tracking horizon limit keeps it below 62 KB)
-    hipLaunchKernelGGL(track_vjp_kernel, dim3(a.B), dim3(W), bytes, stream, a);
+    hipLaunchKernelGGL(track_vjp_kernel<false>, dim3(a.B), dim3(W), bytes, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_track_vjp_model(const VjpModelArgs& a, hipStream_t stream) {
+    const int bytes = 8 * vjp_lds_doubles(a.N);  // the same record: lam_y overlays gX
+    if (bytes > 64 * 1024 || !a.g_model) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(track_vjp_kernel<true>, dim3(a.B), dim3(W), bytes, stream, a);
     return hipGetLastError();
 }
 

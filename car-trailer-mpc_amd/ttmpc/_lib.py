@@ -51,6 +51,12 @@ class TTTrackVjpOut(C.Structure):
                 ("vjp_status", C.c_void_p)]
 
 
+class TTTrackVjpModelOut(C.Structure):
+    """tt_track_vjp_model_out (include/ttmpc.h): tt_track_vjp_out with g_model [B][3] before vjp_status."""
+    _fields_ = [("g_x0", C.c_void_p), ("g_xref", C.c_void_p), ("g_uref", C.c_void_p), ("g_wq_wr", C.c_void_p),
+                ("g_model", C.c_void_p), ("vjp_status", C.c_void_p)]
+
+
 class TTLqrVjpOut(C.Structure):
     """tt_lqr_vjp_out (include/ttmpc.h): the outputs of tt_lqr_score_vjp_device; NULL members are skipped."""
     _fields_ = [("g_x_cur", C.c_void_p), ("g_x_goal", C.c_void_p), ("g_Q", C.c_void_p), ("g_R", C.c_void_p),
@@ -69,6 +75,20 @@ class TrackVjpResult:
     def __init__(self, **kw):
         for k in self.__slots__:
             setattr(self, k, kw.get(k))
+
+
+class TrackVjpModelResult(TrackVjpResult):
+    """What ``BatchSolver.vjp(..., model=True)`` returns: a ``TrackVjpResult`` with g_model (B,3) = dL/d(L1, L2, M) per
+    instance, also read as ``r["model"]``."""
+    __slots__ = ("g_model",)
+
+    def __init__(self, **kw):
+        for k in TrackVjpResult.__slots__ + TrackVjpModelResult.__slots__:
+            setattr(self, k, kw.get(k))
+
+    def __getitem__(self, key):
+        return getattr(self, {"model": "g_model", "x0": "g_x0", "xref": "g_xref", "uref": "g_uref", "w": "g_wq_wr",
+                              "vjp_status": "vjp_status"}[key])
 
 
 class TrackExResult:
@@ -137,6 +157,17 @@ def lib():
         L.tt_track_vjp.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp,
                                    C.POINTER(TTTrackVjpOut)]
         L.tt_track_vjp.restype = C.c_int
+    if not os.environ.get("TTMPC_LIB") or hasattr(L, "tt_track_vjp_model_device"):  # (A/B against a build without them)
+        L.tt_track_vjp_model_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 9 + [
+            C.POINTER(TTTrackVjpModelOut), C.c_int, C.c_void_p]
+        L.tt_track_vjp_model_device.restype = C.c_int
+        L.tt_track_vjp_model.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp,
+                                         C.POINTER(TTTrackVjpModelOut), C.c_int]
+        L.tt_track_vjp_model.restype = C.c_int
+        L.tt_set_model.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double]
+        L.tt_set_model.restype = C.c_int
+        L.tt_get_model.argtypes = [C.c_void_p, _dp, _dp, _dp]
+        L.tt_get_model.restype = C.c_int
     L.tt_plan_batch.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _ip]
     L.tt_plan_batch.restype = C.c_int
     L.tt_obca_solve_batch.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp]
@@ -180,6 +211,8 @@ def lib():
            "tt_policy_plant_noise_device": [i, C.POINTER(TTPlant), i, vp, vp, ll, vp, vp, vp, vp, vp, vp, vp, vp],
            "tt_fuzzy_weights_device": [i, i, vp, vp, vp, vp],
            "tt_policy_plant_vjp_device": [i, i, C.POINTER(TTPlant), i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+           "tt_policy_plant_vjp_model_device": [i, i, C.POINTER(TTPlant), i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                vp],
            "tt_sim_window_vjp_device": [i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
            "tt_lqr_score_vjp_device": [i, C.POINTER(TTPlant), _dp, vp, vp, vp, vp, vp, vp, C.POINTER(TTLqrVjpOut),
                                        vp]}
@@ -205,7 +238,8 @@ EXPORTED_SYMBOLS = ("tt_create", "tt_solve_batch", "tt_solve_batch_device", "tt_
                     "tt_fuzzy_weights_device", "tt_plant_update_noise_device", "tt_policy_plant_noise_device",
                     "tt_track_dual_len", "tt_solve_batch_ex", "tt_solve_batch_ex_device", "tt_track_sens_device",
                     "tt_track_vjp_device", "tt_track_vjp", "tt_policy_plant_vjp_device", "tt_sim_window_vjp_device",
-                    "tt_lqr_score_vjp_device")
+                    "tt_lqr_score_vjp_device", "tt_track_vjp_model_device", "tt_track_vjp_model", "tt_set_model",
+                    "tt_get_model", "tt_policy_plant_vjp_model_device")
 
 
 def _ptr(a):
@@ -403,22 +437,55 @@ class BatchSolver(_Solver):
         if rc != 0:
             self._err(rc, "tt_track_sens_device")
 
+    def set_model(self, L1=None, L2=None, M=None):
+        """tt_set_model: change the handle's geometry (a value left None keeps its current one).  Host-side state only:
+        every later call of this solver, host or device, runs with the new values, and a solve is bitwise that of a
+        fresh solver created with them.  Work already enqueued, and a captured graph, keep the old values.  Raises
+        TTError for L1 or L2 <= 0 or a non-finite value."""
+        cur = self.model()
+        L1, L2, M = (float(c if v is None else v) for v, c in zip((L1, L2, M), cur))
+        rc = self._L.tt_set_model(self._h, L1, L2, M)
+        if rc != 0:
+            self._err(rc, "tt_set_model")
+
+    def model(self):
+        """tt_get_model: the handle's current (L1, L2, M)."""
+        if os.environ.get("TTMPC_LIB") and not hasattr(self._L, "tt_get_model"):  # (A/B against a build without it)
+            return None
+        v = [C.c_double() for _ in range(3)]
+        rc = self._L.tt_get_model(self._h, *[C.byref(c) for c in v])
+        if rc != 0:
+            self._err(rc, "tt_get_model")
+        return tuple(c.value for c in v)
+
     def vjp_device(self, B, x, u, dual, xref, uref, status, grad_x=0, grad_u=0, g_x0=0, g_xref=0, g_uref=0, g_wq_wr=0,
-                   vjp_status=0, wq_wr=0, stream=0):
+                   vjp_status=0, wq_wr=0, stream=0, g_model=0, accumulate=False):
         """tt_track_vjp_device: the adjoint kernel on device arrays of an earlier ``solve_ex_device`` (its x, u, dual,
         status, and its inputs xref, uref, wq_wr) and the upstream gradients grad_x = dL/dX, grad_u = dL/dU (0 = zeros,
         not both).  Outputs (0 = not wanted): g_x0, g_xref, g_uref, g_wq_wr, vjp_status.  Uses no buffer of the handle:
-        any stream will do, behind the solve whose outputs it reads."""
+        any stream will do, behind the solve whose outputs it reads.  g_model (B,3): also dL/d(L1, L2, M) per instance
+        (tt_track_vjp_model_device), added to the buffer instead of written with ``accumulate``."""
+        if g_model:
+            mo = TTTrackVjpModelOut(g_x0 or None, g_xref or None, g_uref or None, g_wq_wr or None, g_model,
+                                    vjp_status or None)
+            rc = self._L.tt_track_vjp_model_device(self._h, int(B), x, u, dual, xref or None, uref or None,
+                                                   wq_wr or None, status, grad_x or None, grad_u or None, C.byref(mo),
+                                                   int(bool(accumulate)), stream or None)
+            if rc != 0:
+                self._err(rc, "tt_track_vjp_model_device")
+            return
         out = TTTrackVjpOut(g_x0 or None, g_xref or None, g_uref or None, g_wq_wr or None, vjp_status or None)
         rc = self._L.tt_track_vjp_device(self._h, int(B), x, u, dual, xref or None, uref or None, wq_wr or None, status,
                                          grad_x or None, grad_u or None, C.byref(out), stream or None)
         if rc != 0:
             self._err(rc, "tt_track_vjp_device")
 
-    def vjp(self, x, u, dual, xref, uref, status, grad_x, grad_u, wq_wr=None):
+    def vjp(self, x, u, dual, xref, uref, status, grad_x, grad_u, wq_wr=None, model=False):
         """Host arrays: the gradient of a scalar loss L(X, U) with respect to the inputs of the solve that returned
         x (B,N+1,6), u (B,N,2), dual (B,N+1,22) and status (B,) for xref, uref and wq_wr; grad_x (B,N+1,6) = dL/dX and
-        grad_u (B,N,2) = dL/dU (either may be None for zeros).  Returns a ``TrackVjpResult``."""
+        grad_u (B,N,2) = dL/dU (either may be None for zeros).  Returns a ``TrackVjpResult``; with ``model=True`` a
+        ``TrackVjpModelResult``, which also has g_model (B,3) = dL/d(L1, L2, M) per instance (``r["model"]``;
+        tt_track_vjp_model)."""
         N = self.N
         x = _f64(x)
         B = x.shape[0] if x.ndim == 3 else 1
@@ -431,8 +498,18 @@ class BatchSolver(_Solver):
         gx = None if grad_x is None else _f64(grad_x, (B, N + 1, 6))
         gu = None if grad_u is None else _f64(grad_u, (B, N, 2))
         w = None if wq_wr is None else _f64(wq_wr, (B, 8))
-        r = TrackVjpResult(g_x0=np.empty((B, 6)), g_xref=np.empty((B, N + 1, 6)), g_uref=np.empty((B, N, 2)),
-                           g_wq_wr=np.empty((B, 8)), vjp_status=np.empty(B, dtype=np.int32))
+        outs = dict(g_x0=np.empty((B, 6)), g_xref=np.empty((B, N + 1, 6)), g_uref=np.empty((B, N, 2)),
+                    g_wq_wr=np.empty((B, 8)), vjp_status=np.empty(B, dtype=np.int32))
+        if model:
+            r = TrackVjpModelResult(g_model=np.empty((B, 3)), **outs)
+            mo = TTTrackVjpModelOut(*[a.ctypes.data for a in (r.g_x0, r.g_xref, r.g_uref, r.g_wq_wr, r.g_model,
+                                                                r.vjp_status)])
+            rc = self._L.tt_track_vjp_model(self._h, B, _ptr(x), _ptr(u), _ptr(dual), _ptr(xref), _ptr(uref), _ptr(w),
+                                            st.ctypes.data_as(_ip), _ptr(gx), _ptr(gu), C.byref(mo), 0)
+            if rc != 0:
+                self._err(rc, "tt_track_vjp_model")
+            return r
+        r = TrackVjpResult(**outs)
         out = TTTrackVjpOut(*[a.ctypes.data for a in (r.g_x0, r.g_xref, r.g_uref, r.g_wq_wr, r.vjp_status)])
         rc = self._L.tt_track_vjp(self._h, B, _ptr(x), _ptr(u), _ptr(dual), _ptr(xref), _ptr(uref), _ptr(w),
                                   st.ctypes.data_as(_ip), _ptr(gx), _ptr(gu), C.byref(out))

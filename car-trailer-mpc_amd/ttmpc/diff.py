@@ -11,6 +11,11 @@ with every solve taped on the device), backward is ``ClosedLoop.backward`` (the 
 one ``vjp_device`` per step).  For a scalar loss on the visited states S and the applied controls Ua it returns
 dL/d(x_init, wq_wr, plan_x, plan_u, noise).
 
+Both layers also take the model geometry as a tensor: ``model`` = (L1, L2, M) of the controller's model (applied to the
+handle with ``set_model``) and, for the closed loop, ``plant_model`` = the plant's.  Their gradients come from the model
+instantiations of the adjoint kernels (include/ttmpc.h, tt_track_vjp_model_device, tt_policy_plant_vjp_model_device),
+summed over the batch.
+
 ``DifferentiableLqrScore(params)`` is the LQR terminal score the drivers report at the end of a run
 (``ttmpc.lqr.lqr_scores``): forward one lqr_kernel launch, backward one lqr_vjp_kernel launch
 (``ttmpc.lqr.lqr_scores_vjp``), differentiable with respect to x_cur, x_goal, Q and R.  Fed with the last state of a
@@ -22,8 +27,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-__all__ = ["TrackingSolveFunction", "DifferentiableTracking", "ClosedLoopFunction", "DifferentiableClosedLoop",
-           "LqrScoreFunction", "DifferentiableLqrScore"]
+__all__ = ["TrackingSolveFunction", "TrackingSolveModelFunction", "DifferentiableTracking", "ClosedLoopFunction",
+           "ClosedLoopModelFunction", "DifferentiableClosedLoop", "LqrScoreFunction", "DifferentiableLqrScore"]
 
 
 def _ptr(t):
@@ -38,6 +43,19 @@ def _check(name, t, shape):
     return t.detach().contiguous()
 
 
+def _geometry(name, t):
+    """(L1, L2, M) of a geometry tensor as host floats: float64, shape (3,), on the CPU or on a device (one host
+    read)."""
+    if not (torch.is_tensor(t) and t.dtype == torch.float64 and tuple(t.shape) == (3,)):
+        raise TypeError(f"{name} must be a float64 tensor of shape (3,) = (L1, L2, M)")
+    return tuple(float(v) for v in t.detach().cpu().tolist())
+
+
+def _batch_sum(g, device):
+    """The per-instance gradients (B,3) summed over the batch, on the geometry tensor's device."""
+    return g.sum(dim=0).to(device)
+
+
 class TrackingSolveFunction(torch.autograd.Function):
     """``X, U, status = TrackingSolveFunction.apply(solver, x0, xref, uref, wq_wr, z_guess)``.
 
@@ -48,63 +66,102 @@ class TrackingSolveFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, solver, x0, xref, uref, wq_wr, z_guess):
-        N, B = solver.N, x0.shape[0]
-        x0 = _check("x0", x0, (B, 6))
-        xref = _check("xref", xref, (B, N + 1, 6))
-        uref = _check("uref", uref, (B, N, 2))
-        wq_wr = None if wq_wr is None else _check("wq_wr", wq_wr, (B, 8))
-        z_guess = None if z_guess is None else _check("z_guess", z_guess, (B, 8 * N + 6))
-        dev = x0.device
-        X = torch.empty((B, N + 1, 6), dtype=torch.float64, device=dev)
-        U = torch.empty((B, N, 2), dtype=torch.float64, device=dev)
-        dual = torch.empty((B, N + 1, 22), dtype=torch.float64, device=dev)
-        status = torch.empty((B,), dtype=torch.int32, device=dev)
-        solver.solve_ex_device(B, x0.data_ptr(), xref.data_ptr(), uref.data_ptr(), X.data_ptr(), U.data_ptr(),
-                               status.data_ptr(), wq_wr=_ptr(wq_wr), z_guess=_ptr(z_guess), dual=dual.data_ptr(),
-                               stream=torch.cuda.current_stream(dev).cuda_stream)
-        ctx.solver = solver
-        ctx.has_w = wq_wr is not None
-        ctx.save_for_backward(X, U, dual, status, xref, uref, *(() if wq_wr is None else (wq_wr,)))
-        ctx.mark_non_differentiable(status)
-        return X, U, status
+        return _track_forward(ctx, solver, x0, xref, uref, wq_wr, z_guess)
 
     @staticmethod
     def backward(ctx, grad_X, grad_U, _grad_status):
-        X, U, dual, status, xref, uref = ctx.saved_tensors[:6]
-        wq_wr = ctx.saved_tensors[6] if ctx.has_w else None
-        need = ctx.needs_input_grad  # (solver, x0, xref, uref, wq_wr, z_guess)
-        if grad_X is None and grad_U is None:
-            return (None,) * 6
-        B, N, dev = X.shape[0], ctx.solver.N, X.device
-        gX = None if grad_X is None else grad_X.to(torch.float64).contiguous()
-        gU = None if grad_U is None else grad_U.to(torch.float64).contiguous()
-        new = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)  # noqa: E731
-        g_x0 = new(B, 6) if need[1] else None
-        g_xref = new(B, N + 1, 6) if need[2] else None
-        g_uref = new(B, N, 2) if need[3] else None
-        g_w = new(B, 8) if need[4] else None
-        ctx.solver.vjp_device(B, X.data_ptr(), U.data_ptr(), dual.data_ptr(), xref.data_ptr(), uref.data_ptr(),
-                              status.data_ptr(), grad_x=_ptr(gX), grad_u=_ptr(gU), g_x0=_ptr(g_x0), g_xref=_ptr(g_xref),
-                              g_uref=_ptr(g_uref), g_wq_wr=_ptr(g_w), wq_wr=_ptr(wq_wr),
-                              stream=torch.cuda.current_stream(dev).cuda_stream)
-        return None, g_x0, g_xref, g_uref, g_w, None
+        return _track_backward(ctx, grad_X, grad_U, False)[0]
+
+
+def _track_forward(ctx, solver, x0, xref, uref, wq_wr, z_guess):
+    N, B = solver.N, x0.shape[0]
+    x0 = _check("x0", x0, (B, 6))
+    xref = _check("xref", xref, (B, N + 1, 6))
+    uref = _check("uref", uref, (B, N, 2))
+    wq_wr = None if wq_wr is None else _check("wq_wr", wq_wr, (B, 8))
+    z_guess = None if z_guess is None else _check("z_guess", z_guess, (B, 8 * N + 6))
+    dev = x0.device
+    X = torch.empty((B, N + 1, 6), dtype=torch.float64, device=dev)
+    U = torch.empty((B, N, 2), dtype=torch.float64, device=dev)
+    dual = torch.empty((B, N + 1, 22), dtype=torch.float64, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    solver.solve_ex_device(B, x0.data_ptr(), xref.data_ptr(), uref.data_ptr(), X.data_ptr(), U.data_ptr(),
+                           status.data_ptr(), wq_wr=_ptr(wq_wr), z_guess=_ptr(z_guess), dual=dual.data_ptr(),
+                           stream=torch.cuda.current_stream(dev).cuda_stream)
+    ctx.solver = solver
+    ctx.has_w = wq_wr is not None
+    ctx.save_for_backward(X, U, dual, status, xref, uref, *(() if wq_wr is None else (wq_wr,)))
+    ctx.mark_non_differentiable(status)
+    return X, U, status
+
+
+def _track_backward(ctx, grad_X, grad_U, want_model):
+    """-> ((None, g_x0, g_xref, g_uref, g_wq_wr, None), g_model (B,3) or None)"""
+    X, U, dual, status, xref, uref = ctx.saved_tensors[:6]
+    wq_wr = ctx.saved_tensors[6] if ctx.has_w else None
+    need = ctx.needs_input_grad  # (solver, x0, xref, uref, wq_wr, z_guess[, model])
+    if grad_X is None and grad_U is None:
+        return (None,) * 6, None
+    B, N, dev = X.shape[0], ctx.solver.N, X.device
+    gX = None if grad_X is None else grad_X.to(torch.float64).contiguous()
+    gU = None if grad_U is None else grad_U.to(torch.float64).contiguous()
+    new = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)  # noqa: E731
+    g_x0 = new(B, 6) if need[1] else None
+    g_xref = new(B, N + 1, 6) if need[2] else None
+    g_uref = new(B, N, 2) if need[3] else None
+    g_w = new(B, 8) if need[4] else None
+    g_m = new(B, 3) if want_model else None
+    ctx.solver.vjp_device(B, X.data_ptr(), U.data_ptr(), dual.data_ptr(), xref.data_ptr(), uref.data_ptr(),
+                          status.data_ptr(), grad_x=_ptr(gX), grad_u=_ptr(gU), g_x0=_ptr(g_x0), g_xref=_ptr(g_xref),
+                          g_uref=_ptr(g_uref), g_wq_wr=_ptr(g_w), wq_wr=_ptr(wq_wr),
+                          stream=torch.cuda.current_stream(dev).cuda_stream, g_model=_ptr(g_m))
+    return (None, g_x0, g_xref, g_uref, g_w, None), g_m
+
+
+class TrackingSolveModelFunction(torch.autograd.Function):
+    """``X, U, status = TrackingSolveModelFunction.apply(solver, x0, xref, uref, wq_wr, z_guess, model)``:
+    ``TrackingSolveFunction`` with the solver's geometry as an input.  model: float64 (3,) = (L1, L2, M), on the CPU or
+    on a device (then the forward reads it to the host once).  The forward applies it with ``solver.set_model`` when it
+    differs from the handle's values, and it stays applied; the backward runs the adjoint kernel's model instantiation
+    and returns the per-instance gradients summed over B on the tensor's device.  It raises if the handle's geometry
+    was changed between the forward and the backward."""
+
+    @staticmethod
+    def forward(ctx, solver, x0, xref, uref, wq_wr, z_guess, model):
+        vals = _geometry("model", model)
+        if vals != solver.model():
+            solver.set_model(*vals)
+        ctx.geometry, ctx.like = vals, model.device
+        return _track_forward(ctx, solver, x0, xref, uref, wq_wr, z_guess)
+
+    @staticmethod
+    def backward(ctx, grad_X, grad_U, _grad_status):
+        if ctx.geometry != ctx.solver.model():
+            raise RuntimeError(f"the solver's geometry changed since the forward: {ctx.geometry} -> "
+                               f"{ctx.solver.model()}")
+        g, g_m = _track_backward(ctx, grad_X, grad_U, ctx.needs_input_grad[6])
+        return (*g, None if g_m is None else _batch_sum(g_m, ctx.like))
 
 
 class DifferentiableTracking:
-    """``X, U, status = layer(x0, xref, uref, wq_wr=None, z_guess=None)`` with float64 CUDA tensors.
+    """``X, U, status = layer(x0, xref, uref, wq_wr=None, z_guess=None, model=None)`` with float64 CUDA tensors.
 
     A thin callable over ``TrackingSolveFunction`` for one ``BatchSolver`` (TT_VARIANT_TRACK, _NMPC or _FUZZY; the
     fuzzy variant needs wq_wr).  One handle serialises its solves on one stream: the forward uses workspaces of the
     handle, so every forward of one layer must be enqueued on the same stream (and a second layer wants its own
     solver).  The backward uses no buffer of the handle and may run on any stream that is ordered behind the forward,
     as autograd's stream bookkeeping arranges.  Look at ``status`` (and at ``solver.vjp_device(..., vjp_status=...)``
-    when in doubt) to see which instances gave a gradient: failed ones give zeros."""
+    when in doubt) to see which instances gave a gradient: failed ones give zeros.  With ``model`` (a float64 (3,)
+    tensor (L1, L2, M), CPU or device) the solver's geometry is an input too: ``TrackingSolveModelFunction``."""
 
     def __init__(self, solver):
         self.solver = solver
 
-    def __call__(self, x0, xref, uref, wq_wr=None, z_guess=None):
-        return TrackingSolveFunction.apply(self.solver, x0, xref, uref, wq_wr, z_guess)
+    def __call__(self, x0, xref, uref, wq_wr=None, z_guess=None, model=None):
+        """model: float64 (3,) tensor (L1, L2, M) or None (the solver's geometry as it is, no gradient for it)."""
+        if model is None:
+            return TrackingSolveFunction.apply(self.solver, x0, xref, uref, wq_wr, z_guess)
+        return TrackingSolveModelFunction.apply(self.solver, x0, xref, uref, wq_wr, z_guess, model)
 
 
 class ClosedLoopFunction(torch.autograd.Function):
@@ -116,53 +173,99 @@ class ClosedLoopFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise):
-        if (plan_x is None) != (plan_u is None):
-            raise ValueError("give plan_x and plan_u together")
-        B = x_init.shape[0]
-        x_init = _check("x_init", x_init, (B, 6))
-        if plan_x is not None:
-            Np = plan_u.shape[-2]
-            P = plan_x.shape[0]
-            if plan_x.dim() != 3 or P not in (1, B):
-                raise ValueError("plan_x must be (1, Np+1, 6) for a shared plan or (B, Np+1, 6)")
-            loop.plan_x, loop.plan_u = _check("plan_x", plan_x, (P, Np + 1, 6)), _check("plan_u", plan_u, (P, Np, 2))
-        out = loop.run_tape(x_init, T_sim, noise=noise, wq_wr=wq_wr)
-        tape = out["tape"]
-        ctx.loop, ctx.tape = loop, tape
-        status = tape.status.clone()   # (copies: the node keeps the tape, the outputs must not keep the node)
-        ctx.mark_non_differentiable(status)
-        return tape.S.clone(), tape.Ua.clone(), status
+        return _loop_forward(ctx, loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise)
 
     @staticmethod
     def backward(ctx, grad_S, grad_Ua, _grad_status):
-        need = ctx.needs_input_grad  # (loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise)
-        tape = ctx.tape
-        if grad_S is None and grad_Ua is None:
-            return (None,) * 7
-        GS = torch.zeros_like(tape.S) if grad_S is None else grad_S.to(torch.float64).contiguous()
-        GU = torch.zeros_like(tape.Ua) if grad_Ua is None else grad_Ua.to(torch.float64).contiguous()
-        g = ctx.loop.backward(tape, GS, GU)
-        pick = lambda i, k: g[k] if need[i] else None  # noqa: E731
-        return (None, None, pick(2, "g_x_init"), pick(3, "g_wq_wr"), pick(4, "g_plan_x"), pick(5, "g_plan_u"),
-                pick(6, "g_noise"))
+        return _loop_backward(ctx, grad_S, grad_Ua, False)[0]
+
+
+def _loop_forward(ctx, loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise):
+    if (plan_x is None) != (plan_u is None):
+        raise ValueError("give plan_x and plan_u together")
+    B = x_init.shape[0]
+    x_init = _check("x_init", x_init, (B, 6))
+    if plan_x is not None:
+        Np = plan_u.shape[-2]
+        P = plan_x.shape[0]
+        if plan_x.dim() != 3 or P not in (1, B):
+            raise ValueError("plan_x must be (1, Np+1, 6) for a shared plan or (B, Np+1, 6)")
+        loop.plan_x, loop.plan_u = _check("plan_x", plan_x, (P, Np + 1, 6)), _check("plan_u", plan_u, (P, Np, 2))
+    out = loop.run_tape(x_init, T_sim, noise=noise, wq_wr=wq_wr)
+    tape = out["tape"]
+    ctx.loop, ctx.tape = loop, tape
+    status = tape.status.clone()   # (copies: the node keeps the tape, the outputs must not keep the node)
+    ctx.mark_non_differentiable(status)
+    return tape.S.clone(), tape.Ua.clone(), status
+
+
+def _loop_backward(ctx, grad_S, grad_Ua, want_model):
+    """-> ((None, None, g_x_init, g_wq_wr, g_plan_x, g_plan_u, g_noise), ClosedLoop.backward's dict or None)"""
+    need = ctx.needs_input_grad  # (loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise[, model, plant_model])
+    tape = ctx.tape
+    if grad_S is None and grad_Ua is None:
+        return (None,) * 7, None
+    GS = torch.zeros_like(tape.S) if grad_S is None else grad_S.to(torch.float64).contiguous()
+    GU = torch.zeros_like(tape.Ua) if grad_Ua is None else grad_Ua.to(torch.float64).contiguous()
+    g = ctx.loop.backward(tape, GS, GU, model=True) if want_model else ctx.loop.backward(tape, GS, GU)
+    pick = lambda i, k: g[k] if need[i] else None  # noqa: E731
+    return (None, None, pick(2, "g_x_init"), pick(3, "g_wq_wr"), pick(4, "g_plan_x"), pick(5, "g_plan_u"),
+            pick(6, "g_noise")), g
+
+
+class ClosedLoopModelFunction(torch.autograd.Function):
+    """``S, Ua, status = ClosedLoopModelFunction.apply(loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise, model,
+    plant_model)``: ``ClosedLoopFunction`` with the two geometries as inputs, each a float64 (3,) tensor (L1, L2, M) on
+    the CPU or on a device (one host read each), or None.  model is the geometry the controller believes, plant_model
+    the plant's; the forward applies them with ``loop.set_model`` when they differ from the current values, and they
+    stay applied.  The backward returns their gradients summed over B on each tensor's device; the same tensor given
+    as both receives the sum of the two, the gradient for a geometry controller and plant share."""
+
+    @staticmethod
+    def forward(ctx, loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise, model, plant_model):
+        vs = None if model is None else _geometry("model", model)
+        vp = None if plant_model is None else _geometry("plant_model", plant_model)
+        loop.set_model(solver=None if vs is None or vs == loop.solver.model() else vs,
+                       plant=None if vp is None or vp == loop.plant_model() else vp)
+        ctx.like = tuple(None if t is None else t.device for t in (model, plant_model))
+        return _loop_forward(ctx, loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise)
+
+    @staticmethod
+    def backward(ctx, grad_S, grad_Ua, _grad_status):
+        need = ctx.needs_input_grad
+        grads, g = _loop_backward(ctx, grad_S, grad_Ua, need[7] or need[8])
+        gm = [None, None]
+        if g is not None and (need[7] or need[8]):
+            for i, key in enumerate(("g_model_solver", "g_model_plant")):
+                if need[7 + i]:
+                    gm[i] = _batch_sum(g[key], ctx.like[i])
+        return (*grads, *gm)
 
 
 class DifferentiableClosedLoop:
-    """``S, Ua, status = layer(x_init, T_sim, wq_wr=None, plan_x=None, plan_u=None, noise=None)``.
+    """``S, Ua, status = layer(x_init, T_sim, wq_wr=None, plan_x=None, plan_u=None, noise=None, model=None,
+    plant_model=None)``.
 
     A thin callable over ``ClosedLoopFunction`` for one ``ClosedLoop`` whose solver is TT_VARIANT_TRACK or
     TT_VARIANT_NMPC (any of the three failure policies, warm start on or off, measurement or in-plant noise, shared or
     per-instance plan).  A TT_VARIANT_FUZZY solver and a switch solver raise ValueError.  A plan given here replaces
     the loop's.  The forward synchronises once at its end, as ``run`` does; the backward does not.  Zero gradient comes
     from: failed solves (whatever the policy then applies), stopped instances, variables sitting on a bound, and the
-    warm start (z_guess does not move a converged solution)."""
+    warm start (z_guess does not move a converged solution).  With ``model`` and / or ``plant_model`` (float64 (3,)
+    tensors (L1, L2, M), CPU or device) the controller's and the plant's geometry are inputs too:
+    ``ClosedLoopModelFunction``."""
 
     def __init__(self, loop):
         loop._check_differentiable()
         self.loop = loop
 
-    def __call__(self, x_init, T_sim, wq_wr=None, plan_x=None, plan_u=None, noise=None):
-        return ClosedLoopFunction.apply(self.loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise)
+    def __call__(self, x_init, T_sim, wq_wr=None, plan_x=None, plan_u=None, noise=None, model=None, plant_model=None):
+        """model, plant_model: float64 (3,) tensors (L1, L2, M) of the controller's and of the plant's geometry, or
+        None (as they are, no gradient)."""
+        if model is None and plant_model is None:
+            return ClosedLoopFunction.apply(self.loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise)
+        return ClosedLoopModelFunction.apply(self.loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise, model,
+                                             plant_model)
 
 
 def _host(name, m, n):

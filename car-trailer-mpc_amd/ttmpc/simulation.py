@@ -167,16 +167,25 @@ def interpolate(state_traj, input_traj, dt_1, dt_2, stream=None):
 
 def policy_plant_vjp(state, status, active_after, consecutive, adj_state, adj_u_last, grad_u, params,
                      disturbance_params=None, policy="track", active_before=None, grad_u_applied=None,
-                     g_state_noise=None, stream=None):
+                     g_state_noise=None, stream=None, g_model=None):
     """Adjoint of one policy + plant step (tt_policy_plant_vjp_device; include/ttmpc.h has the branch table), device
     tensors: state (B,6) = S_t, status / active_after / consecutive (B,) int32 from the logs, active_before (B,) or None
     (the first step: all active), grad_u_applied (B,2) = dL/dUa_t or None.  In place: adj_state (B,6) = dL/dS_{t+1}
     becomes the plant's share of dL/dS_t, adj_u_last (B,2) the adjoint of u_last; grad_u (B,N,2) gets the seed
-    dL/dU_t[0] in row 0; g_state_noise (B,6), if given, dL/d(in-plant noise)."""
+    dL/dU_t[0] in row 0; g_state_noise (B,6), if given, dL/d(in-plant noise).  g_model (B,3), if given, is an
+    accumulator: += adj_state' dS_{t+1}/d(L1, L2, M) of the plant's geometry, with adj_state as it came in
+    (tt_policy_plant_vjp_model_device); stopped and inactive instances add nothing."""
     dev = state.device
     if policy not in POLICIES:
         raise ValueError(f"policy must be one of {sorted(POLICIES)}")
     p = plant(params, disturbance_params)
+    if g_model is not None:
+        _check(lib().tt_policy_plant_vjp_model_device(
+            state.shape[0], grad_u.shape[1], C.byref(p), POLICIES[policy], state.data_ptr(), status.data_ptr(),
+            _ptr(active_before), active_after.data_ptr(), consecutive.data_ptr(), _ptr(grad_u_applied),
+            adj_state.data_ptr(), adj_u_last.data_ptr(), grad_u.data_ptr(), _ptr(g_state_noise), g_model.data_ptr(),
+            _stream(stream, dev)), "tt_policy_plant_vjp_model_device")
+        return adj_state, adj_u_last, grad_u
     _check(lib().tt_policy_plant_vjp_device(state.shape[0], grad_u.shape[1], C.byref(p), POLICIES[policy],
                                             state.data_ptr(), status.data_ptr(), _ptr(active_before),
                                             active_after.data_ptr(), consecutive.data_ptr(), _ptr(grad_u_applied),
@@ -212,9 +221,10 @@ class LoopTape:
     (K,B,2), status / iters / collide / active (K,B) (active: after each step).  ``ClosedLoop.run_tape`` also keeps
     what ``ClosedLoop.backward`` needs, None in a plain ``run``: consec (K,B), the consecutive-failure count after each
     step, each step's solve X (K,B,N+1,6), U (K,B,N,2), dual (K,B,N+1,22) and the noise it used (K,B,6) or None.
-    wq_wr (B,8) or None are the run's weights, plan_x / plan_u the plan it saw."""
+    wq_wr (B,8) or None are the run's weights, plan_x / plan_u the plan it saw, model_solver / model_plant the
+    (L1, L2, M) of the solver's handle and of the plant during a taped run."""
     __slots__ = ("ks", "S", "Ua", "status", "iters", "collide", "active", "consec", "X", "U", "dual", "noise", "wq_wr",
-                 "plan_x", "plan_u")
+                 "plan_x", "plan_u", "model_solver", "model_plant")
     # (log field, the loop's buffer a step leaves it in), in the order record() copies them; the solve writes dual
     STEP = (("S", "state"), ("Ua", "u_applied"), ("status", "st"), ("iters", "it"), ("collide", "flag"),
             ("active", "active"), ("consec", "consec"), ("X", "X"), ("U", "U"))
@@ -235,6 +245,7 @@ class LoopTape:
         if taped:
             log.consec = new(K, B, dtype=torch.int32)
             log.X, log.U, log.dual = new(K, B, N + 1, 6), new(K, B, N, 2), new(K, B, N + 1, 22)
+            log.model_solver, log.model_plant = loop.solver.model(), loop.plant_model()   # (run_tape: a BatchSolver)
         return log
 
     def record(self, j, loop):
@@ -321,6 +332,24 @@ class ClosedLoop:
         self.gen = torch.Generator(device=self.dev)
         self.gen.manual_seed(int(seed))
         self.stream = torch.cuda.Stream(self.dev)
+
+    def plant_model(self):
+        """The plant's (L1, L2, M)."""
+        return tuple(float(self.params[k]) for k in ("L1", "L2", "M"))
+
+    def set_model(self, solver=None, plant=None):
+        """Change the geometry (L1, L2, M) the controller believes (``solver``: through the handle, tt_set_model) and /
+        or the plant's (``plant``: this loop's own copy in ``params``, which also feeds the collision check).  Host-side
+        state only: later steps and runs use the new values.  ``run_graph`` captures its step anew on every call, so it
+        never replays a capture made with other values.  A tape keeps the geometry of its run; ``backward`` on a tape
+        made before a change raises."""
+        if solver is not None:
+            self.solver.set_model(*(float(v) for v in solver))
+        if plant is not None:
+            L1, L2, M = (float(v) for v in plant)
+            if not (L1 > 0 and L2 > 0 and math.isfinite(L1) and math.isfinite(L2) and math.isfinite(M)):
+                raise ValueError("plant geometry: L1, L2 must be > 0 and M finite")
+            self.params.update(L1=L1, L2=L2, M=M)
 
     def _alloc(self, B):
         N, d, f = self.N, self.dev, torch.float64
@@ -609,15 +638,23 @@ class ClosedLoop:
         torch.cuda.synchronize(self.dev)
         return dict(self._policy_logs(), **tape.result(), tape=tape)
 
-    def backward(self, tape, GS, GU):
+    def backward(self, tape, GS, GU, model=False):
         """The adjoint of a taped run for a scalar loss L(S, Ua): GS = dL/dS (K+1,B,6), GU = dL/dUa (K,B,2), float64
         device tensors.  Per step, backwards: tt_policy_plant_vjp_device, the step's window again,
         tt_track_vjp_device on the taped solve, tt_sim_window_vjp_device (include/ttmpc.h, "Reverse mode of the closed
         loop").  Enqueued on the loop's stream, which is ordered behind the current stream at entry and ahead of it at
         exit; no host synchronisation.  Returns device tensors dict(g_x_init (B,6), g_wq_wr (B,8), g_plan_x, g_plan_u
         (shaped as the loop's plan: summed over B for a shared one), g_noise (K,B,6): of the measurement noise, or with
-        noise_in_plant of the plant's process noise; zeros where the run had no noise)."""
+        noise_in_plant of the plant's process noise; zeros where the run had no noise).  model=True adds g_model_solver
+        and g_model_plant (B,3): dL/d(L1, L2, M) per instance of the geometry the controller believes and of the
+        plant's; the step stays four launches (the model instantiations of the plant and solve adjoints, the solve's
+        term accumulated in place).  Raises if the solver's or the plant's geometry is no longer that of the tape."""
         self._check_differentiable()
+        if tape.model_solver is not None and (tape.model_solver != self.solver.model() or
+                                              tape.model_plant != self.plant_model()):
+            raise ValueError(f"the geometry changed since the tape was made: solver {tape.model_solver} -> "
+                             f"{self.solver.model()}, plant {tape.model_plant} -> {self.plant_model()}; run the tape "
+                             "again, or set the geometry back before the backward")
         s, d, N = self.stream, self.dev, self.N
         K, B = tape.status.shape
         Np = tape.plan_u.shape[-2]
@@ -631,6 +668,7 @@ class ClosedLoop:
         g_w, g_px, g_pu, g_n = z(B, 8), z(B, Np + 1, 6), z(B, Np, 2), z(K, B, 6)
         xref, uref = z(B, N + 1, 6), z(B, N, 2)
         g_x0, g_xr, g_ur, g_ws = z(B, 6), z(B, N + 1, 6), z(B, N, 2), z(B, 8)
+        g_ms, g_mp = (z(B, 3), z(B, 3)) if model else (None, None)
         in_plant = self.noise_in_plant and tape.noise is not None
         meas = self.measurement_noise and tape.noise is not None
         # the raw entries, not the module-level wrappers: a backward step is four short launches the host only just
@@ -640,20 +678,22 @@ class ClosedLoop:
         wq = 0 if tape.wq_wr is None else tape.wq_wr.data_ptr()
         s.wait_stream(torch.cuda.current_stream(d))
         for t in range(K - 1, -1, -1):
-            _check(L.tt_policy_plant_vjp_device(B, N, C.byref(p), POLICIES[self.policy], tape.S[t].data_ptr(),
-                                                tape.status[t].data_ptr(),
-                                                None if t == 0 else tape.active[t - 1].data_ptr(),
-                                                tape.active[t].data_ptr(), tape.consec[t].data_ptr(), GU[t].data_ptr(),
-                                                a.data_ptr(), abar.data_ptr(), gU.data_ptr(),
-                                                g_n[t].data_ptr() if in_plant else None, sp),
-                   "tt_policy_plant_vjp_device")
+            pp = (B, N, C.byref(p), POLICIES[self.policy], tape.S[t].data_ptr(), tape.status[t].data_ptr(),
+                  None if t == 0 else tape.active[t - 1].data_ptr(), tape.active[t].data_ptr(),
+                  tape.consec[t].data_ptr(), GU[t].data_ptr(), a.data_ptr(), abar.data_ptr(), gU.data_ptr(),
+                  g_n[t].data_ptr() if in_plant else None)
+            if model:
+                _check(L.tt_policy_plant_vjp_model_device(*pp, g_mp.data_ptr(), sp), "tt_policy_plant_vjp_model_device")
+            else:
+                _check(L.tt_policy_plant_vjp_device(*pp, sp), "tt_policy_plant_vjp_device")
             _check(L.tt_sim_window_device(B, N, int(tape.ks[t]), int(Np), tape.plan_x.data_ptr(),
                                           tape.plan_u.data_ptr(), per, None, None, None, xref.data_ptr(),
                                           uref.data_ptr(), sp), "tt_sim_window_device")
             self.solver.vjp_device(B, tape.X[t].data_ptr(), tape.U[t].data_ptr(), tape.dual[t].data_ptr(),
                                    xref.data_ptr(), uref.data_ptr(), tape.status[t].data_ptr(), grad_u=gU.data_ptr(),
                                    g_x0=g_x0.data_ptr(), g_xref=g_xr.data_ptr(), g_uref=g_ur.data_ptr(),
-                                   g_wq_wr=g_ws.data_ptr(), wq_wr=wq, stream=s.cuda_stream)
+                                   g_wq_wr=g_ws.data_ptr(), wq_wr=wq, stream=s.cuda_stream,
+                                   g_model=g_ms.data_ptr() if model else 0, accumulate=True)
             _check(L.tt_sim_window_vjp_device(B, N, int(tape.ks[t]), int(Np), g_xr.data_ptr(), g_ur.data_ptr(),
                                               g_px.data_ptr(), g_pu.data_ptr(), g_x0.data_ptr(), GS[t].data_ptr(),
                                               a.data_ptr(), g_ws.data_ptr(), g_w.data_ptr(),
@@ -662,7 +702,10 @@ class ClosedLoop:
             if not per:
                 g_px, g_pu = g_px.sum(dim=0, keepdim=True), g_pu.sum(dim=0, keepdim=True)
         torch.cuda.current_stream(d).wait_stream(s)
-        return {"g_x_init": a, "g_wq_wr": g_w, "g_plan_x": g_px, "g_plan_u": g_pu, "g_noise": g_n}
+        out = {"g_x_init": a, "g_wq_wr": g_w, "g_plan_x": g_px, "g_plan_u": g_pu, "g_noise": g_n}
+        if model:
+            out.update(g_model_solver=g_ms, g_model_plant=g_mp)
+        return out
 
     def _policy_logs(self):
         """failure_count / consecutive_failures of the reference drivers, per instance, and whether the

@@ -185,6 +185,42 @@ int tt_track_vjp(void* handle, int B, const double* x, const double* u, const do
                  const double* uref, const double* wq_wr, const int* status, const double* grad_x,
                  const double* grad_u, const tt_track_vjp_out* out);
 
+/* The same adjoint with the gradient in the model geometry theta = (L1, L2, Mh) of the handle (tt_config, or the
+ * last tt_set_model).  Only the dynamics rows c_{k+1} = x_{k+1} - x_k - dt f(x_k, u_k) and the -A_k' y_{k+1} part of
+ * the stationarity rows depend on theta, so with lam of the same solve K (lam_z, lam_y) = (g, 0)
+ *     dL/dtheta = dt sum_{k<N} [ lam_x,k' (dJ_f(x_k)/dtheta)' y_{k+1} + lam_y,k+1' df(x_k, u_k)/dtheta ],
+ * closed forms in rows 2, 3 of f and five entries of J_f.  lam_y comes from the x-rows of K behind the forward
+ * sweep (lam_y,N = gX_N - H_N lam_x,N; lam_y,k = gX_k - H_k lam_x,k + A_k' lam_y,k+1): no second factorisation,
+ * the same LDS record (track_vjp_kernel's model instantiation, tt_vjp.hip).  dt is not a parameter here.
+ *     g_model [B][3]        dL/dL1, dL/dL2, dL/dMh per instance; the sum over B for the geometry the batch shares
+ *                           is the caller's, as for g_Q and g_R of the LQR adjoint
+ *   accumulate == 0: g_model[b] = value, zeros for vjp_status 1 and 2.  accumulate != 0: g_model[b] += value (one
+ *   writer per instance, no atomics); a failed instance adds nothing.  accumulate concerns g_model only.
+ *   g_model == NULL: the call is tt_track_vjp[_device] (the same kernel instantiation, the same bits); with it the
+ *   other four arrays and vjp_status are bitwise what that call writes.
+ * tt_track_vjp_model: host pointers, synchronous, as tt_track_vjp (with accumulate the host's g_model is read). */
+typedef struct { double* g_x0; double* g_xref; double* g_uref; double* g_wq_wr;
+                 double* g_model;   /* [B][3]  dL/dL1, dL/dL2, dL/dMh per instance */
+                 int* vjp_status; } tt_track_vjp_model_out;
+int tt_track_vjp_model_device(void* handle, int B, const double* d_x, const double* d_u, const double* d_dual,
+                              const double* d_xref, const double* d_uref, const double* d_wq_wr, const int* d_status,
+                              const double* d_grad_x, const double* d_grad_u, const tt_track_vjp_model_out* d_out,
+                              int accumulate, void* stream);
+int tt_track_vjp_model(void* handle, int B, const double* x, const double* u, const double* dual, const double* xref,
+                       const double* uref, const double* wq_wr, const int* status, const double* grad_x,
+                       const double* grad_u, const tt_track_vjp_model_out* out, int accumulate);
+
+/* The geometry of a tracking handle (TT_VARIANT_TRACK, _NMPC, _FUZZY) without rebuilding it.  tt_set_model applies
+ * tt_create's validation (L1, L2 > 0, Mh finite; else -EINVAL and the handle keeps its values); an OBCA handle returns
+ * -EINVAL (its geometry also enters the H-representations).  It changes host-side state only: L1, L2 and Mh are
+ * launch arguments of every kernel of the handle (solves, their exporting twins, the sensitivity and adjoint kernels,
+ * host and device entry points alike), so every later call runs with the new values and a solve is bitwise that of
+ * a fresh handle created with them.  Calls on one handle stay serialised as before: work already enqueued keeps
+ * the values it was launched with, and so does a captured graph (hipGraph, ClosedLoop.run_graph): capture again
+ * after a change.  tt_get_model reads the current values (NULL pointers are skipped). */
+int tt_set_model(void* handle, double L1, double L2, double Mh);
+int tt_get_model(void* handle, double* L1, double* L2, double* Mh);
+
 /* Replaces TrajectoryOptimization.plan (trajectory_optimization.py:311-331) for B scenarios of a
  * TT_VARIANT_OBCA_PLAN handle.  x0, xgoal [B][6] (ca.vertcat(initial_state, goal_state), 316-323);
  * z_guess [B][n], n = N(8+16M)+6+16M, the reference's interleaved [x_k,u_k,mu_k,lam_k] vector
@@ -366,6 +402,17 @@ int tt_policy_plant_vjp_device(int B, int N, const tt_plant* p, int policy, cons
 int tt_sim_window_vjp_device(int B, int N, int k, int Np, const double* g_xref, const double* g_uref, double* g_plan_x,
                              double* g_plan_u, const double* g_x0, const double* grad_state, double* adj_state,
                              const double* g_wq_wr, double* g_wq_wr_acc, double* g_meas_noise, void* stream);
+/* tt_policy_plant_vjp_device plus the plant's share of the gradient in its geometry (L1, L2, Mh of tt_plant):
+ *     g_model_acc [B][3] += a' dS_{t+1}/dtheta = dt slip (a_2 df_2/dtheta + a_3 df_3/dtheta),
+ * a = adj_state before the J_q product and slip the forward's factor (the lateral-slip and friction terms do not
+ * depend on the geometry).  An accumulator the caller zeroes; stopped and inactive instances add nothing.  The sum
+ * over the steps of a sweep is dL/d(plant geometry) per instance; the controller's share comes from
+ * tt_track_vjp_model_device.  g_model_acc == NULL is tt_policy_plant_vjp_device, the same kernel and bits. */
+int tt_policy_plant_vjp_model_device(int B, int N, const tt_plant* p, int policy, const double* state,
+                                     const int* status, const int* active_before, const int* active_after,
+                                     const int* consecutive, const double* grad_u_applied, double* adj_state,
+                                     double* adj_u_last, double* grad_u, double* g_state_noise, double* g_model_acc,
+                                     void* stream);
 
 /* lqr_distance (LQR_cost.py:7-41) for B instances: A, B of the forward-Euler map at (x_goal, u_goal),
  * P = DARE(A, B, Q, R) symmetrised, score[b] = (x_cur - x_goal)' P (x_cur - x_goal).  Q (6x6), R (2x2) are
