@@ -6,11 +6,13 @@
 //   policy_plant_vjp_kernel   one instance per thread: a <- J_q' a, the seed g_u0 of the solve adjoint, the adjoint
 //                             of u_last, dL/d(in-plant noise)
 //   sim_window_vjp_kernel     one thread per (instance, window row): the window's scatter into the plan gradient
-//                             with the forward's end padding, and the per-instance accumulation of the step
+//                             with the forward's end padding, and the per-instance accumulation of the step; its
+//                             fuzzy instantiation first applies the adjoint of the weight rule (tt_fuzzy_rule.hpp)
 #include <errno.h>
 #include <math.h>
 #include <hip/hip_runtime.h>
 
+#include "tt_fuzzy_rule.hpp"
 #include "tt_launch.hpp"
 #include "ttmpc.h"
 
@@ -177,11 +179,24 @@ __global__ void __launch_bounds__(kThreads) policy_plant_vjp_model_kernel(
 // input row j to min(k+j, Np-1) while k < Np (else the input window is zeros).  A destination row belongs to the thread
 // of the first window row that lands on it; the padded tail is summed by that thread in ascending j.  The thread of
 // j = N also does the step's per-instance accumulation: adj += g_x0 + grad_s, g_w_acc += g_w, g_noise = g_x0.
-__global__ void __launch_bounds__(kThreads) sim_window_vjp_kernel(
+// kFuzzy: the weights of the step came from the rule, w = rule(x_meas, xref[0]), so that thread first adds the rule's
+// dL/dpsi to g_x0[3] (as it reads it: the buffer is left alone) and the rule's dL/dtheta to g_rule_acc [B][7], unless
+// the instance's accepted solve was the unit-weight retry; the plain instantiation behind sim_window_vjp_kernel is the
+// kernel as it was.
+struct FuzzyVjpArgs {
+    tt_fuzzy_rule rule;
+    const double* x_meas;
+    const double* xref;
+    const int* retried;
+    double* g_rule_acc;
+};
+
+template <bool kFuzzy>
+__device__ __forceinline__ void sim_window_vjp_body(
     int B, int N, int k, int Np, const double* __restrict__ g_xref, const double* __restrict__ g_uref,
     double* __restrict__ g_plan_x, double* __restrict__ g_plan_u, const double* __restrict__ g_x0,
     const double* __restrict__ grad_s, double* __restrict__ adj, const double* __restrict__ g_w,
-    double* __restrict__ g_w_acc, double* __restrict__ g_noise) {
+    double* __restrict__ g_w_acc, double* __restrict__ g_noise, const FuzzyVjpArgs* fz) {
 #pragma clang fp contract(off)
     const long long t = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (t >= (long long)B * (N + 1)) return;
@@ -222,21 +237,54 @@ __global__ void __launch_bounds__(kThreads) sim_window_vjp_kernel(
         }
     }
     if (j == N) {
+        double x0[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (g_x0)
+#pragma unroll
+            for (int i = 0; i < 6; ++i) x0[i] = g_x0[(size_t)b * 6 + i];
+        if constexpr (kFuzzy) {
+            if (g_x0 && g_w && !(fz->retried && fz->retried[b] != 0)) {
+                double gth[7];
+                const double g_psi = fuzzy_rule_vjp(fz->rule, fz->x_meas[(size_t)b * 6 + 3], fz->x_meas[(size_t)b * 6 + 5],
+                                                    fz->xref[(size_t)b * (N + 1) * 6 + 5], g_w + (size_t)b * 8, gth);
+                x0[3] = x0[3] + g_psi;
+                if (fz->g_rule_acc)
+#pragma unroll
+                    for (int i = 0; i < 7; ++i) fz->g_rule_acc[(size_t)b * 7 + i] += gth[i];
+            }
+        }
         if (adj)
 #pragma unroll
             for (int i = 0; i < 6; ++i) {
                 double v = adj[(size_t)b * 6 + i];
-                if (g_x0) v = v + g_x0[(size_t)b * 6 + i];
+                if (g_x0) v = v + x0[i];
                 if (grad_s) v = v + grad_s[(size_t)b * 6 + i];
                 adj[(size_t)b * 6 + i] = v;
             }
         if (g_noise && g_x0)
 #pragma unroll
-            for (int i = 0; i < 6; ++i) g_noise[(size_t)b * 6 + i] = g_x0[(size_t)b * 6 + i];
+            for (int i = 0; i < 6; ++i) g_noise[(size_t)b * 6 + i] = x0[i];
         if (g_w && g_w_acc)
 #pragma unroll
             for (int i = 0; i < 8; ++i) g_w_acc[(size_t)b * 8 + i] += g_w[(size_t)b * 8 + i];
     }
+}
+
+__global__ void __launch_bounds__(kThreads) sim_window_vjp_kernel(
+    int B, int N, int k, int Np, const double* __restrict__ g_xref, const double* __restrict__ g_uref,
+    double* __restrict__ g_plan_x, double* __restrict__ g_plan_u, const double* __restrict__ g_x0,
+    const double* __restrict__ grad_s, double* __restrict__ adj, const double* __restrict__ g_w,
+    double* __restrict__ g_w_acc, double* __restrict__ g_noise) {
+    sim_window_vjp_body<false>(B, N, k, Np, g_xref, g_uref, g_plan_x, g_plan_u, g_x0, grad_s, adj, g_w, g_w_acc, g_noise,
+                               nullptr);
+}
+
+__global__ void __launch_bounds__(kThreads) sim_window_vjp_fuzzy_kernel(
+    int B, int N, int k, int Np, const double* __restrict__ g_xref, const double* __restrict__ g_uref,
+    double* __restrict__ g_plan_x, double* __restrict__ g_plan_u, const double* __restrict__ g_x0,
+    const double* __restrict__ grad_s, double* __restrict__ adj, const double* __restrict__ g_w,
+    double* __restrict__ g_w_acc, double* __restrict__ g_noise, FuzzyVjpArgs fz) {
+    sim_window_vjp_body<true>(B, N, k, Np, g_xref, g_uref, g_plan_x, g_plan_u, g_x0, grad_s, adj, g_w, g_w_acc, g_noise,
+                              &fz);
 }
 
 }  // namespace
@@ -278,6 +326,22 @@ int tt_sim_window_vjp_device(int B, int N, int k, int Np, const double* g_xref, 
     return launch_flat(sim_window_vjp_kernel, "sim_window_vjp_kernel", (long long)B * (N + 1), stream, B, N, k, Np,
                        g_xref, g_uref, g_plan_x, g_plan_u, g_x0, grad_state, adj_state, g_wq_wr, g_wq_wr_acc,
                        g_meas_noise);
+}
+
+int tt_sim_window_vjp_fuzzy_device(int B, int N, int k, int Np, const double* g_xref, const double* g_uref,
+                                   double* g_plan_x, double* g_plan_u, const double* g_x0, const double* grad_state,
+                                   double* adj_state, const double* g_wq_wr, double* g_wq_wr_acc, double* g_meas_noise,
+                                   const tt_fuzzy_rule* rule, const double* x_meas, const double* xref,
+                                   const int* retried, double* g_rule_acc, void* stream) {
+    if (!rule)
+        return tt_sim_window_vjp_device(B, N, k, Np, g_xref, g_uref, g_plan_x, g_plan_u, g_x0, grad_state, adj_state,
+                                        g_wq_wr, g_wq_wr_acc, g_meas_noise, stream);
+    if (B <= 0 || N < 1 || N > tt_max_horizon() || Np < 1 || k < 0 || !fuzzy_rule_valid(*rule) || !x_meas || !xref)
+        return -EINVAL;
+    const FuzzyVjpArgs fz{*rule, x_meas, xref, retried, g_rule_acc};
+    return launch_flat(sim_window_vjp_fuzzy_kernel, "sim_window_vjp_fuzzy_kernel", (long long)B * (N + 1), stream, B, N,
+                       k, Np, g_xref, g_uref, g_plan_x, g_plan_u, g_x0, grad_state, adj_state, g_wq_wr, g_wq_wr_acc,
+                       g_meas_noise, fz);
 }
 
 }  // extern "C"

@@ -39,6 +39,12 @@ class TTPlant(C.Structure):
                 ("lateral_slip_gain", C.c_double), ("slip_angle_max", C.c_double)]
 
 
+class TTFuzzyRule(C.Structure):
+    """tt_fuzzy_rule (include/ttmpc.h): the constants of mpc_control_fuzzy.py:90-119; the first seven are theta."""
+    _fields_ = [(k, C.c_double) for k in ("psi_full", "gain_hitch", "gain_steer", "gain_rate", "rev_hitch", "rev_steer",
+                                          "rev_rate", "w_min", "w_max", "v_rev")]
+
+
 class TTTrackExtra(C.Structure):
     """tt_track_extra (include/ttmpc.h): the optional outputs of tt_solve_batch_ex*; NULL members are skipped."""
     _fields_ = [("dual", C.c_void_p), ("gain", C.c_void_p), ("dxdx0", C.c_void_p), ("dudx0", C.c_void_p),
@@ -214,6 +220,10 @@ def lib():
            "tt_policy_plant_vjp_model_device": [i, i, C.POINTER(TTPlant), i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                                 vp],
            "tt_sim_window_vjp_device": [i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+           "tt_fuzzy_weights_rule_device": [i, i, C.POINTER(TTFuzzyRule), vp, vp, vp, vp],
+           "tt_fuzzy_weights_vjp_device": [i, i, C.POINTER(TTFuzzyRule), vp, vp, vp, vp, vp, vp, vp],
+           "tt_sim_window_vjp_fuzzy_device": [i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(TTFuzzyRule),
+                                              vp, vp, vp, vp, vp],
            "tt_lqr_score_vjp_device": [i, C.POINTER(TTPlant), _dp, vp, vp, vp, vp, vp, vp, C.POINTER(TTLqrVjpOut),
                                        vp]}
     sim["ttx_obca_set_helpers"] = [C.c_void_p, i]  # diagnostics (not in include/ttmpc.h)
@@ -239,7 +249,8 @@ EXPORTED_SYMBOLS = ("tt_create", "tt_solve_batch", "tt_solve_batch_device", "tt_
                     "tt_track_dual_len", "tt_solve_batch_ex", "tt_solve_batch_ex_device", "tt_track_sens_device",
                     "tt_track_vjp_device", "tt_track_vjp", "tt_policy_plant_vjp_device", "tt_sim_window_vjp_device",
                     "tt_lqr_score_vjp_device", "tt_track_vjp_model_device", "tt_track_vjp_model", "tt_set_model",
-                    "tt_get_model", "tt_policy_plant_vjp_model_device")
+                    "tt_get_model", "tt_policy_plant_vjp_model_device", "tt_fuzzy_weights_rule_device",
+                    "tt_fuzzy_weights_vjp_device", "tt_sim_window_vjp_fuzzy_device")
 
 
 def _ptr(a):

@@ -16,6 +16,10 @@ handle with ``set_model``) and, for the closed loop, ``plant_model`` = the plant
 instantiations of the adjoint kernels (include/ttmpc.h, tt_track_vjp_model_device, tt_policy_plant_vjp_model_device),
 summed over the batch.
 
+A closed loop built with a ``ttmpc.simulation.FuzzyRule`` takes the rule's seven parameters as a tensor too
+(``fuzzy_rule=``, ``ClosedLoopRuleFunction``), and ``fuzzy_weights(x, xref, theta)`` is the rule alone as an autograd
+node (tt_fuzzy_weights_rule_device / tt_fuzzy_weights_vjp_device) whose output feeds ``DifferentiableTracking``'s wq_wr.
+
 ``DifferentiableLqrScore(params)`` is the LQR terminal score the drivers report at the end of a run
 (``ttmpc.lqr.lqr_scores``): forward one lqr_kernel launch, backward one lqr_vjp_kernel launch
 (``ttmpc.lqr.lqr_scores_vjp``), differentiable with respect to x_cur, x_goal, Q and R.  Fed with the last state of a
@@ -28,7 +32,8 @@ import numpy as np
 import torch
 
 __all__ = ["TrackingSolveFunction", "TrackingSolveModelFunction", "DifferentiableTracking", "ClosedLoopFunction",
-           "ClosedLoopModelFunction", "DifferentiableClosedLoop", "LqrScoreFunction", "DifferentiableLqrScore"]
+           "ClosedLoopModelFunction", "ClosedLoopRuleFunction", "DifferentiableClosedLoop", "FuzzyWeightsFunction",
+           "fuzzy_weights", "LqrScoreFunction", "DifferentiableLqrScore"]
 
 
 def _ptr(t):
@@ -54,6 +59,14 @@ def _geometry(name, t):
 def _batch_sum(g, device):
     """The per-instance gradients (B,3) summed over the batch, on the geometry tensor's device."""
     return g.sum(dim=0).to(device)
+
+
+def _theta(t):
+    """The seven rule parameters of a theta tensor as host floats: float64, shape (7,), CPU or device (one host read)."""
+    if not (torch.is_tensor(t) and t.dtype == torch.float64 and tuple(t.shape) == (7,)):
+        raise TypeError("fuzzy_rule must be a float64 tensor of shape (7,) = (psi_full, gain_hitch, gain_steer, "
+                        "gain_rate, rev_hitch, rev_steer, rev_rate)")
+    return tuple(float(v) for v in t.detach().cpu().tolist())
 
 
 class TrackingSolveFunction(torch.autograd.Function):
@@ -199,15 +212,18 @@ def _loop_forward(ctx, loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise):
     return tape.S.clone(), tape.Ua.clone(), status
 
 
-def _loop_backward(ctx, grad_S, grad_Ua, want_model):
+def _loop_backward(ctx, grad_S, grad_Ua, want_model, want_rule=False):
     """-> ((None, None, g_x_init, g_wq_wr, g_plan_x, g_plan_u, g_noise), ClosedLoop.backward's dict or None)"""
-    need = ctx.needs_input_grad  # (loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise[, model, plant_model])
+    need = ctx.needs_input_grad  # (loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise[, model, plant_model[, rule]])
     tape = ctx.tape
     if grad_S is None and grad_Ua is None:
         return (None,) * 7, None
     GS = torch.zeros_like(tape.S) if grad_S is None else grad_S.to(torch.float64).contiguous()
     GU = torch.zeros_like(tape.Ua) if grad_Ua is None else grad_Ua.to(torch.float64).contiguous()
-    g = ctx.loop.backward(tape, GS, GU, model=True) if want_model else ctx.loop.backward(tape, GS, GU)
+    kw = dict(model=True) if want_model else {}
+    if want_rule:
+        kw["rule"] = True
+    g = ctx.loop.backward(tape, GS, GU, **kw)
     pick = lambda i, k: g[k] if need[i] else None  # noqa: E731
     return (None, None, pick(2, "g_x_init"), pick(3, "g_wq_wr"), pick(4, "g_plan_x"), pick(5, "g_plan_u"),
             pick(6, "g_noise")), g
@@ -242,26 +258,102 @@ class ClosedLoopModelFunction(torch.autograd.Function):
         return (*grads, *gm)
 
 
+class ClosedLoopRuleFunction(torch.autograd.Function):
+    """``S, Ua, status = ClosedLoopRuleFunction.apply(loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise, model,
+    plant_model, fuzzy_rule)``: ``ClosedLoopModelFunction`` for a loop built with a ``FuzzyRule``, with the rule's
+    parameters as an input: fuzzy_rule is a float64 (7,) tensor theta on the CPU or on a device (one host read).  The
+    forward applies it with ``loop.set_fuzzy_rule`` (the rule's settings w_min, w_max, v_rev stay the loop's) when it
+    differs from the current values, and it stays applied; the backward returns dL/dtheta summed over B on the
+    tensor's device.  wq_wr must be None: the weights come from the rule."""
+
+    @staticmethod
+    def forward(ctx, loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise, model, plant_model, fuzzy_rule):
+        if loop.rule is None:
+            raise ValueError("fuzzy_rule= needs a loop built with ClosedLoop(..., fuzzy_rule=FuzzyRule(...))")
+        vals = _theta(fuzzy_rule)
+        if vals != loop.rule.theta():
+            loop.set_fuzzy_rule(loop.rule.with_theta(vals))
+        vs = None if model is None else _geometry("model", model)
+        vp = None if plant_model is None else _geometry("plant_model", plant_model)
+        loop.set_model(solver=None if vs is None or vs == loop.solver.model() else vs,
+                       plant=None if vp is None or vp == loop.plant_model() else vp)
+        ctx.like = tuple(None if t is None else t.device for t in (model, plant_model, fuzzy_rule))
+        return _loop_forward(ctx, loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise)
+
+    @staticmethod
+    def backward(ctx, grad_S, grad_Ua, _grad_status):
+        need = ctx.needs_input_grad
+        grads, g = _loop_backward(ctx, grad_S, grad_Ua, need[7] or need[8], need[9])
+        extra = [None, None, None]
+        if g is not None:
+            for i, key in enumerate(("g_model_solver", "g_model_plant", "g_fuzzy_rule")):
+                if need[7 + i]:
+                    extra[i] = _batch_sum(g[key], ctx.like[i])
+        return (*grads, *extra)
+
+
+class FuzzyWeightsFunction(torch.autograd.Function):
+    """``wq_wr = FuzzyWeightsFunction.apply(x, xref, theta, rule)``: the fuzzy weight rule alone, for the one-solve
+    case.  x (B,6) the measured states, xref (B,N+1,6) the windows: float64 CUDA tensors; theta: float64 (7,), CPU or
+    device; rule: a ``FuzzyRule`` whose settings (w_min, w_max, v_rev) are used, or None for the reference's.  wq_wr
+    (B,8) is differentiable with respect to x (only the hitch angle x[:, 3] carries a gradient) and theta (summed over
+    B, on theta's device); xref only switches and gets none.  Forward tt_fuzzy_weights_rule_device, backward
+    tt_fuzzy_weights_vjp_device, both on the current stream."""
+
+    @staticmethod
+    def forward(ctx, x, xref, theta, rule):
+        from . import simulation as sim
+        B = x.shape[0]
+        x = _check("x", x, (B, 6))
+        if xref.dim() != 3:
+            raise ValueError("xref must be (B, N+1, 6)")
+        xref = _check("xref", xref, (B, xref.shape[1], 6))
+        ctx.rule = (rule or sim.FuzzyRule()).with_theta(_theta(theta))
+        ctx.like = theta.device
+        ctx.save_for_backward(x, xref)
+        return sim.fuzzy_weights_rule(x, xref, ctx.rule)
+
+    @staticmethod
+    def backward(ctx, grad_w):
+        from . import simulation as sim
+        x, xref = ctx.saved_tensors
+        g_x, g_rule = sim.fuzzy_weights_vjp(x, xref, grad_w.to(torch.float64).contiguous(), ctx.rule)
+        need = ctx.needs_input_grad
+        return g_x if need[0] else None, None, _batch_sum(g_rule, ctx.like) if need[2] else None, None
+
+
+def fuzzy_weights(x, xref, theta, rule=None):
+    """``FuzzyWeightsFunction.apply``: the weights (B,8) of a ``DifferentiableTracking`` solve from the measured state,
+    the window and the rule parameters theta (7,)."""
+    return FuzzyWeightsFunction.apply(x, xref, theta, rule)
+
+
 class DifferentiableClosedLoop:
     """``S, Ua, status = layer(x_init, T_sim, wq_wr=None, plan_x=None, plan_u=None, noise=None, model=None,
-    plant_model=None)``.
+    plant_model=None, fuzzy_rule=None)``.
 
     A thin callable over ``ClosedLoopFunction`` for one ``ClosedLoop`` whose solver is TT_VARIANT_TRACK or
     TT_VARIANT_NMPC (any of the three failure policies, warm start on or off, measurement or in-plant noise, shared or
-    per-instance plan).  A TT_VARIANT_FUZZY solver and a switch solver raise ValueError.  A plan given here replaces
+    per-instance plan), or any tracking variant with a ``FuzzyRule`` (ClosedLoop(..., fuzzy_rule=...)).  A
+    TT_VARIANT_FUZZY solver on the built-in rule and a switch solver raise ValueError.  A plan given here replaces
     the loop's.  The forward synchronises once at its end, as ``run`` does; the backward does not.  Zero gradient comes
     from: failed solves (whatever the policy then applies), stopped instances, variables sitting on a bound, and the
     warm start (z_guess does not move a converged solution).  With ``model`` and / or ``plant_model`` (float64 (3,)
     tensors (L1, L2, M), CPU or device) the controller's and the plant's geometry are inputs too:
-    ``ClosedLoopModelFunction``."""
+    ``ClosedLoopModelFunction``.  With ``fuzzy_rule`` (a float64 (7,) tensor theta, CPU or device) the parameters of the
+    loop's fuzzy rule are an input as well: ``ClosedLoopRuleFunction``."""
 
     def __init__(self, loop):
         loop._check_differentiable()
         self.loop = loop
 
-    def __call__(self, x_init, T_sim, wq_wr=None, plan_x=None, plan_u=None, noise=None, model=None, plant_model=None):
+    def __call__(self, x_init, T_sim, wq_wr=None, plan_x=None, plan_u=None, noise=None, model=None, plant_model=None,
+                 fuzzy_rule=None):
         """model, plant_model: float64 (3,) tensors (L1, L2, M) of the controller's and of the plant's geometry, or
-        None (as they are, no gradient)."""
+        None (as they are, no gradient).  fuzzy_rule: float64 (7,) tensor theta of the loop's ``FuzzyRule``, or None."""
+        if fuzzy_rule is not None:
+            return ClosedLoopRuleFunction.apply(self.loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise, model,
+                                                plant_model, fuzzy_rule)
         if model is None and plant_model is None:
             return ClosedLoopFunction.apply(self.loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise)
         return ClosedLoopModelFunction.apply(self.loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise, model,

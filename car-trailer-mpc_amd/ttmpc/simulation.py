@@ -19,17 +19,20 @@ reproduce a given draw, else it is drawn on the device with a seeded torch gener
 Reverse mode: ``ClosedLoop.run_tape`` keeps every step's solve on the device and ``ClosedLoop.backward`` sweeps that
 tape for the gradient of a loss on the visited states and applied controls with respect to x_init, the weights, the
 plan and the noise (tt_sim_vjp.hip around tt_vjp.hip; ``ttmpc.diff.DifferentiableClosedLoop`` is the autograd layer).
+A loop built with a ``FuzzyRule`` (the fuzzy weight rule with its constants as data, tt_fuzzy.hip) is differentiable
+with respect to the rule's parameters too.
 """
 from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import dataclasses
 import math
 
 import numpy as np
 import torch
 
-from ._lib import TT_ACCEPTABLE, TT_VARIANT_FUZZY, TTError, TTPlant, lib
+from ._lib import TT_ACCEPTABLE, TT_VARIANT_FUZZY, TTError, TTFuzzyRule, TTPlant, lib
 
 # closed-loop failure policies (include/ttmpc.h TT_POLICY_*): what a driver does after a failed solve
 POLICIES = {"track": 0, "nmpc": 1, "fuzzy": 2}
@@ -216,18 +219,85 @@ def window_vjp(g_xref, g_uref, k, Np, g_plan_x=None, g_plan_u=None, shared=False
     return g_plan_x, g_plan_u
 
 
+@dataclasses.dataclass(frozen=True)
+class FuzzyRule:
+    """tt_fuzzy_rule (include/ttmpc.h): the constants of the fuzzy weight rule (mpc_control_fuzzy.py:90-119), the
+    reference's by default.  The first seven fields are the differentiable vector theta; w_min, w_max and v_rev are
+    settings without a gradient."""
+    psi_full: float = 0.35
+    gain_hitch: float = 2.0
+    gain_steer: float = 1.2
+    gain_rate: float = 1.5
+    rev_hitch: float = 1.1
+    rev_steer: float = 1.1
+    rev_rate: float = 1.2
+    w_min: float = 1.0
+    w_max: float = 3.5
+    v_rev: float = -0.1
+
+    def __post_init__(self):
+        v = dataclasses.astuple(self)
+        if not (all(math.isfinite(float(t)) for t in v) and self.psi_full > 0 and self.w_min <= self.w_max):
+            raise ValueError(f"fuzzy rule: every value finite, psi_full > 0 and w_min <= w_max, got {self}")
+
+    def as_struct(self) -> TTFuzzyRule:
+        return TTFuzzyRule(*(float(t) for t in dataclasses.astuple(self)))
+
+    def theta(self):
+        """(psi_full, gain_hitch, gain_steer, gain_rate, rev_hitch, rev_steer, rev_rate)."""
+        return tuple(float(t) for t in dataclasses.astuple(self)[:7])
+
+    def with_theta(self, theta):
+        """This rule with other values of theta (7), the settings kept."""
+        theta = [float(t) for t in theta]
+        if len(theta) != 7:
+            raise ValueError("theta has seven entries")
+        return FuzzyRule(*theta, self.w_min, self.w_max, self.v_rev)
+
+
+def _rule_ref(rule):
+    return None if rule is None else C.byref(rule.as_struct())
+
+
+def fuzzy_weights_rule(x, xref, rule=None, wq_wr=None, stream=None):
+    """The fuzzy weights (B,8) of measured states x (B,6) and windows xref (B,N+1,6), device tensors, for a
+    ``FuzzyRule`` (tt_fuzzy_weights_rule_device; None: the reference's constants, bitwise tt_fuzzy_weights_device)."""
+    dev = x.device
+    B, N = x.shape[0], xref.shape[1] - 1
+    wq_wr = torch.empty((B, 8), dtype=torch.float64, device=dev) if wq_wr is None else wq_wr
+    _check(lib().tt_fuzzy_weights_rule_device(B, N, _rule_ref(rule), x.data_ptr(), xref.data_ptr(), wq_wr.data_ptr(),
+                                              _stream(stream, dev)), "tt_fuzzy_weights_rule_device")
+    return wq_wr
+
+
+def fuzzy_weights_vjp(x, xref, g_wq_wr, rule=None, retried=None, g_x=None, g_rule=None, stream=None):
+    """Adjoint of ``fuzzy_weights_rule`` (tt_fuzzy_weights_vjp_device): for the upstream g_wq_wr (B,8), g_x (B,6) gets
+    g_x[:, 3] += dL/dpsi and g_rule (B,7) += dL/dtheta per instance; both are accumulators, made of zeros when None.
+    retried (B,) int32 or None: instances whose accepted solve used unit weights add nothing.  -> (g_x, g_rule)."""
+    dev = x.device
+    B, N = x.shape[0], xref.shape[1] - 1
+    g_x = torch.zeros((B, 6), dtype=torch.float64, device=dev) if g_x is None else g_x
+    g_rule = torch.zeros((B, 7), dtype=torch.float64, device=dev) if g_rule is None else g_rule
+    _check(lib().tt_fuzzy_weights_vjp_device(B, N, _rule_ref(rule), x.data_ptr(), xref.data_ptr(), _ptr(retried),
+                                             g_wq_wr.data_ptr(), g_x.data_ptr(), g_rule.data_ptr(),
+                                             _stream(stream, dev)), "tt_fuzzy_weights_vjp_device")
+    return g_x, g_rule
+
+
 class LoopTape:
     """The device log of an eager run.  Every recorded run has the step indices ks and the logs S (K+1,B,6), Ua
     (K,B,2), status / iters / collide / active (K,B) (active: after each step).  ``ClosedLoop.run_tape`` also keeps
     what ``ClosedLoop.backward`` needs, None in a plain ``run``: consec (K,B), the consecutive-failure count after each
     step, each step's solve X (K,B,N+1,6), U (K,B,N,2), dual (K,B,N+1,22) and the noise it used (K,B,6) or None.
     wq_wr (B,8) or None are the run's weights, plan_x / plan_u the plan it saw, model_solver / model_plant the
-    (L1, L2, M) of the solver's handle and of the plant during a taped run."""
+    (L1, L2, M) of the solver's handle and of the plant during a taped run.  The taped run of a loop with a
+    ``FuzzyRule`` also keeps rule (that rule), W (K,B,8), the weights each step's accepted solve used (ones where the
+    unit-weight retry was taken), and retried (K,B) int32, where it was: 68 bytes per instance and step."""
     __slots__ = ("ks", "S", "Ua", "status", "iters", "collide", "active", "consec", "X", "U", "dual", "noise", "wq_wr",
-                 "plan_x", "plan_u", "model_solver", "model_plant")
+                 "plan_x", "plan_u", "model_solver", "model_plant", "W", "retried", "rule")
     # (log field, the loop's buffer a step leaves it in), in the order record() copies them; the solve writes dual
     STEP = (("S", "state"), ("Ua", "u_applied"), ("status", "st"), ("iters", "it"), ("collide", "flag"),
-            ("active", "active"), ("consec", "consec"), ("X", "X"), ("U", "U"))
+            ("active", "active"), ("consec", "consec"), ("X", "X"), ("U", "U"), ("W", "wq"), ("retried", "retried"))
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -246,6 +316,8 @@ class LoopTape:
             log.consec = new(K, B, dtype=torch.int32)
             log.X, log.U, log.dual = new(K, B, N + 1, 6), new(K, B, N, 2), new(K, B, N + 1, 22)
             log.model_solver, log.model_plant = loop.solver.model(), loop.plant_model()   # (run_tape: a BatchSolver)
+            if loop.rule is not None:
+                log.W, log.retried, log.rule = new(K, B, 8), new(K, B, dtype=torch.int32), loop.rule
         return log
 
     def record(self, j, loop):
@@ -293,6 +365,12 @@ class ClosedLoop:
       (tt_fuzzy_weights_device, mpc_control_fuzzy.py:90-119) and its failed instances are re-solved once
       with unit weights from the same guess (145-159).
 
+    fuzzy_rule: None, or a ``FuzzyRule``: the weight rule with its constants as data (tt_fuzzy_weights_rule_device),
+      for a solver of any tracking variant (TT_VARIANT_TRACK, _NMPC, _FUZZY), with the unit-weight retry.  Such a loop
+      is differentiable (``run_tape`` / ``backward``, also with respect to the rule's parameters); policy and
+      noise_in_plant still default from the solver's variant.  None keeps a TT_VARIANT_FUZZY solver on the built-in
+      rule, which is not differentiable.
+
     noise_in_plant=True is the NMPC / fuzzy drivers' disturbance model (simulation_nmpc.py:94-105,
     simulation_fuzzy.py): the solver sees the exact state and, with disturbances on, the process noise
     N(0, process_noise_std) enters the plant as q_ += noise * dt (tt_policy_plant_noise_device); the default is
@@ -301,7 +379,7 @@ class ClosedLoop:
 
     def __init__(self, solver, plan_x, plan_u, params, disturbance_params=None, measurement_noise=None,
                  obstacles=None, check_collision=True, switch_solver=None, warm_start=False, bug_compatible=True,
-                 zero_on_fail=False, device=None, seed=0, policy=None, noise_in_plant=None):
+                 zero_on_fail=False, device=None, seed=0, policy=None, noise_in_plant=None, fuzzy_rule=None):
         self.solver = solver
         self.N = solver.N
         self.dev = torch.device("cuda", solver.device if device is None else device)
@@ -318,9 +396,10 @@ class ClosedLoop:
         self.check_collision = check_collision and self.obstacles is not None
         self.switch = switch_solver
         self.warm, self.bug_compatible, self.zero_on_fail = warm_start, bug_compatible, zero_on_fail
-        self.fuzzy = getattr(solver, "variant", None) == TT_VARIANT_FUZZY
+        self._fuzzy_variant = getattr(solver, "variant", None) == TT_VARIANT_FUZZY
+        self.set_fuzzy_rule(fuzzy_rule)
         if policy is None:
-            policy = "fuzzy" if self.fuzzy else ("nmpc" if zero_on_fail else "track")
+            policy = "fuzzy" if self._fuzzy_variant else ("nmpc" if zero_on_fail else "track")
         if policy not in POLICIES:
             raise ValueError(f"policy must be one of {sorted(POLICIES)}")
         self.policy = policy
@@ -351,6 +430,15 @@ class ClosedLoop:
                 raise ValueError("plant geometry: L1, L2 must be > 0 and M finite")
             self.params.update(L1=L1, L2=L2, M=M)
 
+    def set_fuzzy_rule(self, rule):
+        """The ``FuzzyRule`` of the steps and runs from now on (None: the built-in rule for a TT_VARIANT_FUZZY solver,
+        no rule for another).  Host-side state only.  A tape keeps the rule of its run; ``backward`` on a tape made
+        with another raises."""
+        if rule is not None and not isinstance(rule, FuzzyRule):
+            raise TypeError("fuzzy_rule must be a ttmpc.simulation.FuzzyRule or None")
+        self.rule = rule
+        self.fuzzy = self._fuzzy_variant or rule is not None   # per-step weights and the unit-weight retry
+
     def _alloc(self, B):
         N, d, f = self.N, self.dev, torch.float64
         self.B = B
@@ -370,8 +458,8 @@ class ClosedLoop:
         self.consec = torch.zeros(B, dtype=torch.int32, device=d)
         self.fails = torch.zeros(B, dtype=torch.int32, device=d)
         self.active = torch.ones(B, dtype=torch.int32, device=d)
-        if self.fuzzy:
-            self.wq = torch.empty((B, 8), dtype=f, device=d)
+        self.wq = torch.empty((B, 8), dtype=f, device=d)          # the fuzzy weights of a step
+        self.retried = torch.empty(B, dtype=torch.int32, device=d)  # taped fuzzy steps: took the unit-weight retry
         if self.warm:
             self.zg = torch.empty((B, 8 * N + 6), dtype=f, device=d)
             self.last = torch.zeros((B, 8 * N + 6), dtype=f, device=d)
@@ -440,7 +528,12 @@ class ClosedLoop:
                    "tt_warm_start_device")
             zg = self.zg.data_ptr()
         wq = 0
-        if self.fuzzy:
+        if self.rule is not None:
+            _check(L.tt_fuzzy_weights_rule_device(B, N, _rule_ref(self.rule), self.x_meas.data_ptr(),
+                                                  self.xref.data_ptr(), self.wq.data_ptr(), sp),
+                   "tt_fuzzy_weights_rule_device")
+            wq = self.wq.data_ptr()
+        elif self.fuzzy:
             _check(L.tt_fuzzy_weights_device(B, N, self.x_meas.data_ptr(), self.xref.data_ptr(), self.wq.data_ptr(),
                                              sp), "tt_fuzzy_weights_device")
             wq = self.wq.data_ptr()
@@ -452,7 +545,7 @@ class ClosedLoop:
         else:
             self.solver.solve_ex_device(B, *io, wq_wr=wq, z_guess=zg, dual=dual.data_ptr(), stream=s.cuda_stream)
         if self.fuzzy:
-            self._fuzzy_retry(s)
+            self._fuzzy_retry(s, dual)
         if self.switch is not None and self.check_collision:
             self._switch_solve(s)
         if self.warm:
@@ -475,16 +568,26 @@ class ClosedLoop:
                                                   self.active.data_ptr(), sn, self.u_applied.data_ptr(), sp),
                "tt_policy_plant_noise_device")
 
-    def _fuzzy_retry(self, s):
-        """mpc_control_fuzzy.py:145-159: failed instances re-solve once with unit weights, same guess."""
+    def _fuzzy_retry(self, s, dual=None):
+        """mpc_control_fuzzy.py:145-159: failed instances re-solve once with unit weights, same guess.  dual (a taped
+        step): the retry exports its multipliers too, and the step leaves in ``retried`` / ``wq`` which instances took
+        it and the weights every accepted solve used."""
         idx = torch.nonzero((self.st > TT_ACCEPTABLE) & (self.active != 0), as_tuple=True)[0]
 
-        def solve(n, *io):
+        def solve(n, *io, dual=0):
             w = torch.ones((n, 8), dtype=torch.float64, device=self.dev)
             zg = self.zg[idx].contiguous() if self.warm else None
-            self.solver.solve_device(n, *io, wq_wr=w.data_ptr(), z_guess=0 if zg is None else zg.data_ptr(),
-                                     stream=s.cuda_stream)
-        self._resolve(idx, solve)
+            kw = dict(wq_wr=w.data_ptr(), z_guess=0 if zg is None else zg.data_ptr(), stream=s.cuda_stream)
+            if dual:
+                self.solver.solve_ex_device(n, *io, dual=dual, **kw)
+            else:
+                self.solver.solve_device(n, *io, **kw)
+        self._resolve(idx, solve, dual)
+        if dual is not None:
+            self.retried.zero_()
+            if idx.numel():
+                self.retried[idx] = 1
+                self.wq[idx] = 1.0
 
     def _switch_solve(self, s):
         """USE_SWITCH_MPC: instances whose check collided use MPCTrackingControlObs (simulation.py:506-512)."""
@@ -492,10 +595,11 @@ class ClosedLoop:
                       lambda n, x0, xr, ur, X, U, st, it, kk: self.switch.solve_device(
                           n, x0, 0, xr, ur, 0, X, U, 0, st, it, kk, stream=s.cuda_stream))
 
-    def _resolve(self, idx, solve):
+    def _resolve(self, idx, solve, dual=None):
         """Solve the instances idx again as a compacted batch and put the results in their places: gathers x_meas,
         xref, uref, calls solve(n, x0, xref, uref, X, U, status, iters, kkt) with device pointers of n-instance buffers
-        (it launches on the loop's stream, which is current), scatters the five outputs back."""
+        (it launches on the loop's stream, which is current), scatters the five outputs back.  dual (B,N+1,22), the
+        step's multipliers of a taped run: solve also gets dual=<pointer of an (n,N+1,22) buffer>, scattered likewise."""
         n = int(idx.numel())          # host sync: the compaction size decides the launch
         if n == 0:
             return
@@ -503,7 +607,12 @@ class ClosedLoop:
         new = lambda *sh, dtype=torch.float64: torch.empty(sh, dtype=dtype, device=self.dev)  # noqa: E731
         x0, xr, ur = self.x_meas[idx].contiguous(), self.xref[idx].contiguous(), self.uref[idx].contiguous()
         X, U, st, it, kk = new(n, N + 1, 6), new(n, N, 2), new(n, dtype=torch.int32), new(n, dtype=torch.int32), new(n)
-        solve(n, *(t.data_ptr() for t in (x0, xr, ur, X, U, st, it, kk)))
+        if dual is None:
+            solve(n, *(t.data_ptr() for t in (x0, xr, ur, X, U, st, it, kk)))
+        else:
+            D = new(n, N + 1, 22)
+            solve(n, *(t.data_ptr() for t in (x0, xr, ur, X, U, st, it, kk)), dual=D.data_ptr())
+            dual[idx] = D
         self.X[idx], self.U[idx], self.st[idx], self.it[idx], self.kkt[idx] = X, U, st, it, kk
 
     # ---------------- hipGraph replay of the closed loop ----------------
@@ -621,9 +730,10 @@ class ClosedLoop:
 
     # ---------------- reverse mode: taped run and backward sweep ----------------
     def _check_differentiable(self):
-        if self.fuzzy:
-            raise ValueError("the closed loop of a TT_VARIANT_FUZZY solver is not differentiable here: its weights "
-                             "depend on the measured state and its retry compacts the failed instances on the host")
+        if self.fuzzy and self.rule is None:
+            raise ValueError("the closed loop of a TT_VARIANT_FUZZY solver on the built-in weight rule is not "
+                             "differentiable: give the rule as data, ClosedLoop(..., fuzzy_rule=FuzzyRule()), whose "
+                             "adjoint and taped retry exist")
         if self.switch is not None:
             raise ValueError("the closed loop with a switch solver is not differentiable: the OBCA solve has no adjoint")
 
@@ -631,14 +741,18 @@ class ClosedLoop:
         """``run`` that also keeps what ``backward`` needs: the same steps with the solve's multipliers exported
         (solve_ex_device: bitwise the plain solve) and each step's X, U, dual copied to a ``LoopTape`` on the device,
         (30 (N+1) - 2) * 8 bytes per instance and step.  wq_wr: constant per-instance weights (B,8), host or device.
-        Returns run()'s dict plus "tape".  Solver variants TT_VARIANT_TRACK and TT_VARIANT_NMPC; no switch solver."""
+        Returns run()'s dict plus "tape".  Solver variants TT_VARIANT_TRACK and TT_VARIANT_NMPC, or any tracking
+        variant with a ``FuzzyRule`` (then the weights come from the rule and wq_wr must be None; the unit-weight retry
+        exports its multipliers into the step's dual, and the tape keeps W and retried); no switch solver."""
         self._check_differentiable()
+        if self.rule is not None and wq_wr is not None:
+            raise ValueError("a loop with a fuzzy_rule takes its weights from the rule: wq_wr must be None")
         tape, drawn = self._begin(x_init, T_sim, noise, wq_wr, taped=True)
         self._steps(tape, drawn)
         torch.cuda.synchronize(self.dev)
         return dict(self._policy_logs(), **tape.result(), tape=tape)
 
-    def backward(self, tape, GS, GU, model=False):
+    def backward(self, tape, GS, GU, model=False, rule=False):
         """The adjoint of a taped run for a scalar loss L(S, Ua): GS = dL/dS (K+1,B,6), GU = dL/dUa (K,B,2), float64
         device tensors.  Per step, backwards: tt_policy_plant_vjp_device, the step's window again,
         tt_track_vjp_device on the taped solve, tt_sim_window_vjp_device (include/ttmpc.h, "Reverse mode of the closed
@@ -648,8 +762,20 @@ class ClosedLoop:
         noise_in_plant of the plant's process noise; zeros where the run had no noise).  model=True adds g_model_solver
         and g_model_plant (B,3): dL/d(L1, L2, M) per instance of the geometry the controller believes and of the
         plant's; the step stays four launches (the model instantiations of the plant and solve adjoints, the solve's
-        term accumulated in place).  Raises if the solver's or the plant's geometry is no longer that of the tape."""
+        term accumulated in place).  Raises if the solver's or the plant's geometry is no longer that of the tape.
+        The tape of a loop with a ``FuzzyRule``: each step's weights were w_t = rule(x_meas_t, xref_t[0]), so the window
+        launch also rebuilds x_meas_t, the solve adjoint runs at tape.W[t], and the fourth launch is
+        tt_sim_window_vjp_fuzzy_device, which sends the solve's dL/dw_t through the rule's adjoint into the state
+        adjoint (and the measurement-noise gradient) unless the step took the unit-weight retry: still four launches.
+        g_wq_wr is then the sum over the steps of dL/dW_t, the gradient for a constant offset added to every step's
+        weights.  rule=True adds g_fuzzy_rule (B,7): dL/dtheta per instance.  Raises if the loop's rule is no longer the
+        tape's."""
         self._check_differentiable()
+        if tape.rule != self.rule:
+            raise ValueError(f"the fuzzy rule changed since the tape was made: {tape.rule} -> {self.rule}; run the tape "
+                             "again, or set the rule back before the backward")
+        if rule and tape.rule is None:
+            raise ValueError("rule=True needs the tape of a loop with a fuzzy_rule")
         if tape.model_solver is not None and (tape.model_solver != self.solver.model() or
                                               tape.model_plant != self.plant_model()):
             raise ValueError(f"the geometry changed since the tape was made: solver {tape.model_solver} -> "
@@ -669,6 +795,10 @@ class ClosedLoop:
         xref, uref = z(B, N + 1, 6), z(B, N, 2)
         g_x0, g_xr, g_ur, g_ws = z(B, 6), z(B, N + 1, 6), z(B, N, 2), z(B, 8)
         g_ms, g_mp = (z(B, 3), z(B, 3)) if model else (None, None)
+        fz = tape.rule is not None
+        g_th = z(B, 7) if rule else None
+        x_meas = z(B, 6) if fz else None
+        rs = _rule_ref(tape.rule)
         in_plant = self.noise_in_plant and tape.noise is not None
         meas = self.measurement_noise and tape.noise is not None
         # the raw entries, not the module-level wrappers: a backward step is four short launches the host only just
@@ -676,6 +806,13 @@ class ClosedLoop:
         L, p, sp = lib(), plant(self.params, self.dist), C.c_void_p(s.cuda_stream)
         per = int(tape.plan_x.shape[0] != 1)
         wq = 0 if tape.wq_wr is None else tape.wq_wr.data_ptr()
+        if fz:
+            # the rule's four extra per-step addresses by offset: a tape slice made on the host costs it more than the
+            # launch it feeds, and the host only just keeps ahead of a backward step
+            if not all(t.is_contiguous() for t in (tape.S, tape.W, tape.retried) + ((tape.noise,) if meas else ())):
+                raise ValueError("the tape's S, W, retried and noise must be contiguous")
+            S0, W0, R0 = tape.S.data_ptr(), tape.W.data_ptr(), tape.retried.data_ptr()
+            N0 = tape.noise.data_ptr() if meas else None
         s.wait_stream(torch.cuda.current_stream(d))
         for t in range(K - 1, -1, -1):
             pp = (B, N, C.byref(p), POLICIES[self.policy], tape.S[t].data_ptr(), tape.status[t].data_ptr(),
@@ -687,17 +824,25 @@ class ClosedLoop:
             else:
                 _check(L.tt_policy_plant_vjp_device(*pp, sp), "tt_policy_plant_vjp_device")
             _check(L.tt_sim_window_device(B, N, int(tape.ks[t]), int(Np), tape.plan_x.data_ptr(),
-                                          tape.plan_u.data_ptr(), per, None, None, None, xref.data_ptr(),
-                                          uref.data_ptr(), sp), "tt_sim_window_device")
+                                          tape.plan_u.data_ptr(), per, S0 + t * B * 48 if fz else None,
+                                          N0 + t * B * 48 if fz and meas else None, _ptr(x_meas), xref.data_ptr(),
+                                          uref.data_ptr(), sp),
+                   "tt_sim_window_device")
             self.solver.vjp_device(B, tape.X[t].data_ptr(), tape.U[t].data_ptr(), tape.dual[t].data_ptr(),
                                    xref.data_ptr(), uref.data_ptr(), tape.status[t].data_ptr(), grad_u=gU.data_ptr(),
                                    g_x0=g_x0.data_ptr(), g_xref=g_xr.data_ptr(), g_uref=g_ur.data_ptr(),
-                                   g_wq_wr=g_ws.data_ptr(), wq_wr=wq, stream=s.cuda_stream,
+                                   g_wq_wr=g_ws.data_ptr(), wq_wr=W0 + t * B * 64 if fz else wq,
+                                   stream=s.cuda_stream,
                                    g_model=g_ms.data_ptr() if model else 0, accumulate=True)
-            _check(L.tt_sim_window_vjp_device(B, N, int(tape.ks[t]), int(Np), g_xr.data_ptr(), g_ur.data_ptr(),
-                                              g_px.data_ptr(), g_pu.data_ptr(), g_x0.data_ptr(), GS[t].data_ptr(),
-                                              a.data_ptr(), g_ws.data_ptr(), g_w.data_ptr(),
-                                              g_n[t].data_ptr() if meas else None, sp), "tt_sim_window_vjp_device")
+            wv = (B, N, int(tape.ks[t]), int(Np), g_xr.data_ptr(), g_ur.data_ptr(), g_px.data_ptr(), g_pu.data_ptr(),
+                  g_x0.data_ptr(), GS[t].data_ptr(), a.data_ptr(), g_ws.data_ptr(), g_w.data_ptr(),
+                  g_n[t].data_ptr() if meas else None)
+            if fz:
+                _check(L.tt_sim_window_vjp_fuzzy_device(*wv, rs, x_meas.data_ptr(), xref.data_ptr(),
+                                                        R0 + t * B * 4, _ptr(g_th), sp),
+                       "tt_sim_window_vjp_fuzzy_device")
+            else:
+                _check(L.tt_sim_window_vjp_device(*wv, sp), "tt_sim_window_vjp_device")
         with torch.cuda.stream(s):
             if not per:
                 g_px, g_pu = g_px.sum(dim=0, keepdim=True), g_pu.sum(dim=0, keepdim=True)
@@ -705,6 +850,8 @@ class ClosedLoop:
         out = {"g_x_init": a, "g_wq_wr": g_w, "g_plan_x": g_px, "g_plan_u": g_pu, "g_noise": g_n}
         if model:
             out.update(g_model_solver=g_ms, g_model_plant=g_mp)
+        if rule:
+            out["g_fuzzy_rule"] = g_th
         return out
 
     def _policy_logs(self):

@@ -362,6 +362,8 @@ int tt_interpolate_device(int B, int Np, int factor, const double* state_traj, c
  *     tt_track_vjp_device          on step t's taped x, u, dual, status with grad_x = NULL, grad_u = the buffer
  *                                  whose row 0 holds g_u0 (rows 1.. zeroed once by the caller)
  *     tt_sim_window_vjp_device     a += g_x0 + GS[t], weight and plan gradients accumulated
+ *       (a rule loop: tt_sim_window_vjp_fuzzy_device, which first sends the solve's g_wq_wr through the adjoint of
+ *        the fuzzy weight rule into g_x0[3] and the rule parameters; the window call before it also rebuilds x_meas)
  * and dL/dx_init = a at the end.  Device pointers, asynchronous on `stream`, no atomics: two sweeps over one
  * tape give the same bits.  Both calls return -EINVAL for B <= 0 or N outside 1..tt_max_horizon().
  *
@@ -413,6 +415,55 @@ int tt_policy_plant_vjp_model_device(int B, int N, const tt_plant* p, int policy
                                      const int* consecutive, const double* grad_u_applied, double* adj_state,
                                      double* adj_u_last, double* grad_u, double* g_state_noise, double* g_model_acc,
                                      void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The fuzzy weight rule as data, and its adjoint.  tt_fuzzy_weights_device evaluates the rule of
+ * mpc_control_fuzzy.py:90-119 with the reference's constants; here they are a struct, so that a closed loop can be
+ * differentiated with respect to them (ttmpc.simulation.ClosedLoop(fuzzy_rule=...), backward(rule=True)).
+ * The first seven fields, in this order, are the differentiable rule vector theta; w_min, w_max and v_rev are
+ * settings without a gradient (at the defaults the clip bounds sit on a kink, and v_rev is a switch).
+ * With psi = x[3], v = x[5], ref_v = xref[0][5], for one instance:
+ *     s = |psi| / psi_full,  h = min(s, 1),  rev = (ref_v < v_rev) or (v < v_rev)
+ *     per channel c in {hitch, steer, rate}:  f_c = rev ? rev_c : 1,  raw_c = (1 + gain_c h) f_c,
+ *                                             m_c = max(1.0, raw_c),  w_c = min(max(m_c, w_min), w_max)
+ *     wq_wr = (1, 1, w_steer, w_hitch, w_steer, 1, 1, w_rate)
+ * Adjoint, for the upstream g_w [8]: G_steer = g_w[2] + g_w[4], G_hitch = g_w[3], G_rate = g_w[7],
+ * pass_c = (raw_c > 1) and (w_min < m_c < w_max), in = (s < 1), d|x|/dx = sign(x) with 0 at 0:
+ *     g_psi      = sum_c G_c pass_c gain_c f_c in sign(psi) / psi_full
+ *     g_psi_full = -sum_c G_c pass_c gain_c f_c in |psi| / psi_full^2
+ *     g_gain_c   = G_c pass_c h f_c
+ *     g_rev_c    = G_c pass_c (rev ? 1 + gain_c h : 0)
+ * and zero for every other input: v and ref_v only switch, the constant channels carry nothing.  The adjoint is
+ * plain IEEE arithmetic without contraction, as the plant adjoint; no atomics.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct { double psi_full;                          /* 0.35 */
+                 double gain_hitch, gain_steer, gain_rate; /* 2.0, 1.2, 1.5 */
+                 double rev_hitch, rev_steer, rev_rate;    /* 1.1, 1.1, 1.2 */
+                 double w_min, w_max, v_rev;               /* 1.0, 3.5, -0.1: no gradient */ } tt_fuzzy_rule;
+/* tt_fuzzy_weights_device for a rule; rule == NULL means the defaults, and with the defaults the weights are
+ * bitwise those of tt_fuzzy_weights_device. */
+int tt_fuzzy_weights_rule_device(int B, int N, const tt_fuzzy_rule* rule, const double* x, const double* xref,
+                                 double* wq_wr, void* stream);
+/* The rule's adjoint alone, one instance per thread: g_x [B][6] gets g_x[b][3] += g_psi, g_rule_acc [B][7] += the
+ * theta gradients (an accumulator the caller zeroes).  retried [B] (may be NULL: none): an instance with
+ * retried[b] != 0 adds nothing, because its accepted solve used unit weights.  Any pointer may be NULL (that part is
+ * skipped). */
+int tt_fuzzy_weights_vjp_device(int B, int N, const tt_fuzzy_rule* rule, const double* x, const double* xref,
+                                const int* retried, const double* g_wq_wr, double* g_x, double* g_rule_acc,
+                                void* stream);
+/* tt_sim_window_vjp_device for a step whose weights came from the rule, w_t = rule(x_meas_t, xref_t[0]): the thread
+ * that does the per-instance accumulation first applies the rule adjoint to g_x0 (as it reads it; the buffer itself is
+ * not written), then accumulates, so adj_state and g_meas_noise receive the rule's term and g_rule_acc [B][7] the
+ * theta gradients, and a backward step stays four launches.  Bitwise "tt_fuzzy_weights_vjp_device on g_x0, then
+ * tt_sim_window_vjp_device".  The rule part needs g_x0 and g_wq_wr; x_meas [B][6] and xref [B][N+1][6] are the step's.
+ * rule == NULL is tt_sim_window_vjp_device: the same kernel and bits.
+ * All three return -EINVAL for B <= 0, N outside 1..tt_max_horizon(), a non-finite rule, psi_full <= 0 or
+ * w_min > w_max. */
+int tt_sim_window_vjp_fuzzy_device(int B, int N, int k, int Np, const double* g_xref, const double* g_uref,
+                                   double* g_plan_x, double* g_plan_u, const double* g_x0, const double* grad_state,
+                                   double* adj_state, const double* g_wq_wr, double* g_wq_wr_acc, double* g_meas_noise,
+                                   const tt_fuzzy_rule* rule, const double* x_meas, const double* xref,
+                                   const int* retried, double* g_rule_acc, void* stream);
 
 /* lqr_distance (LQR_cost.py:7-41) for B instances: A, B of the forward-Euler map at (x_goal, u_goal),
  * P = DARE(A, B, Q, R) symmetrised, score[b] = (x_cur - x_goal)' P (x_cur - x_goal).  Q (6x6), R (2x2) are

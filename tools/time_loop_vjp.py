@@ -7,8 +7,11 @@ B starts around the plan's start) without the collision check.  After a warm-up 
   * the K steps of ClosedLoop.run_tape   (step with multiplier export + the tape copies),
   * the K steps of ClosedLoop.run        (plain step + the log copies),
   * ClosedLoop.backward on the tape just made,
-each between two device events on the stream it runs on, with no host synchronisation inside.  Prints the median and the
-min..max over the rounds in microseconds per step, the ratio taped / plain, and one JSON line.
+and the same three for a rule loop: the same solver variant, plan, noise and starts with
+ClosedLoop(..., fuzzy_rule=FuzzyRule()), whose weights come from the fuzzy rule each step and whose backward step ends
+in the fused window + rule adjoint (its taped forward step also has the retry's host compaction and two more copies);
+each between two device events on the stream it runs on, with no host synchronisation inside the backward.  Prints the
+median and the min..max over the rounds in microseconds per step, the ratio taped / plain, and one JSON line.
 """
 import argparse
 import json
@@ -52,6 +55,8 @@ def main():
     GU = torch.from_numpy(rng.uniform(-1, 1, (K, B, 2))).to(dev)
     solver = ttmpc.BatchSolver(N, params, sc.MPC_Q, sc.MPC_R, sc.XLB, sc.XUB, sc.ULB, sc.UUB)
     cl = sim.ClosedLoop(solver, S, U, params, sim.DISTURBANCE_PARAMS)
+    rule_solver = ttmpc.BatchSolver(N, params, sc.MPC_Q, sc.MPC_R, sc.XLB, sc.XUB, sc.ULB, sc.UUB)
+    rl = sim.ClosedLoop(rule_solver, S, U, params, sim.DISTURBANCE_PARAMS, fuzzy_rule=sim.FuzzyRule())
 
     def timed(stream, fn):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -61,35 +66,50 @@ def main():
         e1.synchronize()
         return 1e3 * e0.elapsed_time(e1) / K, out
 
-    def forward(taped):
-        """run_tape()'s / run()'s steps (step + the nine / six log copies) without the host copies at the end."""
-        log, drawn = cl._begin(x0, T, noise, w, taped=taped)
-        us, _ = timed(cl.stream, lambda: cl._steps(log, drawn))
+    def forward(taped, loop=cl):
+        """run_tape()'s / run()'s steps (step + the nine / six log copies; a rule loop: eleven) without the host copies
+        at the end."""
+        log, drawn = loop._begin(x0, T, noise, w if loop.rule is None else None, taped=taped)
+        us, _ = timed(loop.stream, lambda: loop._steps(log, drawn))
         return us, log
 
-    def backward(tape):
-        return timed(torch.cuda.current_stream(dev), lambda: cl.backward(tape, GS, GU))
+    def backward(tape, loop=cl):
+        return timed(torch.cuda.current_stream(dev), lambda: loop.backward(tape, GS, GU, rule=loop.rule is not None))
 
     _, tape = forward(True)
     forward(False)
     _, grads = backward(tape)
+    _, rtape = forward(True, rl)
+    forward(False, rl)
+    _, rgrads = backward(rtape, rl)
     torch.cuda.synchronize()
-    ok = int((tape.status <= 1).sum())
-    times = {"taped forward step": [], "plain forward step": [], "backward step": []}
+    ok, rok, retried = int((tape.status <= 1).sum()), int((rtape.status <= 1).sum()), int(rtape.retried.sum())
+    times = {"taped forward step": [], "plain forward step": [], "backward step": [],
+             "rule loop: taped forward step": [], "rule loop: plain forward step": [], "rule loop: backward step": []}
     for _ in range(args.rounds):
         us, tape = forward(True)
         times["taped forward step"].append(us)
         times["plain forward step"].append(forward(False)[0])
         times["backward step"].append(backward(tape)[0])
-    assert bool(torch.isfinite(grads["g_x_init"]).all())
-    print(f"B = {B}, N = {N}, K = {K} ({ok} of {K * B} solves succeeded), {args.rounds} rounds, us per step; tape "
-          f"{tape.nbytes() / 2**20:.1f} MiB:")
+        us, rtape = forward(True, rl)
+        times["rule loop: taped forward step"].append(us)
+        times["rule loop: plain forward step"].append(forward(False, rl)[0])
+        times["rule loop: backward step"].append(backward(rtape, rl)[0])
+    assert bool(torch.isfinite(grads["g_x_init"]).all()) and bool(torch.isfinite(rgrads["g_fuzzy_rule"]).all())
+    print(f"B = {B}, N = {N}, K = {K} ({ok} of {K * B} solves succeeded; rule loop {rok}, {retried} retried), "
+          f"{args.rounds} rounds, us per step; tape {tape.nbytes() / 2**20:.1f} MiB, rule loop "
+          f"{rtape.nbytes() / 2**20:.1f} MiB:")
     for k, v in times.items():
-        print(f"  {k:20s} median {statistics.median(v):8.2f}   min {min(v):8.2f}   max {max(v):8.2f}")
+        print(f"  {k:30s} median {statistics.median(v):8.2f}   min {min(v):8.2f}   max {max(v):8.2f}")
     ratio = statistics.median(times["taped forward step"]) / statistics.median(times["plain forward step"])
     print(f"  taped / plain {ratio:.3f}")
     result = {k: {"median_us": statistics.median(v), "min_us": min(v), "max_us": max(v)} for k, v in times.items()}
     result["taped_over_plain"] = ratio
+    rratio = (statistics.median(times["rule loop: taped forward step"]) /
+              statistics.median(times["rule loop: plain forward step"]))
+    bratio = statistics.median(times["rule loop: backward step"]) / statistics.median(times["backward step"])
+    print(f"  rule loop: taped / plain {rratio:.3f}, backward step rule / plain {bratio:.3f}")
+    result["rule_taped_over_plain"], result["rule_backward_over_plain_backward"] = rratio, bratio
 
     # the four launches of a backward step on their own: 200 back-to-back launches each, median of the rounds
     import ctypes as C
@@ -101,6 +121,7 @@ def main():
     gpx, gpu_ = z(B, Np + 1, 6), z(B, Np, 2)
     t, L = K // 2, ttmpc.lib()
     pl, sp = sim.plant(params, sim.DISTURBANCE_PARAMS), C.c_void_p(cur.cuda_stream)
+    rstruct, gth = sim.FuzzyRule().as_struct(), z(B, 7)
     parts = {
         "policy_plant_vjp_kernel": lambda: L.tt_policy_plant_vjp_device(
             B, N, C.byref(pl), 0, tape.S[t].data_ptr(), tape.status[t].data_ptr(), tape.active[t - 1].data_ptr(),
@@ -116,6 +137,10 @@ def main():
         "sim_window_vjp_kernel": lambda: L.tt_sim_window_vjp_device(
             B, N, tape.ks[t], Np, gxr.data_ptr(), gur.data_ptr(), gpx.data_ptr(), gpu_.data_ptr(), g0.data_ptr(),
             GS[t].data_ptr(), a.data_ptr(), gws.data_ptr(), gw.data_ptr(), None, sp),
+        "sim_window_vjp_fuzzy_kernel": lambda: L.tt_sim_window_vjp_fuzzy_device(
+            B, N, tape.ks[t], Np, gxr.data_ptr(), gur.data_ptr(), gpx.data_ptr(), gpu_.data_ptr(), g0.data_ptr(),
+            GS[t].data_ptr(), a.data_ptr(), gws.data_ptr(), gw.data_ptr(), None, C.byref(rstruct), rtape.S[t].data_ptr(),
+            xref.data_ptr(), rtape.retried[t].data_ptr(), gth.data_ptr(), sp),
     }
     n = 200
     print(f"  the launches of one backward step alone ({n} back to back), us per launch:")
