@@ -170,6 +170,24 @@ class Stager {
     }
     void upload(hipStream_t s) { copy(s, true); }
     void download(hipStream_t s) { copy(s, false); }
+    // The tail of a host call, after carve(): the uploads, device() (the call's device entry on s; it has set the error
+    // text if it fails), the downloads and the stream wait.  The first error wins; `what` names a failed copy or wait.
+    template <class Device>
+    int run(Handle* h, hipStream_t s, const char* what, Device device) {
+        upload(s);
+        if (err != hipSuccess) {
+            (void)hipStreamSynchronize(s);
+            return hip_fail(h, err, "H2D copy");
+        }
+        if (const int rc = device()) {
+            (void)hipStreamSynchronize(s);
+            return rc;
+        }
+        download(s);
+        const hipError_t es = hipStreamSynchronize(s);
+        const hipError_t e = err != hipSuccess ? err : es;
+        return e != hipSuccess ? hip_fail(h, e, what) : 0;
+    }
 
   private:
     struct Item {
@@ -199,6 +217,13 @@ class Stager {
         }
     }
 };
+
+// tt_track_vjp_out as the model entries take it, in o: no g_model.  NULL stays NULL (theirs to refuse).
+const tt_track_vjp_model_out* widen(const tt_track_vjp_out* out, tt_track_vjp_model_out& o) {
+    if (!out) return nullptr;
+    o = {out->g_x0, out->g_xref, out->g_uref, out->g_wq_wr, nullptr, out->vjp_status};
+    return &o;
+}
 
 // ---------------- the zero-copy mirror of tracking host calls ----------------
 void free_stage(Handle* h) {
@@ -641,13 +666,9 @@ int tt_track_vjp_model_device(void* handle, int B, const double* d_x, const doub
 int tt_track_vjp_device(void* handle, int B, const double* d_x, const double* d_u, const double* d_dual,
                         const double* d_xref, const double* d_uref, const double* d_wq_wr, const int* d_status,
                         const double* d_grad_x, const double* d_grad_u, const tt_track_vjp_out* d_out, void* stream) {
-    if (!d_out)
-        return tt_track_vjp_model_device(handle, B, d_x, d_u, d_dual, d_xref, d_uref, d_wq_wr, d_status, d_grad_x,
-                                         d_grad_u, nullptr, 0, stream);
-    const tt_track_vjp_model_out o = {d_out->g_x0, d_out->g_xref, d_out->g_uref, d_out->g_wq_wr, nullptr,
-                                      d_out->vjp_status};
+    tt_track_vjp_model_out o;
     return tt_track_vjp_model_device(handle, B, d_x, d_u, d_dual, d_xref, d_uref, d_wq_wr, d_status, d_grad_x,
-                                     d_grad_u, &o, 0, stream);
+                                     d_grad_u, widen(d_out, o), 0, stream);
 }
 
 int tt_track_vjp_model(void* handle, int B, const double* x, const double* u, const double* dual, const double* xref,
@@ -685,31 +706,17 @@ int tt_track_vjp_model(void* handle, int B, const double* x, const double* u, co
         st.out(out->g_model, b * 3, &dout.g_model);
     if (!st.carve(h->xfer)) return no_memory(h, "adjoint staging");
     hipStream_t s = h->stream;
-    st.upload(s);
-    if (st.err != hipSuccess) {
-        (void)hipStreamSynchronize(s);
-        return hip_fail(h, st.err, "H2D copy");
-    }
-    const int rc = tt_track_vjp_model_device(handle, B, d_x, d_u, d_dual, d_xref, d_uref, d_w, d_st, d_gx, d_gu, &dout,
-                                             accumulate, s);
-    if (rc) {
-        (void)hipStreamSynchronize(s);
-        return rc;
-    }
-    st.download(s);
-    const hipError_t es = hipStreamSynchronize(s);
-    const hipError_t e = st.err != hipSuccess ? st.err : es;
-    if (e != hipSuccess) return hip_fail(h, e, "adjoint");
-    return 0;
+    return st.run(h, s, "adjoint", [&] {
+        return tt_track_vjp_model_device(handle, B, d_x, d_u, d_dual, d_xref, d_uref, d_w, d_st, d_gx, d_gu, &dout,
+                                         accumulate, s);
+    });
 }
 
 int tt_track_vjp(void* handle, int B, const double* x, const double* u, const double* dual, const double* xref,
                  const double* uref, const double* wq_wr, const int* status, const double* grad_x,
                  const double* grad_u, const tt_track_vjp_out* out) {
-    if (!out)
-        return tt_track_vjp_model(handle, B, x, u, dual, xref, uref, wq_wr, status, grad_x, grad_u, nullptr, 0);
-    const tt_track_vjp_model_out o = {out->g_x0, out->g_xref, out->g_uref, out->g_wq_wr, nullptr, out->vjp_status};
-    return tt_track_vjp_model(handle, B, x, u, dual, xref, uref, wq_wr, status, grad_x, grad_u, &o, 0);
+    tt_track_vjp_model_out o;
+    return tt_track_vjp_model(handle, B, x, u, dual, xref, uref, wq_wr, status, grad_x, grad_u, widen(out, o), 0);
 }
 
 int tt_set_model(void* handle, double L1, double L2, double Mh) {
@@ -864,22 +871,10 @@ int tt_obca_solve_batch_iterate(void* handle, int B, const double* x0, const dou
     if (!st.carve(h->xfer))
         return fail(h, -ENOMEM, "device workspace allocation failed for B=%s", std::to_string(B).c_str());
     hipStream_t s = h->stream;
-    st.upload(s);
-    if (st.err != hipSuccess) {
-        (void)hipStreamSynchronize(s);
-        return hip_fail(h, st.err, "H2D copy");
-    }
-    const int rc = tt_obca_solve_batch_iterate_device(h, B, d_x0, d_xg, d_xr, d_ur, d_zg, d_xo, d_uo, d_zo, d_st, d_it,
-                                                      d_kkt, d_itout, s);
-    if (rc) {
-        (void)hipStreamSynchronize(s);
-        return rc;
-    }
-    st.download(s);
-    const hipError_t es = hipStreamSynchronize(s);
-    const hipError_t e = st.err != hipSuccess ? st.err : es;
-    if (e != hipSuccess) return hip_fail(h, e, "OBCA solve");
-    return 0;
+    return st.run(h, s, "OBCA solve", [&] {
+        return tt_obca_solve_batch_iterate_device(h, B, d_x0, d_xg, d_xr, d_ur, d_zg, d_xo, d_uo, d_zo, d_st, d_it, d_kkt,
+                                                  d_itout, s);
+    });
 }
 
 int tt_obca_solve_batch(void* handle, int B, const double* x0, const double* xgoal, const double* xref,

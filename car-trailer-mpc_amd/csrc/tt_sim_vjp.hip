@@ -287,6 +287,18 @@ __global__ void __launch_bounds__(kThreads) sim_window_vjp_fuzzy_kernel(
                               &fz);
 }
 
+// What the two policy-plant adjoint entries, and the two window adjoint entries, ask of their arguments.
+bool policy_plant_vjp_args_ok(int B, int N, const tt_plant* p, int policy, const double* state, const int* status,
+                              const int* active_after, const int* consecutive, const double* adj_state,
+                              const double* adj_u_last, const double* grad_u) {
+    return B > 0 && N >= 1 && N <= tt_max_horizon() && p && state && status && active_after && consecutive &&
+           adj_state && adj_u_last && grad_u && policy >= TT_POLICY_TRACK && policy <= TT_POLICY_FUZZY;
+}
+
+bool window_vjp_args_ok(int B, int N, int k, int Np) {
+    return B > 0 && N >= 1 && N <= tt_max_horizon() && Np >= 1 && k >= 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -295,8 +307,8 @@ int tt_policy_plant_vjp_device(int B, int N, const tt_plant* p, int policy, cons
                                const int* active_before, const int* active_after, const int* consecutive,
                                const double* grad_u_applied, double* adj_state, double* adj_u_last,
                                double* grad_u, double* g_state_noise, void* stream) {
-    if (B <= 0 || N < 1 || N > tt_max_horizon() || !p || !state || !status || !active_after || !consecutive ||
-        !adj_state || !adj_u_last || !grad_u || policy < TT_POLICY_TRACK || policy > TT_POLICY_FUZZY)
+    if (!policy_plant_vjp_args_ok(B, N, p, policy, state, status, active_after, consecutive, adj_state, adj_u_last,
+                                  grad_u))
         return -EINVAL;
     return launch_flat(policy_plant_vjp_kernel, "policy_plant_vjp_kernel", B, stream, B, N, *p, policy, state, status,
                        active_before, active_after, consecutive, grad_u_applied, adj_state, adj_u_last, grad_u,
@@ -311,8 +323,8 @@ int tt_policy_plant_vjp_model_device(int B, int N, const tt_plant* p, int policy
     if (!g_model_acc)
         return tt_policy_plant_vjp_device(B, N, p, policy, state, status, active_before, active_after, consecutive,
                                           grad_u_applied, adj_state, adj_u_last, grad_u, g_state_noise, stream);
-    if (B <= 0 || N < 1 || N > tt_max_horizon() || !p || !state || !status || !active_after || !consecutive ||
-        !adj_state || !adj_u_last || !grad_u || policy < TT_POLICY_TRACK || policy > TT_POLICY_FUZZY)
+    if (!policy_plant_vjp_args_ok(B, N, p, policy, state, status, active_after, consecutive, adj_state, adj_u_last,
+                                  grad_u))
         return -EINVAL;
     return launch_flat(policy_plant_vjp_model_kernel, "policy_plant_vjp_model_kernel", B, stream, B, N, *p, policy,
                        state, status, active_before, active_after, consecutive, grad_u_applied, adj_state, adj_u_last,
@@ -322,7 +334,7 @@ int tt_policy_plant_vjp_model_device(int B, int N, const tt_plant* p, int policy
 int tt_sim_window_vjp_device(int B, int N, int k, int Np, const double* g_xref, const double* g_uref, double* g_plan_x,
                              double* g_plan_u, const double* g_x0, const double* grad_state, double* adj_state,
                              const double* g_wq_wr, double* g_wq_wr_acc, double* g_meas_noise, void* stream) {
-    if (B <= 0 || N < 1 || N > tt_max_horizon() || Np < 1 || k < 0) return -EINVAL;
+    if (!window_vjp_args_ok(B, N, k, Np)) return -EINVAL;
     return launch_flat(sim_window_vjp_kernel, "sim_window_vjp_kernel", (long long)B * (N + 1), stream, B, N, k, Np,
                        g_xref, g_uref, g_plan_x, g_plan_u, g_x0, grad_state, adj_state, g_wq_wr, g_wq_wr_acc,
                        g_meas_noise);
@@ -336,8 +348,7 @@ int tt_sim_window_vjp_fuzzy_device(int B, int N, int k, int Np, const double* g_
     if (!rule)
         return tt_sim_window_vjp_device(B, N, k, Np, g_xref, g_uref, g_plan_x, g_plan_u, g_x0, grad_state, adj_state,
                                         g_wq_wr, g_wq_wr_acc, g_meas_noise, stream);
-    if (B <= 0 || N < 1 || N > tt_max_horizon() || Np < 1 || k < 0 || !fuzzy_rule_valid(*rule) || !x_meas || !xref)
-        return -EINVAL;
+    if (!window_vjp_args_ok(B, N, k, Np) || !fuzzy_rule_valid(*rule) || !x_meas || !xref) return -EINVAL;
     const FuzzyVjpArgs fz{*rule, x_meas, xref, retried, g_rule_acc};
     return launch_flat(sim_window_vjp_fuzzy_kernel, "sim_window_vjp_fuzzy_kernel", (long long)B * (N + 1), stream, B, N,
                        k, Np, g_xref, g_uref, g_plan_x, g_plan_u, g_x0, grad_state, adj_state, g_wq_wr, g_wq_wr_acc,

@@ -75,26 +75,21 @@ class TTError(RuntimeError):
 
 class TrackVjpResult:
     """What ``BatchSolver.vjp`` returns: g_x0 (B,6) = dL/dx0, g_xref (B,N+1,6), g_uref (B,N,2), g_wq_wr (B,8) and
-    vjp_status (B,) (0 ok, 1 undefined, 2 solve not successful; the gradients of a failed instance are zeros)."""
-    __slots__ = ("g_x0", "g_xref", "g_uref", "g_wq_wr", "vjp_status")
+    vjp_status (B,) (0 ok, 1 undefined, 2 solve not successful; the gradients of a failed instance are zeros); with
+    ``model=True`` also g_model (B,3) = dL/d(L1, L2, M) per instance, else None.  ``r["model"]``, ``r["x0"]``,
+    ``r["xref"]``, ``r["uref"]``, ``r["w"]`` read the gradients by the names of the inputs."""
+    __slots__ = ("g_x0", "g_xref", "g_uref", "g_wq_wr", "g_model", "vjp_status")
 
     def __init__(self, **kw):
         for k in self.__slots__:
             setattr(self, k, kw.get(k))
 
-
-class TrackVjpModelResult(TrackVjpResult):
-    """What ``BatchSolver.vjp(..., model=True)`` returns: a ``TrackVjpResult`` with g_model (B,3) = dL/d(L1, L2, M) per
-    instance, also read as ``r["model"]``."""
-    __slots__ = ("g_model",)
-
-    def __init__(self, **kw):
-        for k in TrackVjpResult.__slots__ + TrackVjpModelResult.__slots__:
-            setattr(self, k, kw.get(k))
-
     def __getitem__(self, key):
         return getattr(self, {"model": "g_model", "x0": "g_x0", "xref": "g_xref", "uref": "g_uref", "w": "g_wq_wr",
                               "vjp_status": "vjp_status"}[key])
+
+
+TrackVjpModelResult = TrackVjpResult
 
 
 class TrackExResult:
@@ -474,29 +469,23 @@ class BatchSolver(_Solver):
         """tt_track_vjp_device: the adjoint kernel on device arrays of an earlier ``solve_ex_device`` (its x, u, dual,
         status, and its inputs xref, uref, wq_wr) and the upstream gradients grad_x = dL/dX, grad_u = dL/dU (0 = zeros,
         not both).  Outputs (0 = not wanted): g_x0, g_xref, g_uref, g_wq_wr, vjp_status.  Uses no buffer of the handle:
-        any stream will do, behind the solve whose outputs it reads.  g_model (B,3): also dL/d(L1, L2, M) per instance
-        (tt_track_vjp_model_device), added to the buffer instead of written with ``accumulate``."""
-        if g_model:
-            mo = TTTrackVjpModelOut(g_x0 or None, g_xref or None, g_uref or None, g_wq_wr or None, g_model,
-                                    vjp_status or None)
-            rc = self._L.tt_track_vjp_model_device(self._h, int(B), x, u, dual, xref or None, uref or None,
-                                                   wq_wr or None, status, grad_x or None, grad_u or None, C.byref(mo),
-                                                   int(bool(accumulate)), stream or None)
-            if rc != 0:
-                self._err(rc, "tt_track_vjp_model_device")
-            return
-        out = TTTrackVjpOut(g_x0 or None, g_xref or None, g_uref or None, g_wq_wr or None, vjp_status or None)
-        rc = self._L.tt_track_vjp_device(self._h, int(B), x, u, dual, xref or None, uref or None, wq_wr or None, status,
-                                         grad_x or None, grad_u or None, C.byref(out), stream or None)
+        any stream will do, behind the solve whose outputs it reads.  g_model (B,3): also dL/d(L1, L2, M) per instance,
+        added to the buffer instead of written with ``accumulate``.  One call of tt_track_vjp_model_device either way:
+        without g_model it launches the plain kernel instantiation, as tt_track_vjp_device does."""
+        out = TTTrackVjpModelOut(g_x0 or None, g_xref or None, g_uref or None, g_wq_wr or None, g_model or None,
+                                 vjp_status or None)
+        rc = self._L.tt_track_vjp_model_device(self._h, int(B), x, u, dual, xref or None, uref or None, wq_wr or None,
+                                               status, grad_x or None, grad_u or None, C.byref(out),
+                                               int(bool(accumulate)), stream or None)
         if rc != 0:
-            self._err(rc, "tt_track_vjp_device")
+            self._err(rc, "tt_track_vjp_model_device" if g_model else "tt_track_vjp_device")
 
     def vjp(self, x, u, dual, xref, uref, status, grad_x, grad_u, wq_wr=None, model=False):
         """Host arrays: the gradient of a scalar loss L(X, U) with respect to the inputs of the solve that returned
         x (B,N+1,6), u (B,N,2), dual (B,N+1,22) and status (B,) for xref, uref and wq_wr; grad_x (B,N+1,6) = dL/dX and
-        grad_u (B,N,2) = dL/dU (either may be None for zeros).  Returns a ``TrackVjpResult``; with ``model=True`` a
-        ``TrackVjpModelResult``, which also has g_model (B,3) = dL/d(L1, L2, M) per instance (``r["model"]``;
-        tt_track_vjp_model)."""
+        grad_u (B,N,2) = dL/dU (either may be None for zeros).  Returns a ``TrackVjpResult``; with ``model=True`` it
+        also has g_model (B,3) = dL/d(L1, L2, M) per instance (``r["model"]``).  One call of tt_track_vjp_model either
+        way."""
         N = self.N
         x = _f64(x)
         B = x.shape[0] if x.ndim == 3 else 1
@@ -509,23 +498,15 @@ class BatchSolver(_Solver):
         gx = None if grad_x is None else _f64(grad_x, (B, N + 1, 6))
         gu = None if grad_u is None else _f64(grad_u, (B, N, 2))
         w = None if wq_wr is None else _f64(wq_wr, (B, 8))
-        outs = dict(g_x0=np.empty((B, 6)), g_xref=np.empty((B, N + 1, 6)), g_uref=np.empty((B, N, 2)),
-                    g_wq_wr=np.empty((B, 8)), vjp_status=np.empty(B, dtype=np.int32))
-        if model:
-            r = TrackVjpModelResult(g_model=np.empty((B, 3)), **outs)
-            mo = TTTrackVjpModelOut(*[a.ctypes.data for a in (r.g_x0, r.g_xref, r.g_uref, r.g_wq_wr, r.g_model,
-                                                                r.vjp_status)])
-            rc = self._L.tt_track_vjp_model(self._h, B, _ptr(x), _ptr(u), _ptr(dual), _ptr(xref), _ptr(uref), _ptr(w),
-                                            st.ctypes.data_as(_ip), _ptr(gx), _ptr(gu), C.byref(mo), 0)
-            if rc != 0:
-                self._err(rc, "tt_track_vjp_model")
-            return r
-        r = TrackVjpResult(**outs)
-        out = TTTrackVjpOut(*[a.ctypes.data for a in (r.g_x0, r.g_xref, r.g_uref, r.g_wq_wr, r.vjp_status)])
-        rc = self._L.tt_track_vjp(self._h, B, _ptr(x), _ptr(u), _ptr(dual), _ptr(xref), _ptr(uref), _ptr(w),
-                                  st.ctypes.data_as(_ip), _ptr(gx), _ptr(gu), C.byref(out))
+        r = TrackVjpResult(g_x0=np.empty((B, 6)), g_xref=np.empty((B, N + 1, 6)), g_uref=np.empty((B, N, 2)),
+                           g_wq_wr=np.empty((B, 8)), g_model=np.empty((B, 3)) if model else None,
+                           vjp_status=np.empty(B, dtype=np.int32))
+        out = TTTrackVjpModelOut(*[None if a is None else a.ctypes.data for a in (r.g_x0, r.g_xref, r.g_uref, r.g_wq_wr,
+                                                                                   r.g_model, r.vjp_status)])
+        rc = self._L.tt_track_vjp_model(self._h, B, _ptr(x), _ptr(u), _ptr(dual), _ptr(xref), _ptr(uref), _ptr(w),
+                                        st.ctypes.data_as(_ip), _ptr(gx), _ptr(gu), C.byref(out), 0)
         if rc != 0:
-            self._err(rc, "tt_track_vjp")
+            self._err(rc, "tt_track_vjp_model" if model else "tt_track_vjp")
         return r
 
 

@@ -17,7 +17,7 @@ instantiations of the adjoint kernels (include/ttmpc.h, tt_track_vjp_model_devic
 summed over the batch.
 
 A closed loop built with a ``ttmpc.simulation.FuzzyRule`` takes the rule's seven parameters as a tensor too
-(``fuzzy_rule=``, ``ClosedLoopRuleFunction``), and ``fuzzy_weights(x, xref, theta)`` is the rule alone as an autograd
+(``fuzzy_rule=``), and ``fuzzy_weights(x, xref, theta)`` is the rule alone as an autograd
 node (tt_fuzzy_weights_rule_device / tt_fuzzy_weights_vjp_device) whose output feeds ``DifferentiableTracking``'s wq_wr.
 
 ``DifferentiableLqrScore(params)`` is the LQR terminal score the drivers report at the end of a run
@@ -31,6 +31,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from . import simulation as sim
+
 __all__ = ["TrackingSolveFunction", "TrackingSolveModelFunction", "DifferentiableTracking", "ClosedLoopFunction",
            "ClosedLoopModelFunction", "ClosedLoopRuleFunction", "DifferentiableClosedLoop", "FuzzyWeightsFunction",
            "fuzzy_weights", "LqrScoreFunction", "DifferentiableLqrScore"]
@@ -41,119 +43,97 @@ def _ptr(t):
 
 
 def _check(name, t, shape):
-    if not (t.is_cuda and t.dtype == torch.float64):
-        raise TypeError(f"{name} must be a float64 CUDA tensor, got {t.dtype} on {t.device}")
-    if tuple(t.shape) != shape:
-        raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+    sim.check_tensor(name, t, shape)
     return t.detach().contiguous()
 
 
-def _geometry(name, t):
-    """(L1, L2, M) of a geometry tensor as host floats: float64, shape (3,), on the CPU or on a device (one host
-    read)."""
-    if not (torch.is_tensor(t) and t.dtype == torch.float64 and tuple(t.shape) == (3,)):
-        raise TypeError(f"{name} must be a float64 tensor of shape (3,) = (L1, L2, M)")
+_GEOMETRY = "(L1, L2, M)"
+_THETA = "(psi_full, gain_hitch, gain_steer, gain_rate, rev_hitch, rev_steer, rev_rate)"
+
+
+def _host_vector(name, t, what):
+    """A geometry (_GEOMETRY) or rule-parameter (_THETA) tensor as host floats: float64, shape (3,) or (7,), on the CPU
+    or on a device (one host read)."""
+    n = what.count(",") + 1
+    if not (torch.is_tensor(t) and t.dtype == torch.float64 and tuple(t.shape) == (n,)):
+        raise TypeError(f"{name} must be a float64 tensor of shape ({n},) = {what}")
     return tuple(float(v) for v in t.detach().cpu().tolist())
 
 
 def _batch_sum(g, device):
-    """The per-instance gradients (B,3) summed over the batch, on the geometry tensor's device."""
+    """The per-instance gradients (B,n) summed over the batch, on the input tensor's device."""
     return g.sum(dim=0).to(device)
 
 
-def _theta(t):
-    """The seven rule parameters of a theta tensor as host floats: float64, shape (7,), CPU or device (one host read)."""
-    if not (torch.is_tensor(t) and t.dtype == torch.float64 and tuple(t.shape) == (7,)):
-        raise TypeError("fuzzy_rule must be a float64 tensor of shape (7,) = (psi_full, gain_hitch, gain_steer, "
-                        "gain_rate, rev_hitch, rev_steer, rev_rate)")
-    return tuple(float(v) for v in t.detach().cpu().tolist())
-
-
 class TrackingSolveFunction(torch.autograd.Function):
-    """``X, U, status = TrackingSolveFunction.apply(solver, x0, xref, uref, wq_wr, z_guess)``.
+    """``X, U, status = TrackingSolveFunction.apply(solver, x0, xref, uref, wq_wr, z_guess[, model])``.
 
     x0 (B,6), xref (B,N+1,6), uref (B,N,2), wq_wr (B,8) or None, z_guess (B,8N+6) or None: float64 CUDA tensors on the
     solver's device.  X (B,N+1,6) and U (B,N,2) are differentiable with respect to x0, xref, uref and wq_wr; status
     (B,) int32 is not, and z_guess gets no gradient (it does not move a converged solution).  An instance whose solve
-    status is above TT_ACCEPTABLE, or whose adjoint is undefined, contributes a zero gradient."""
+    status is above TT_ACCEPTABLE, or whose adjoint is undefined, contributes a zero gradient.
+
+    model, if given, makes the solver's geometry an input: float64 (3,) = (L1, L2, M), on the CPU or on a device (then
+    the forward reads it to the host once).  The forward applies it with ``solver.set_model`` when it differs from the
+    handle's values, and it stays applied; the backward runs the adjoint kernel's model instantiation and returns the
+    per-instance gradients summed over B on the tensor's device.  It raises if the handle's geometry was changed
+    between the forward and the backward.  Left out or None: the geometry as it is, no gradient for it."""
 
     @staticmethod
-    def forward(ctx, solver, x0, xref, uref, wq_wr, z_guess):
-        return _track_forward(ctx, solver, x0, xref, uref, wq_wr, z_guess)
-
-    @staticmethod
-    def backward(ctx, grad_X, grad_U, _grad_status):
-        return _track_backward(ctx, grad_X, grad_U, False)[0]
-
-
-def _track_forward(ctx, solver, x0, xref, uref, wq_wr, z_guess):
-    N, B = solver.N, x0.shape[0]
-    x0 = _check("x0", x0, (B, 6))
-    xref = _check("xref", xref, (B, N + 1, 6))
-    uref = _check("uref", uref, (B, N, 2))
-    wq_wr = None if wq_wr is None else _check("wq_wr", wq_wr, (B, 8))
-    z_guess = None if z_guess is None else _check("z_guess", z_guess, (B, 8 * N + 6))
-    dev = x0.device
-    X = torch.empty((B, N + 1, 6), dtype=torch.float64, device=dev)
-    U = torch.empty((B, N, 2), dtype=torch.float64, device=dev)
-    dual = torch.empty((B, N + 1, 22), dtype=torch.float64, device=dev)
-    status = torch.empty((B,), dtype=torch.int32, device=dev)
-    solver.solve_ex_device(B, x0.data_ptr(), xref.data_ptr(), uref.data_ptr(), X.data_ptr(), U.data_ptr(),
-                           status.data_ptr(), wq_wr=_ptr(wq_wr), z_guess=_ptr(z_guess), dual=dual.data_ptr(),
-                           stream=torch.cuda.current_stream(dev).cuda_stream)
-    ctx.solver = solver
-    ctx.has_w = wq_wr is not None
-    ctx.save_for_backward(X, U, dual, status, xref, uref, *(() if wq_wr is None else (wq_wr,)))
-    ctx.mark_non_differentiable(status)
-    return X, U, status
-
-
-def _track_backward(ctx, grad_X, grad_U, want_model):
-    """-> ((None, g_x0, g_xref, g_uref, g_wq_wr, None), g_model (B,3) or None)"""
-    X, U, dual, status, xref, uref = ctx.saved_tensors[:6]
-    wq_wr = ctx.saved_tensors[6] if ctx.has_w else None
-    need = ctx.needs_input_grad  # (solver, x0, xref, uref, wq_wr, z_guess[, model])
-    if grad_X is None and grad_U is None:
-        return (None,) * 6, None
-    B, N, dev = X.shape[0], ctx.solver.N, X.device
-    gX = None if grad_X is None else grad_X.to(torch.float64).contiguous()
-    gU = None if grad_U is None else grad_U.to(torch.float64).contiguous()
-    new = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)  # noqa: E731
-    g_x0 = new(B, 6) if need[1] else None
-    g_xref = new(B, N + 1, 6) if need[2] else None
-    g_uref = new(B, N, 2) if need[3] else None
-    g_w = new(B, 8) if need[4] else None
-    g_m = new(B, 3) if want_model else None
-    ctx.solver.vjp_device(B, X.data_ptr(), U.data_ptr(), dual.data_ptr(), xref.data_ptr(), uref.data_ptr(),
-                          status.data_ptr(), grad_x=_ptr(gX), grad_u=_ptr(gU), g_x0=_ptr(g_x0), g_xref=_ptr(g_xref),
-                          g_uref=_ptr(g_uref), g_wq_wr=_ptr(g_w), wq_wr=_ptr(wq_wr),
-                          stream=torch.cuda.current_stream(dev).cuda_stream, g_model=_ptr(g_m))
-    return (None, g_x0, g_xref, g_uref, g_w, None), g_m
-
-
-class TrackingSolveModelFunction(torch.autograd.Function):
-    """``X, U, status = TrackingSolveModelFunction.apply(solver, x0, xref, uref, wq_wr, z_guess, model)``:
-    ``TrackingSolveFunction`` with the solver's geometry as an input.  model: float64 (3,) = (L1, L2, M), on the CPU or
-    on a device (then the forward reads it to the host once).  The forward applies it with ``solver.set_model`` when it
-    differs from the handle's values, and it stays applied; the backward runs the adjoint kernel's model instantiation
-    and returns the per-instance gradients summed over B on the tensor's device.  It raises if the handle's geometry
-    was changed between the forward and the backward."""
-
-    @staticmethod
-    def forward(ctx, solver, x0, xref, uref, wq_wr, z_guess, model):
-        vals = _geometry("model", model)
-        if vals != solver.model():
-            solver.set_model(*vals)
-        ctx.geometry, ctx.like = vals, model.device
-        return _track_forward(ctx, solver, x0, xref, uref, wq_wr, z_guess)
+    def forward(ctx, solver, x0, xref, uref, wq_wr, z_guess, model=None):
+        ctx.geometry = None
+        if model is not None:
+            ctx.geometry, ctx.like = _host_vector("model", model, _GEOMETRY), model.device
+            if ctx.geometry != solver.model():
+                solver.set_model(*ctx.geometry)
+        N, B = solver.N, x0.shape[0]
+        x0 = _check("x0", x0, (B, 6))
+        xref = _check("xref", xref, (B, N + 1, 6))
+        uref = _check("uref", uref, (B, N, 2))
+        wq_wr = None if wq_wr is None else _check("wq_wr", wq_wr, (B, 8))
+        z_guess = None if z_guess is None else _check("z_guess", z_guess, (B, 8 * N + 6))
+        dev = x0.device
+        X = torch.empty((B, N + 1, 6), dtype=torch.float64, device=dev)
+        U = torch.empty((B, N, 2), dtype=torch.float64, device=dev)
+        dual = torch.empty((B, N + 1, 22), dtype=torch.float64, device=dev)
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        solver.solve_ex_device(B, x0.data_ptr(), xref.data_ptr(), uref.data_ptr(), X.data_ptr(), U.data_ptr(),
+                               status.data_ptr(), wq_wr=_ptr(wq_wr), z_guess=_ptr(z_guess), dual=dual.data_ptr(),
+                               stream=torch.cuda.current_stream(dev).cuda_stream)
+        ctx.solver = solver
+        ctx.has_w = wq_wr is not None
+        ctx.save_for_backward(X, U, dual, status, xref, uref, *(() if wq_wr is None else (wq_wr,)))
+        ctx.mark_non_differentiable(status)
+        return X, U, status
 
     @staticmethod
     def backward(ctx, grad_X, grad_U, _grad_status):
-        if ctx.geometry != ctx.solver.model():
+        need = ctx.needs_input_grad  # (solver, x0, xref, uref, wq_wr, z_guess[, model]): one gradient per input given
+        if ctx.geometry is not None and ctx.geometry != ctx.solver.model():
             raise RuntimeError(f"the solver's geometry changed since the forward: {ctx.geometry} -> "
                                f"{ctx.solver.model()}")
-        g, g_m = _track_backward(ctx, grad_X, grad_U, ctx.needs_input_grad[6])
-        return (*g, None if g_m is None else _batch_sum(g_m, ctx.like))
+        if grad_X is None and grad_U is None:
+            return (None,) * len(need)
+        X, U, dual, status, xref, uref = ctx.saved_tensors[:6]
+        wq_wr = ctx.saved_tensors[6] if ctx.has_w else None
+        B, N, dev = X.shape[0], ctx.solver.N, X.device
+        gX = None if grad_X is None else grad_X.to(torch.float64).contiguous()
+        gU = None if grad_U is None else grad_U.to(torch.float64).contiguous()
+        new = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)  # noqa: E731
+        g_x0 = new(B, 6) if need[1] else None
+        g_xref = new(B, N + 1, 6) if need[2] else None
+        g_uref = new(B, N, 2) if need[3] else None
+        g_w = new(B, 8) if need[4] else None
+        g_m = new(B, 3) if len(need) > 6 and need[6] else None
+        ctx.solver.vjp_device(B, X.data_ptr(), U.data_ptr(), dual.data_ptr(), xref.data_ptr(), uref.data_ptr(),
+                              status.data_ptr(), grad_x=_ptr(gX), grad_u=_ptr(gU), g_x0=_ptr(g_x0), g_xref=_ptr(g_xref),
+                              g_uref=_ptr(g_uref), g_wq_wr=_ptr(g_w), wq_wr=_ptr(wq_wr),
+                              stream=torch.cuda.current_stream(dev).cuda_stream, g_model=_ptr(g_m))
+        return (None, g_x0, g_xref, g_uref, g_w, None,
+                None if g_m is None else _batch_sum(g_m, ctx.like))[:len(need)]
+
+
+TrackingSolveModelFunction = TrackingSolveFunction
 
 
 class DifferentiableTracking:
@@ -165,131 +145,87 @@ class DifferentiableTracking:
     solver).  The backward uses no buffer of the handle and may run on any stream that is ordered behind the forward,
     as autograd's stream bookkeeping arranges.  Look at ``status`` (and at ``solver.vjp_device(..., vjp_status=...)``
     when in doubt) to see which instances gave a gradient: failed ones give zeros.  With ``model`` (a float64 (3,)
-    tensor (L1, L2, M), CPU or device) the solver's geometry is an input too: ``TrackingSolveModelFunction``."""
+    tensor (L1, L2, M), CPU or device) the solver's geometry is an input too."""
 
     def __init__(self, solver):
         self.solver = solver
 
     def __call__(self, x0, xref, uref, wq_wr=None, z_guess=None, model=None):
         """model: float64 (3,) tensor (L1, L2, M) or None (the solver's geometry as it is, no gradient for it)."""
-        if model is None:
-            return TrackingSolveFunction.apply(self.solver, x0, xref, uref, wq_wr, z_guess)
-        return TrackingSolveModelFunction.apply(self.solver, x0, xref, uref, wq_wr, z_guess, model)
+        return TrackingSolveFunction.apply(self.solver, x0, xref, uref, wq_wr, z_guess, model)
 
 
 class ClosedLoopFunction(torch.autograd.Function):
-    """``S, Ua, status = ClosedLoopFunction.apply(loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise)``.
+    """``S, Ua, status = ClosedLoopFunction.apply(loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise[, model,
+    plant_model[, fuzzy_rule]])``.
 
     x_init (B,6), wq_wr (B,8) or None, plan_x (P,Np+1,6) and plan_u (P,Np,2) with P = 1 (shared) or B, or None for the
     loop's own plan, noise (K,B,6) or None: float64 CUDA tensors on the loop's device.  S (K+1,B,6) and Ua (K,B,2) are
-    differentiable with respect to all five; status (K,B) int32 is not."""
+    differentiable with respect to all five; status (K,B) int32 is not.
+
+    model, plant_model: the two geometries as inputs, each a float64 (3,) tensor (L1, L2, M) on the CPU or on a device
+    (one host read each), or None.  model is the geometry the controller believes, plant_model the plant's; the forward
+    applies them with ``loop.set_model`` when they differ from the current values, and they stay applied.  The backward
+    returns their gradients summed over B on each tensor's device; the same tensor given as both receives the sum of
+    the two, the gradient for a geometry controller and plant share.
+
+    fuzzy_rule, for a loop built with a ``FuzzyRule``: the rule's parameters as an input, a float64 (7,) tensor theta on
+    the CPU or on a device (one host read), or None.  The forward applies it with ``loop.set_fuzzy_rule`` (the rule's
+    settings w_min, w_max, v_rev stay the loop's) when it differs from the current values, and it stays applied; the
+    backward returns dL/dtheta summed over B on the tensor's device.  wq_wr must then be None: the weights come from
+    the rule."""
+
+    EXTRA = ("g_model_solver", "g_model_plant", "g_fuzzy_rule")   # ClosedLoop.backward's keys of inputs 7, 8, 9
 
     @staticmethod
-    def forward(ctx, loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise):
-        return _loop_forward(ctx, loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise)
-
-    @staticmethod
-    def backward(ctx, grad_S, grad_Ua, _grad_status):
-        return _loop_backward(ctx, grad_S, grad_Ua, False)[0]
-
-
-def _loop_forward(ctx, loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise):
-    if (plan_x is None) != (plan_u is None):
-        raise ValueError("give plan_x and plan_u together")
-    B = x_init.shape[0]
-    x_init = _check("x_init", x_init, (B, 6))
-    if plan_x is not None:
-        Np = plan_u.shape[-2]
-        P = plan_x.shape[0]
-        if plan_x.dim() != 3 or P not in (1, B):
-            raise ValueError("plan_x must be (1, Np+1, 6) for a shared plan or (B, Np+1, 6)")
-        loop.plan_x, loop.plan_u = _check("plan_x", plan_x, (P, Np + 1, 6)), _check("plan_u", plan_u, (P, Np, 2))
-    out = loop.run_tape(x_init, T_sim, noise=noise, wq_wr=wq_wr)
-    tape = out["tape"]
-    ctx.loop, ctx.tape = loop, tape
-    status = tape.status.clone()   # (copies: the node keeps the tape, the outputs must not keep the node)
-    ctx.mark_non_differentiable(status)
-    return tape.S.clone(), tape.Ua.clone(), status
-
-
-def _loop_backward(ctx, grad_S, grad_Ua, want_model, want_rule=False):
-    """-> ((None, None, g_x_init, g_wq_wr, g_plan_x, g_plan_u, g_noise), ClosedLoop.backward's dict or None)"""
-    need = ctx.needs_input_grad  # (loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise[, model, plant_model[, rule]])
-    tape = ctx.tape
-    if grad_S is None and grad_Ua is None:
-        return (None,) * 7, None
-    GS = torch.zeros_like(tape.S) if grad_S is None else grad_S.to(torch.float64).contiguous()
-    GU = torch.zeros_like(tape.Ua) if grad_Ua is None else grad_Ua.to(torch.float64).contiguous()
-    kw = dict(model=True) if want_model else {}
-    if want_rule:
-        kw["rule"] = True
-    g = ctx.loop.backward(tape, GS, GU, **kw)
-    pick = lambda i, k: g[k] if need[i] else None  # noqa: E731
-    return (None, None, pick(2, "g_x_init"), pick(3, "g_wq_wr"), pick(4, "g_plan_x"), pick(5, "g_plan_u"),
-            pick(6, "g_noise")), g
-
-
-class ClosedLoopModelFunction(torch.autograd.Function):
-    """``S, Ua, status = ClosedLoopModelFunction.apply(loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise, model,
-    plant_model)``: ``ClosedLoopFunction`` with the two geometries as inputs, each a float64 (3,) tensor (L1, L2, M) on
-    the CPU or on a device (one host read each), or None.  model is the geometry the controller believes, plant_model
-    the plant's; the forward applies them with ``loop.set_model`` when they differ from the current values, and they
-    stay applied.  The backward returns their gradients summed over B on each tensor's device; the same tensor given
-    as both receives the sum of the two, the gradient for a geometry controller and plant share."""
-
-    @staticmethod
-    def forward(ctx, loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise, model, plant_model):
-        vs = None if model is None else _geometry("model", model)
-        vp = None if plant_model is None else _geometry("plant_model", plant_model)
-        loop.set_model(solver=None if vs is None or vs == loop.solver.model() else vs,
-                       plant=None if vp is None or vp == loop.plant_model() else vp)
-        ctx.like = tuple(None if t is None else t.device for t in (model, plant_model))
-        return _loop_forward(ctx, loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise)
-
-    @staticmethod
-    def backward(ctx, grad_S, grad_Ua, _grad_status):
-        need = ctx.needs_input_grad
-        grads, g = _loop_backward(ctx, grad_S, grad_Ua, need[7] or need[8])
-        gm = [None, None]
-        if g is not None and (need[7] or need[8]):
-            for i, key in enumerate(("g_model_solver", "g_model_plant")):
-                if need[7 + i]:
-                    gm[i] = _batch_sum(g[key], ctx.like[i])
-        return (*grads, *gm)
-
-
-class ClosedLoopRuleFunction(torch.autograd.Function):
-    """``S, Ua, status = ClosedLoopRuleFunction.apply(loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise, model,
-    plant_model, fuzzy_rule)``: ``ClosedLoopModelFunction`` for a loop built with a ``FuzzyRule``, with the rule's
-    parameters as an input: fuzzy_rule is a float64 (7,) tensor theta on the CPU or on a device (one host read).  The
-    forward applies it with ``loop.set_fuzzy_rule`` (the rule's settings w_min, w_max, v_rev stay the loop's) when it
-    differs from the current values, and it stays applied; the backward returns dL/dtheta summed over B on the
-    tensor's device.  wq_wr must be None: the weights come from the rule."""
-
-    @staticmethod
-    def forward(ctx, loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise, model, plant_model, fuzzy_rule):
-        if loop.rule is None:
-            raise ValueError("fuzzy_rule= needs a loop built with ClosedLoop(..., fuzzy_rule=FuzzyRule(...))")
-        vals = _theta(fuzzy_rule)
-        if vals != loop.rule.theta():
-            loop.set_fuzzy_rule(loop.rule.with_theta(vals))
-        vs = None if model is None else _geometry("model", model)
-        vp = None if plant_model is None else _geometry("plant_model", plant_model)
+    def forward(ctx, loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise, model=None, plant_model=None, fuzzy_rule=None):
+        if fuzzy_rule is not None:
+            if loop.rule is None:
+                raise ValueError("fuzzy_rule= needs a loop built with ClosedLoop(..., fuzzy_rule=FuzzyRule(...))")
+            vals = _host_vector("fuzzy_rule", fuzzy_rule, _THETA)
+            if vals != loop.rule.theta():
+                loop.set_fuzzy_rule(loop.rule.with_theta(vals))
+        vs = None if model is None else _host_vector("model", model, _GEOMETRY)
+        vp = None if plant_model is None else _host_vector("plant_model", plant_model, _GEOMETRY)
         loop.set_model(solver=None if vs is None or vs == loop.solver.model() else vs,
                        plant=None if vp is None or vp == loop.plant_model() else vp)
         ctx.like = tuple(None if t is None else t.device for t in (model, plant_model, fuzzy_rule))
-        return _loop_forward(ctx, loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise)
+        if (plan_x is None) != (plan_u is None):
+            raise ValueError("give plan_x and plan_u together")
+        B = x_init.shape[0]
+        x_init = _check("x_init", x_init, (B, 6))
+        if plan_x is not None:
+            Np = plan_u.shape[-2]
+            P = plan_x.shape[0]
+            if plan_x.dim() != 3 or P not in (1, B):
+                raise ValueError("plan_x must be (1, Np+1, 6) for a shared plan or (B, Np+1, 6)")
+            loop.plan_x, loop.plan_u = _check("plan_x", plan_x, (P, Np + 1, 6)), _check("plan_u", plan_u, (P, Np, 2))
+        out = loop.run_tape(x_init, T_sim, noise=noise, wq_wr=wq_wr)
+        tape = out["tape"]
+        ctx.loop, ctx.tape = loop, tape
+        status = tape.status.clone()   # (copies: the node keeps the tape, the outputs must not keep the node)
+        ctx.mark_non_differentiable(status)
+        return tape.S.clone(), tape.Ua.clone(), status
 
     @staticmethod
     def backward(ctx, grad_S, grad_Ua, _grad_status):
-        need = ctx.needs_input_grad
-        grads, g = _loop_backward(ctx, grad_S, grad_Ua, need[7] or need[8], need[9])
-        extra = [None, None, None]
-        if g is not None:
-            for i, key in enumerate(("g_model_solver", "g_model_plant", "g_fuzzy_rule")):
-                if need[7 + i]:
-                    extra[i] = _batch_sum(g[key], ctx.like[i])
-        return (*grads, *extra)
+        # (loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise[, model, plant_model[, fuzzy_rule]]): one gradient per
+        # input given
+        need = ctx.needs_input_grad + (False,) * (10 - len(ctx.needs_input_grad))
+        tape = ctx.tape
+        if grad_S is None and grad_Ua is None:
+            return (None,) * len(ctx.needs_input_grad)
+        GS = torch.zeros_like(tape.S) if grad_S is None else grad_S.to(torch.float64).contiguous()
+        GU = torch.zeros_like(tape.Ua) if grad_Ua is None else grad_Ua.to(torch.float64).contiguous()
+        g = ctx.loop.backward(tape, GS, GU, **(dict(model=True) if need[7] or need[8] else {}),
+                              **(dict(rule=True) if need[9] else {}))
+        pick = lambda i, k: g[k] if need[i] else None  # noqa: E731
+        extra = [_batch_sum(g[k], ctx.like[i]) if need[7 + i] else None for i, k in enumerate(ClosedLoopFunction.EXTRA)]
+        return (None, None, pick(2, "g_x_init"), pick(3, "g_wq_wr"), pick(4, "g_plan_x"), pick(5, "g_plan_u"),
+                pick(6, "g_noise"), *extra)[:len(ctx.needs_input_grad)]
+
+
+ClosedLoopModelFunction = ClosedLoopRuleFunction = ClosedLoopFunction
 
 
 class FuzzyWeightsFunction(torch.autograd.Function):
@@ -302,20 +238,18 @@ class FuzzyWeightsFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, xref, theta, rule):
-        from . import simulation as sim
         B = x.shape[0]
         x = _check("x", x, (B, 6))
         if xref.dim() != 3:
             raise ValueError("xref must be (B, N+1, 6)")
         xref = _check("xref", xref, (B, xref.shape[1], 6))
-        ctx.rule = (rule or sim.FuzzyRule()).with_theta(_theta(theta))
+        ctx.rule = (rule or sim.FuzzyRule()).with_theta(_host_vector("fuzzy_rule", theta, _THETA))
         ctx.like = theta.device
         ctx.save_for_backward(x, xref)
         return sim.fuzzy_weights_rule(x, xref, ctx.rule)
 
     @staticmethod
     def backward(ctx, grad_w):
-        from . import simulation as sim
         x, xref = ctx.saved_tensors
         g_x, g_rule = sim.fuzzy_weights_vjp(x, xref, grad_w.to(torch.float64).contiguous(), ctx.rule)
         need = ctx.needs_input_grad
@@ -339,9 +273,8 @@ class DifferentiableClosedLoop:
     the loop's.  The forward synchronises once at its end, as ``run`` does; the backward does not.  Zero gradient comes
     from: failed solves (whatever the policy then applies), stopped instances, variables sitting on a bound, and the
     warm start (z_guess does not move a converged solution).  With ``model`` and / or ``plant_model`` (float64 (3,)
-    tensors (L1, L2, M), CPU or device) the controller's and the plant's geometry are inputs too:
-    ``ClosedLoopModelFunction``.  With ``fuzzy_rule`` (a float64 (7,) tensor theta, CPU or device) the parameters of the
-    loop's fuzzy rule are an input as well: ``ClosedLoopRuleFunction``."""
+    tensors (L1, L2, M), CPU or device) the controller's and the plant's geometry are inputs too.  With ``fuzzy_rule``
+    (a float64 (7,) tensor theta, CPU or device) the parameters of the loop's fuzzy rule are an input as well."""
 
     def __init__(self, loop):
         loop._check_differentiable()
@@ -351,13 +284,8 @@ class DifferentiableClosedLoop:
                  fuzzy_rule=None):
         """model, plant_model: float64 (3,) tensors (L1, L2, M) of the controller's and of the plant's geometry, or
         None (as they are, no gradient).  fuzzy_rule: float64 (7,) tensor theta of the loop's ``FuzzyRule``, or None."""
-        if fuzzy_rule is not None:
-            return ClosedLoopRuleFunction.apply(self.loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise, model,
-                                                plant_model, fuzzy_rule)
-        if model is None and plant_model is None:
-            return ClosedLoopFunction.apply(self.loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise)
-        return ClosedLoopModelFunction.apply(self.loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise, model,
-                                             plant_model)
+        return ClosedLoopFunction.apply(self.loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise, model, plant_model,
+                                        fuzzy_rule)
 
 
 def _host(name, m, n):

@@ -80,6 +80,22 @@ def _dev(a, dev, dtype=torch.float64):
     return torch.as_tensor(np.ascontiguousarray(a) if not torch.is_tensor(a) else a, dtype=dtype).to(dev).contiguous()
 
 
+def check_tensor(name, t, shape, dev=None, got=False):
+    """Raise unless t is a float64 tensor of exactly ``shape`` (the kernels index it as such) on ``dev``; got: the
+    message also says what came instead.  dev None, the autograd layer's inputs: on any CUDA device, a TypeError for
+    the kind of tensor and a ValueError for its shape."""
+    shape = tuple(shape)
+    if dev is None:
+        if not (t.is_cuda and t.dtype == torch.float64):
+            raise TypeError(f"{name} must be a float64 CUDA tensor, got {t.dtype} on {t.device}")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+    elif not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.device == dev and
+              tuple(t.shape) == shape):
+        what = (tuple(t.shape), t.dtype, t.device) if isinstance(t, torch.Tensor) else type(t)
+        raise ValueError(f"{name} must be a float64 tensor of shape {shape} on {dev}" + (f", got {what}" if got else ""))
+
+
 def _run_noise(noise, K, B, dev):
     """A whole run's noise draws (host or device, or None) as a (steps, B, 6) float64 tensor on the device."""
     if noise is None:
@@ -182,18 +198,11 @@ def policy_plant_vjp(state, status, active_after, consecutive, adj_state, adj_u_
     if policy not in POLICIES:
         raise ValueError(f"policy must be one of {sorted(POLICIES)}")
     p = plant(params, disturbance_params)
-    if g_model is not None:
-        _check(lib().tt_policy_plant_vjp_model_device(
-            state.shape[0], grad_u.shape[1], C.byref(p), POLICIES[policy], state.data_ptr(), status.data_ptr(),
-            _ptr(active_before), active_after.data_ptr(), consecutive.data_ptr(), _ptr(grad_u_applied),
-            adj_state.data_ptr(), adj_u_last.data_ptr(), grad_u.data_ptr(), _ptr(g_state_noise), g_model.data_ptr(),
-            _stream(stream, dev)), "tt_policy_plant_vjp_model_device")
-        return adj_state, adj_u_last, grad_u
-    _check(lib().tt_policy_plant_vjp_device(state.shape[0], grad_u.shape[1], C.byref(p), POLICIES[policy],
-                                            state.data_ptr(), status.data_ptr(), _ptr(active_before),
-                                            active_after.data_ptr(), consecutive.data_ptr(), _ptr(grad_u_applied),
-                                            adj_state.data_ptr(), adj_u_last.data_ptr(), grad_u.data_ptr(),
-                                            _ptr(g_state_noise), _stream(stream, dev)), "tt_policy_plant_vjp_device")
+    _check(lib().tt_policy_plant_vjp_model_device(   # (a NULL accumulator forwards to the plain entry)
+        state.shape[0], grad_u.shape[1], C.byref(p), POLICIES[policy], state.data_ptr(), status.data_ptr(),
+        _ptr(active_before), active_after.data_ptr(), consecutive.data_ptr(), _ptr(grad_u_applied),
+        adj_state.data_ptr(), adj_u_last.data_ptr(), grad_u.data_ptr(), _ptr(g_state_noise), _ptr(g_model),
+        _stream(stream, dev)), "tt_policy_plant_vjp_model_device" if g_model is not None else "tt_policy_plant_vjp_device")
     return adj_state, adj_u_last, grad_u
 
 
@@ -474,11 +483,7 @@ class ClosedLoop:
         self.stream.wait_stream(torch.cuda.current_stream(self.dev))
 
     def _check_noise(self, noise, shape):
-        """noise must be a float64 tensor of exactly `shape` on the loop's device (the kernels index it as such)."""
-        if not (isinstance(noise, torch.Tensor) and noise.dtype == torch.float64 and noise.device == self.dev and
-                tuple(noise.shape) == tuple(shape)):
-            got = (tuple(noise.shape), noise.dtype, noise.device) if isinstance(noise, torch.Tensor) else type(noise)
-            raise ValueError(f"noise must be a float64 tensor of shape {tuple(shape)} on {self.dev}, got {got}")
+        check_tensor("noise", noise, shape, self.dev, got=True)
 
     def step(self, k, noise=None, dual=None, wq_wr=None):
         """Enqueue one closed-loop step at window index k (noise: (B,6) float64 device tensor or None: the measurement
@@ -784,10 +789,8 @@ class ClosedLoop:
         s, d, N = self.stream, self.dev, self.N
         K, B = tape.status.shape
         Np = tape.plan_u.shape[-2]
-        for name, t, shape in (("GS", GS, (K + 1, B, 6)), ("GU", GU, (K, B, 2))):
-            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.device == d and
-                    tuple(t.shape) == shape):
-                raise ValueError(f"{name} must be a float64 tensor of shape {shape} on {d}")
+        check_tensor("GS", GS, (K + 1, B, 6), d)
+        check_tensor("GU", GU, (K, B, 2), d)
         GS, GU = GS.contiguous(), GU.contiguous()
         z = lambda *sh: torch.zeros(sh, dtype=torch.float64, device=d)  # noqa: E731
         a, abar, gU = GS[K].clone(), z(B, 2), z(B, N, 2)
@@ -806,6 +809,13 @@ class ClosedLoop:
         L, p, sp = lib(), plant(self.params, self.dist), C.c_void_p(s.cuda_stream)
         per = int(tape.plan_x.shape[0] != 1)
         wq = 0 if tape.wq_wr is None else tape.wq_wr.data_ptr()
+        # Chosen once per run: the plant adjoint and the window adjoint each come in a plain and a wider form, and a run
+        # calls the form it needs (marshalling the wider argument lists costs about 1.5 us per step, which the plain
+        # loop must not pay).  at(t): what a rule loop adds per step, ((state, noise) of the window launch that rebuilds
+        # x_meas, the weights the solve used, the tail of the window adjoint).
+        plant_vjp, plant_tail = ((L.tt_policy_plant_vjp_model_device, (g_mp.data_ptr(), sp)) if model else
+                                 (L.tt_policy_plant_vjp_device, (sp,)))
+        g_model = g_ms.data_ptr() if model else 0
         if fz:
             # the rule's four extra per-step addresses by offset: a tape slice made on the host costs it more than the
             # launch it feeds, and the host only just keeps ahead of a backward step
@@ -813,36 +823,32 @@ class ClosedLoop:
                 raise ValueError("the tape's S, W, retried and noise must be contiguous")
             S0, W0, R0 = tape.S.data_ptr(), tape.W.data_ptr(), tape.retried.data_ptr()
             N0 = tape.noise.data_ptr() if meas else None
+            win_vjp, head = L.tt_sim_window_vjp_fuzzy_device, (rs, x_meas.data_ptr(), xref.data_ptr())
+            at = lambda t: ((S0 + t * B * 48, N0 + t * B * 48 if meas else None), W0 + t * B * 64,  # noqa: E731
+                            (*head, R0 + t * B * 4, _ptr(g_th), sp))
+        else:
+            win_vjp, plain = L.tt_sim_window_vjp_device, ((None, None), wq, (sp,))
+            at = lambda t: plain  # noqa: E731
+        plant_name, win_name = plant_vjp.__name__, win_vjp.__name__
         s.wait_stream(torch.cuda.current_stream(d))
         for t in range(K - 1, -1, -1):
-            pp = (B, N, C.byref(p), POLICIES[self.policy], tape.S[t].data_ptr(), tape.status[t].data_ptr(),
-                  None if t == 0 else tape.active[t - 1].data_ptr(), tape.active[t].data_ptr(),
-                  tape.consec[t].data_ptr(), GU[t].data_ptr(), a.data_ptr(), abar.data_ptr(), gU.data_ptr(),
-                  g_n[t].data_ptr() if in_plant else None)
-            if model:
-                _check(L.tt_policy_plant_vjp_model_device(*pp, g_mp.data_ptr(), sp), "tt_policy_plant_vjp_model_device")
-            else:
-                _check(L.tt_policy_plant_vjp_device(*pp, sp), "tt_policy_plant_vjp_device")
+            meas_in, w_t, win_tail = at(t)
+            _check(plant_vjp(B, N, C.byref(p), POLICIES[self.policy], tape.S[t].data_ptr(), tape.status[t].data_ptr(),
+                             None if t == 0 else tape.active[t - 1].data_ptr(), tape.active[t].data_ptr(),
+                             tape.consec[t].data_ptr(), GU[t].data_ptr(), a.data_ptr(), abar.data_ptr(), gU.data_ptr(),
+                             g_n[t].data_ptr() if in_plant else None, *plant_tail), plant_name)
             _check(L.tt_sim_window_device(B, N, int(tape.ks[t]), int(Np), tape.plan_x.data_ptr(),
-                                          tape.plan_u.data_ptr(), per, S0 + t * B * 48 if fz else None,
-                                          N0 + t * B * 48 if fz and meas else None, _ptr(x_meas), xref.data_ptr(),
+                                          tape.plan_u.data_ptr(), per, *meas_in, _ptr(x_meas), xref.data_ptr(),
                                           uref.data_ptr(), sp),
                    "tt_sim_window_device")
             self.solver.vjp_device(B, tape.X[t].data_ptr(), tape.U[t].data_ptr(), tape.dual[t].data_ptr(),
                                    xref.data_ptr(), uref.data_ptr(), tape.status[t].data_ptr(), grad_u=gU.data_ptr(),
                                    g_x0=g_x0.data_ptr(), g_xref=g_xr.data_ptr(), g_uref=g_ur.data_ptr(),
-                                   g_wq_wr=g_ws.data_ptr(), wq_wr=W0 + t * B * 64 if fz else wq,
-                                   stream=s.cuda_stream,
-                                   g_model=g_ms.data_ptr() if model else 0, accumulate=True)
-            wv = (B, N, int(tape.ks[t]), int(Np), g_xr.data_ptr(), g_ur.data_ptr(), g_px.data_ptr(), g_pu.data_ptr(),
-                  g_x0.data_ptr(), GS[t].data_ptr(), a.data_ptr(), g_ws.data_ptr(), g_w.data_ptr(),
-                  g_n[t].data_ptr() if meas else None)
-            if fz:
-                _check(L.tt_sim_window_vjp_fuzzy_device(*wv, rs, x_meas.data_ptr(), xref.data_ptr(),
-                                                        R0 + t * B * 4, _ptr(g_th), sp),
-                       "tt_sim_window_vjp_fuzzy_device")
-            else:
-                _check(L.tt_sim_window_vjp_device(*wv, sp), "tt_sim_window_vjp_device")
+                                   g_wq_wr=g_ws.data_ptr(), wq_wr=w_t, stream=s.cuda_stream, g_model=g_model,
+                                   accumulate=True)
+            _check(win_vjp(B, N, int(tape.ks[t]), int(Np), g_xr.data_ptr(), g_ur.data_ptr(), g_px.data_ptr(),
+                           g_pu.data_ptr(), g_x0.data_ptr(), GS[t].data_ptr(), a.data_ptr(), g_ws.data_ptr(),
+                           g_w.data_ptr(), g_n[t].data_ptr() if meas else None, *win_tail), win_name)
         with torch.cuda.stream(s):
             if not per:
                 g_px, g_pu = g_px.sum(dim=0, keepdim=True), g_pu.sum(dim=0, keepdim=True)

@@ -8,7 +8,7 @@ where the retry was taken.
 
 * ``rule_weights`` / ``rule_vjp``: the rule and its adjoint table, vectorised over leading axes.
 * ``rule_kink_distance``: how far a point is from every kink and switch of the rule.
-* ``sweep``: lr.sweep with the rule adjoint between the solve adjoint and the state accumulation.
+* ``chain``: lr.sweep on a tape, with the rule adjoint between the solve adjoint and the state accumulation.
 * ``fuzzy_case`` and the oracle helpers: the issue's loop (``to.closed_loop(policy="fuzzy", fuzzy=True)`` with the rule
   patched into ``oracle.ttmpc_oracle.fuzzy_weights``), its tape, its central differences, forced first-attempt failures.
 """
@@ -87,71 +87,23 @@ def rule_kink_distance(theta, psi, v, ref_v, settings=SETTINGS):
 
 
 # ---- the sweep --------------------------------------------------------------------------------------------------
-def sweep(solve_vjp, policy, ks, Np, S, status, active, count, GS, GU, p, dist=None, in_plant=False, theta=None,
-          x_meas=None, ref_v=None, retried=None, settings=SETTINGS):
-    """lr.sweep for a rule loop: x_meas (K,B,6), ref_v (K,B) = xref_t[0][5], retried (K,B).  After the solve adjoint of
-    step t, g["w"] goes through ``rule_vjp`` (nothing where retried): g_x0[3] += g_psi before the state accumulation
-    (so the measurement-noise gradient carries it too), theta (B,7) += g_theta.  out["w"] is sum_t dL/dW_t.  With
-    theta None this is lr.sweep plus a zero theta group."""
-    K, B = status.shape
-    a, abar = np.array(GS[K], dtype=np.float64), np.zeros((B, 2))
-    out = {"w": np.zeros((B, 8)), "noise": np.zeros((K, B, 6)), "plan_x": np.zeros((B, Np + 1, 6)),
-           "plan_u": np.zeros((B, Np, 2)), "theta": np.zeros((B, 7)), "rule_terms": np.zeros((K, B, 7))}
-    for t in range(K - 1, -1, -1):
-        a, abar, g_u0, gn = lr.policy_plant_vjp(policy, S[t], status[t], None if t == 0 else active[t - 1], active[t],
-                                                count[t], GU[t], a, abar, p, dist, in_plant)
-        g = solve_vjp(t, g_u0)
-        gx0 = np.array(g["x0"], dtype=np.float64)
-        if theta is not None:
-            g_psi, g_th = rule_vjp(theta, x_meas[t][:, 3], x_meas[t][:, 5], ref_v[t], g["w"], settings)
-            live = np.asarray(retried[t]) == 0
-            gx0[:, 3] = np.where(live, gx0[:, 3] + g_psi, gx0[:, 3])
-            out["rule_terms"][t] = np.where(live[:, None], g_th, 0.0)
-            out["theta"] += out["rule_terms"][t]
-        a = (a + gx0) + GS[t]
-        out["w"] += g["w"]
-        out["noise"][t] = gn if in_plant else gx0
-        lr.window_vjp(g["xref"], g["uref"], ks[t], Np, out["plan_x"], out["plan_u"])
-    out["x_init"] = a
-    return out
-
-
-def solve_vjp_from_tape(nlp, fn, X, U, dual, status, ks, plan_x, plan_u, W):
-    """lr.solve_vjp_from_tape with each step's own weights W (K,B,8)."""
-    N = nlp.N
-
-    def cb(t, g_u0):
-        B = g_u0.shape[0]
-        Xr, Ur = to.reference_window(plan_x, plan_u, ks[t], N)
-        out = {"x0": np.zeros((B, 6)), "xref": np.zeros((B, N + 1, 6)), "uref": np.zeros((B, N, 2)), "w": np.zeros((B, 8))}
-        for b in range(B):
-            if status[t, b] > 1:
-                continue
-            gU = np.zeros((N, 2))
-            gU[0] = g_u0[b]
-            r = fn(nlp, nlp.pack(X[t, b], U[t, b]), dual[t, b], Xr.T, Ur.T, np.zeros((N + 1, 6)), gU, W[t, b, :6],
-                   W[t, b, 6:])
-            for key in out:
-                out[key][b] = r[key]
-        return out
-    return cb
-
-
 def window_ref_v(plan_x, ks, Np, B):
     """ref_v (K,B) of a shared plan (6,Np+1): the speed of the window's first row."""
     return np.array([[plan_x[5, min(k, Np)]] * B for k in ks])
 
 
-def chain(c, fn, tp, in_plant=True, policy="fuzzy", theta=None):
-    """The numpy sweep on a tape dict (S, status, active, consec|count, X, U, dual, W, retried) of the case."""
+def chain(c, fn, tp, in_plant=True, policy="fuzzy", theta=None, settings=SETTINGS):
+    """``lr.chain`` on a tape dict that also has W and retried: the sweep at each step's own weights, with ``rule_vjp``
+    (nothing where retried) as its rule term."""
     theta = c["theta"] if theta is None else theta
     K, B = tp["status"].shape
-    cb = solve_vjp_from_tape(c["nlp"], fn, tp["X"], tp["U"], tp["dual"], tp["status"], c["ks"], c["plan_x"], c["plan_u"],
-                             tp["W"])
     x_meas = tp["S"][:K] if in_plant else tp["S"][:K] + c["noise"]
-    count = tp["count"] if "count" in tp else tp["consec"]
-    return sweep(cb, policy, c["ks"], c["Np"], tp["S"], tp["status"], tp["active"], count, c["GS"], c["GU"], P, DIST,
-                 in_plant, theta, x_meas, window_ref_v(c["plan_x"], c["ks"], c["Np"], B), tp["retried"])
+    ref_v = window_ref_v(c["plan_x"], c["ks"], c["Np"], B)
+
+    def rule(t, g_w):
+        return (*rule_vjp(theta, x_meas[t][:, 3], x_meas[t][:, 5], ref_v[t], g_w, settings),
+                np.asarray(tp["retried"][t]) == 0)
+    return lr.chain(c, fn, tp, policy, in_plant, rule_vjp=rule)
 
 
 # ---- the issue's loop on the CPU oracle ---------------------------------------------------------------------------
@@ -225,76 +177,18 @@ def oracle_loop(c, x_init, noise, theta=None, plan_x=None, plan_u=None, tape=Non
 
 def oracle_tape(c, force=None):
     """The oracle's own run with each step's accepted solution, weights and interior multipliers: what ``chain`` needs."""
-    from test_vjp_reference import _interior_dual
-    nlp, N, B, K = c["nlp"], c["N"], c["B"], c["K"]
-    rec = []
-    S, Ua, st = oracle_loop(c, c["x_init"], c["noise"], tape=rec, force=force)
-    X, U, W = (np.array([r[k] for r in rec]) for k in ("X", "U", "W"))
-    retried = np.array([r["retried"] for r in rec])
-    dual = np.zeros((K, B, N + 1, 22))
-    for t in range(K):
-        Xr, Ur = to.reference_window(c["plan_x"], c["plan_u"], c["ks"][t], N)
-        for b in range(B):
-            z = nlp.pack(X[t, b], U[t, b])
-            y = nlp.kkt_residual(z, rec[t]["x_meas"][b], Xr, Ur, W[t, b, :6], W[t, b, 6:])["y"].reshape(N + 1, 6)
-            dual[t, b] = _interior_dual(nlp, z, y)
-    return dict(S=S, Ua=Ua, status=st, active=np.ones((K, B), dtype=np.int32), count=np.zeros((K, B), dtype=np.int32),
-                X=X, U=U, dual=dual, W=W, retried=retried, x_meas=np.array([r["x_meas"] for r in rec]))
+    return lr.oracle_tape(c, run=lambda rec: oracle_loop(c, c["x_init"], c["noise"], tape=rec, force=force))
 
 
 def oracle_fd(c, h=1e-4, force=None, plan_entries=None):
-    """Central differences of L = sum(GS * S) + sum(GU * Ua) over ``oracle_loop``.  x_init and noise: one loop whose
-    instances are the perturbed copies of the instance each entry belongs to (a forced failure follows its owner).
-    theta: two loops per entry, differentiated per instance (L is a sum over the instances).  The shared plan: two
-    loops per entry, summed over B.  force: {t: instance b}.
+    """``lr.central_differences`` of ``oracle_loop``: x_init and noise in one loop of perturbed copies (a forced failure
+    follows its owner), theta per instance, the shared plan summed over B.  force: {t: instance b}.
     -> (dict(x_init (B,6), noise (K,B,6), theta (B,7), plan_x {(r, i): v}, plan_u {(r, i): v}), every final status 0)."""
-    B, K, GS, GU = c["B"], c["K"], c["GS"], c["GU"]
     force = force or {}
-    owners, xs, ns = [], [], []
-    for name, arr in (("x_init", c["x_init"]), ("noise", c["noise"])):
-        for idx in np.ndindex(arr.shape):
-            b = idx[0] if name == "x_init" else idx[1]
-            for sgn in (1.0, -1.0):
-                x, n = c["x_init"][b].copy(), c["noise"][:, b].copy()
-                if name == "x_init":
-                    x[idx[1]] += sgn * h
-                else:
-                    n[idx[0], idx[2]] += sgn * h
-                owners.append((name, idx, b))
-                xs.append(x), ns.append(n)
-    own_b = np.array([o[2] for o in owners])
-    S, Ua, st = oracle_loop(c, np.array(xs), np.array(ns).transpose(1, 0, 2),
-                            force={t: own_b == b for t, b in force.items()})
-    ok = bool(np.all(st == 0))
-    out = {"x_init": np.zeros((B, 6)), "noise": np.zeros((K, B, 6)), "theta": np.zeros((B, 7)), "plan_x": {}, "plan_u": {}}
-    for m in range(0, len(owners), 2):
-        name, idx, b = owners[m]
-        L = [float(np.sum(GS[:, b] * S[:, m + d]) + np.sum(GU[:, b] * Ua[:, m + d])) for d in (0, 1)]
-        out[name][idx] = (L[0] - L[1]) / (2.0 * h)
-    small = {t: np.arange(B) == b for t, b in force.items()}
-    for i in range(7):
-        L = []
-        for sgn in (1.0, -1.0):
-            th = np.array(c["theta"], dtype=np.float64)
-            th[i] += sgn * h
-            S, Ua, st = oracle_loop(c, c["x_init"], c["noise"], theta=th, force=small)
-            ok = ok and bool(np.all(st == 0))
-            L.append(np.sum(GS * S, axis=(0, 2)) + np.sum(GU * Ua, axis=(0, 2)))
-        out["theta"][:, i] = (L[0] - L[1]) / (2.0 * h)
-    Np = c["Np"]
-    if plan_entries is None:
-        plan_entries = [("plan_x", r, i) for r in range(Np + 1) for i in range(6)] + \
-                       [("plan_u", r, i) for r in range(Np) for i in range(2)]
-    for name, r, i in plan_entries:
-        L = []
-        for sgn in (1.0, -1.0):
-            px, pu = c["plan_x"].copy(), c["plan_u"].copy()
-            (px if name == "plan_x" else pu)[i, r] += sgn * h
-            S, Ua, st = oracle_loop(c, c["x_init"], c["noise"], plan_x=px, plan_u=pu, force=small)
-            ok = ok and bool(np.all(st == 0))
-            L.append(float(np.sum(GS * S) + np.sum(GU * Ua)))
-        out[name][(r, i)] = (L[0] - L[1]) / (2.0 * h)
-    return out, ok
+    return lr.central_differences(
+        c, lambda i, owners: oracle_loop(c, i["x_init"], i["noise"], i["theta"], i["plan_x"], i["plan_u"],
+                                         force={t: owners == b for t, b in force.items()}),
+        ("x_init", "noise"), {"theta": c["theta"]}, h, plan_entries)
 
 
 def fd_errors(g, fd):
@@ -308,9 +202,5 @@ def fd_errors(g, fd):
             "theta": float(np.max(np.abs(g["theta"] - fd["theta"])))}
 
 
-def group_err(a, b):
-    return {g: float(np.max(np.abs(np.asarray(a[g]) - np.asarray(b[g])))) for g in GROUPS}
-
-
 def group_max(a):
-    return {g: float(np.max(np.abs(np.asarray(a[g])))) for g in GROUPS}
+    return lr.group_max(a, GROUPS)

@@ -193,56 +193,91 @@ def window_vjp(g_xref, g_uref, k, Np, acc_x, acc_u):
 
 
 # ---- the sweep --------------------------------------------------------------------------------------------------
-def sweep(solve_vjp, policy, ks, Np, S, status, active, count, GS, GU, p, dist=None, in_plant=False):
+def sweep(solve_vjp, policy, ks, Np, S, status, active, count, GS, GU, p, dist=None, in_plant=False, rule_vjp=None,
+          plant_model_vjp=None):
     """The backward pass over logged S (K+1,B,6), status / active / count (K,B) (active, count: after the step).
     solve_vjp(t, g_u0 (B,2)) -> dict(x0 (B,6), xref (B,N+1,6), uref (B,N,2), w (B,8)): the solve adjoint of step t for
     the upstream gradient dL/dU_t[0] = g_u0 (zeros for an instance whose status is above 1).
     Returns dict(x_init (B,6), w (B,8), noise (K,B,6), plan_x (B,Np+1,6), plan_u (B,Np,2)): the noise gradient is the
-    measurement noise's (g_x0 of each step), or with in_plant the plant noise's."""
+    measurement noise's (g_x0 of each step), or with in_plant the plant noise's.
+
+    Three optional terms ride along, each through a callable so that this module needs neither of the two that own them:
+    * rule_vjp(t, g_w (B,8)) -> (g_psi (B,), g_theta (B,7), live (B,) bool), a rule loop's weights w_t = rule(x_meas_t,
+      xref_t[0]): where live, g_x0[3] += g_psi before the state accumulation (so the measurement-noise gradient carries
+      it too) and theta (B,7) += g_theta, kept per step in rule_terms (K,B,7).  w is then sum_t dL/dW_t.
+    * plant_model_vjp(S_t, a, p, dist) -> a' dS_{t+1}/d(L1, L2, M) (B,3), with a = dL/dS_{t+1} before the J_q product:
+      model_plant (B,3); stopped and inactive instances add nothing.
+    * a solve adjoint that also returns model (B,3): model_solver (B,3) is their sum over the steps."""
     K, B = status.shape
     a, abar = np.array(GS[K], dtype=np.float64), np.zeros((B, 2))
     out = {"w": np.zeros((B, 8)), "noise": np.zeros((K, B, 6)), "plan_x": np.zeros((B, Np + 1, 6)),
            "plan_u": np.zeros((B, Np, 2))}
+    if rule_vjp is not None:
+        out.update(theta=np.zeros((B, 7)), rule_terms=np.zeros((K, B, 7)))
+    if plant_model_vjp is not None:
+        out.update(model_solver=np.zeros((B, 3)), model_plant=np.zeros((B, 3)))
     for t in range(K - 1, -1, -1):
+        if plant_model_vjp is not None:
+            before = np.ones(B, dtype=bool) if t == 0 else np.asarray(active[t - 1]) != 0
+            moved = before & (np.asarray(active[t]) != 0)
+            out["model_plant"] += np.where(moved[:, None], plant_model_vjp(S[t], a, p, dist), 0.0)
         a, abar, g_u0, gn = policy_plant_vjp(policy, S[t], status[t], None if t == 0 else active[t - 1], active[t],
                                              count[t], GU[t], a, abar, p, dist, in_plant)
         g = solve_vjp(t, g_u0)
-        a = (a + g["x0"]) + GS[t]
+        gx0 = np.array(g["x0"], dtype=np.float64)
+        if rule_vjp is not None:
+            g_psi, g_th, live = rule_vjp(t, g["w"])
+            gx0[:, 3] = np.where(live, gx0[:, 3] + g_psi, gx0[:, 3])
+            out["rule_terms"][t] = np.where(live[:, None], g_th, 0.0)
+            out["theta"] += out["rule_terms"][t]
+        a = (a + gx0) + GS[t]
         out["w"] += g["w"]
-        out["noise"][t] = gn if in_plant else g["x0"]
+        out["noise"][t] = gn if in_plant else gx0
         window_vjp(g["xref"], g["uref"], ks[t], Np, out["plan_x"], out["plan_u"])
+        if "model" in g:
+            out["model_solver"] += g["model"]
     out["x_init"] = a
     return out
 
 
-def solve_vjp_from_tape(nlp, fn, X, U, dual, status, ks, plan_x, plan_u, w=None):
+def solve_vjp_from_tape(nlp, fn, X, U, dual, status, ks, plan_x, plan_u, w=None, keys=("x0", "xref", "uref", "w")):
     """The callback for ``sweep`` from a taped run: fn = vjp_reference.dense_vjp or riccati_vjp on step t's (X, U, dual)
-    (K,B,...) and the window of the shared plan (6,Np+1), (2,Np); failed solves give zeros, as the kernel does."""
+    (K,B,...) and the window of the shared plan (6,Np+1), (2,Np); failed solves give zeros, as the kernel does.
+    w: the weights of the run (B,8), of each step (K,B,8), or None.  keys: what is taken from fn's result; the others
+    stay zeros, and "model" (B,3) is one more (model_vjp_reference.chain)."""
     N = nlp.N
 
     def cb(t, g_u0):
         B = g_u0.shape[0]
         Xr, Ur = to.reference_window(plan_x, plan_u, ks[t], N)
         out = {"x0": np.zeros((B, 6)), "xref": np.zeros((B, N + 1, 6)), "uref": np.zeros((B, N, 2)), "w": np.zeros((B, 8))}
+        if "model" in keys:
+            out["model"] = np.zeros((B, 3))
+        wt = w if w is None or w.ndim == 2 else w[t]
         for b in range(B):
             if status[t, b] > 1:
                 continue
             gU = np.zeros((N, 2))
             gU[0] = g_u0[b]
-            wq, wr = (None, None) if w is None else (w[b, :6], w[b, 6:])
+            wq, wr = (None, None) if wt is None else (wt[b, :6], wt[b, 6:])
             r = fn(nlp, nlp.pack(X[t, b], U[t, b]), dual[t, b], Xr.T, Ur.T, np.zeros((N + 1, 6)), gU, wq, wr)
-            for key in out:
+            for key in keys:
                 out[key][b] = r[key]
         return out
     return cb
 
 
-def group_err(a, b):
-    return {g: float(np.max(np.abs(np.asarray(a[g]) - np.asarray(b[g])))) for g in GROUPS}
+def chain(c, fn, tp, policy="track", in_plant=False, keys=("x0", "xref", "uref", "w"), **terms):
+    """``sweep`` on a tape dict of the case (S, status, active, consec|count, X, U, dual[, W]: a GPU tape as numpy, or
+    ``oracle_tape``'s) with fn per step, at the tape's per-step weights W if it has them, else at the case's."""
+    cb = solve_vjp_from_tape(c["nlp"], fn, tp["X"], tp["U"], tp["dual"], tp["status"], c["ks"], c["plan_x"], c["plan_u"],
+                             tp["W"] if "W" in tp else c["w"], keys)
+    return sweep(cb, policy, c["ks"], c["Np"], tp["S"], tp["status"], tp["active"],
+                 tp["count"] if "count" in tp else tp["consec"], c["GS"], c["GU"], P, DIST, in_plant, **terms)
 
 
-def group_max(a):
-    return {g: float(np.max(np.abs(np.asarray(a[g])))) for g in GROUPS}
+def group_max(a, groups=GROUPS):
+    return {g: float(np.max(np.abs(np.asarray(a[g])))) for g in groups}
 
 
 # ---- the issue's inputs -------------------------------------------------------------------------------------------
@@ -270,7 +305,7 @@ def loop_case(golden_ref):
 
 def oracle_solver(nlp, w, tape=None):
     """solve(x, Xr, Ur) for ``to.closed_loop`` on the C oracle with per-instance weights w (B,8); every call appends
-    (x_meas, X, U, status) to ``tape`` when one is given."""
+    dict(x_meas, X, U, status) to ``tape`` when one is given."""
     import sens_reference as sr
     from oracle import c_oracle as co
     from ttmpc import layout
@@ -280,7 +315,7 @@ def oracle_solver(nlp, w, tape=None):
         z, st, _, _ = co.solve_batch(Pp, x, Xr, Ur, wq=w[:, :6], wr=w[:, 6:])
         X, Uo = layout.unpack(z, nlp.N)
         if tape is not None:
-            tape.append((np.array(x), X, Uo, np.array(st)))
+            tape.append(dict(x_meas=np.array(x), X=X, U=Uo, status=np.array(st)))
         return X, Uo, st
     return solve
 
@@ -293,66 +328,100 @@ def oracle_loop(c, x_init, w, noise, plan_x=None, plan_u=None, in_plant=False, t
                           None if in_plant else noise, plant_noise=noise if in_plant else None)[:3]
 
 
-def oracle_fd(c, h=1e-4, in_plant=False, plan_entries=None):
-    """Central differences of L = sum(GS * S) + sum(GU * Ua) over ``oracle_loop``.  L is a sum over the instances, so
-    every entry of x_init, w and noise is differentiated in ONE loop whose instances are the perturbed copies of the
-    instance the entry belongs to.  The plan is shared: each of its entries (plan_entries: (name, column, row) with the
-    oracle's (6,Np+1) / (2,Np) orientation, default all) takes two loops and gives the gradient summed over B.
-    -> (dict(x_init (B,6), w (B,8), noise (K,B,6), plan_x {(r, i): v}, plan_u {(r, i): v}), every status 0)."""
-    B, K = c["B"], c["K"]
-    GS, GU = c["GS"], c["GU"]
-    owners, xs, ws, ns = [], [], [], []
-    for name, arr in (("x_init", c["x_init"]), ("w", c["w"]), ("noise", c["noise"])):
-        for idx in np.ndindex(arr.shape):
-            b = idx[0] if name != "noise" else idx[1]
+def central_differences(c, run, groups, shared=None, h=1e-4, plan_entries=None):
+    """Central differences of L = sum(GS * S) + sum(GU * Ua) over run(inputs, owners) -> (S, Ua, status): an oracle loop
+    of the case on ``inputs``, a dict with every differentiated input of the case, some replaced; owners (n,): the
+    instance of the case each of the loop's n instances is (a copy of).
+    * groups: per-instance inputs (c[name] with the instances on axis 0, "noise" on axis 1).  L is a sum over the
+      instances, so every entry of all of them is differentiated in ONE loop whose instances are the perturbed copies of
+      the instance the entry belongs to.
+    * shared {name: vector}: inputs all instances share, differentiated per instance: two loops per entry, -> (B, n).
+    * the shared plan: each of its entries (plan_entries: (name, column, row) with the oracle's (6,Np+1) / (2,Np)
+      orientation, default all) takes two loops and gives the gradient summed over B, -> {(r, i): v}.
+    -> (dict of them all, every status 0)."""
+    B, GS, GU = c["B"], c["GS"], c["GU"]
+    shared = shared or {}
+    base = dict({k: c[k] for k in (*groups, "plan_x", "plan_u")}, **shared)
+    axis = lambda name: 1 if name == "noise" else 0  # noqa: E731
+    out, ok = {"plan_x": {}, "plan_u": {}}, True
+    owners, rows = [], {g: [] for g in groups}
+    for name in groups:
+        out[name] = np.zeros(c[name].shape)
+        for idx in np.ndindex(c[name].shape):
+            b = idx[axis(name)]
             for sgn in (1.0, -1.0):
-                x, w, n = c["x_init"][b].copy(), c["w"][b].copy(), c["noise"][:, b].copy()
-                if name == "x_init":
-                    x[idx[1]] += sgn * h
-                elif name == "w":
-                    w[idx[1]] += sgn * h
-                else:
-                    n[idx[0], idx[2]] += sgn * h
+                row = {g: np.take(c[g], b, axis=axis(g)).copy() for g in groups}
+                row[name][idx[:axis(name)] + idx[axis(name) + 1:]] += sgn * h
                 owners.append((name, idx, b))
-                xs.append(x), ws.append(w), ns.append(n)
-    S, Ua, st = oracle_loop(c, np.array(xs), np.array(ws), np.array(ns).transpose(1, 0, 2), in_plant=in_plant)
-    ok = bool(np.all(st == 0))
-    out = {"x_init": np.zeros((B, 6)), "w": np.zeros((B, 8)), "noise": np.zeros((K, B, 6)), "plan_x": {}, "plan_u": {}}
-    for m in range(0, len(owners), 2):
-        name, idx, b = owners[m]
-        L = [float(np.sum(GS[:, b] * S[:, m + d]) + np.sum(GU[:, b] * Ua[:, m + d])) for d in (0, 1)]
-        out[name][idx] = (L[0] - L[1]) / (2.0 * h)
+                for g in groups:
+                    rows[g].append(row[g])
+    if owners:
+        S, Ua, st = run(dict(base, **{g: np.moveaxis(np.array(rows[g]), 0, axis(g)) for g in groups}),
+                        np.array([o[2] for o in owners]))
+        ok = bool(np.all(st == 0))
+        for m in range(0, len(owners), 2):
+            name, idx, b = owners[m]
+            L = [float(np.sum(GS[:, b] * S[:, m + d]) + np.sum(GU[:, b] * Ua[:, m + d])) for d in (0, 1)]
+            out[name][idx] = (L[0] - L[1]) / (2.0 * h)
+
+    def two_loops(name, changed, total):
+        nonlocal ok
+        L = []
+        for sgn in (1.0, -1.0):
+            S, Ua, st = run(dict(base, **{name: changed(sgn * h)}), np.arange(B))
+            ok = ok and bool(np.all(st == 0))
+            L.append(total(GS * S) + total(GU * Ua))
+        return (L[0] - L[1]) / (2.0 * h)
+
+    def bumped(v, at):
+        def changed(d):
+            w = np.array(v, dtype=np.float64)
+            w[at] += d
+            return w
+        return changed
+
+    for name, v in shared.items():
+        out[name] = np.zeros((B, len(v)))
+        for i in range(len(v)):
+            out[name][:, i] = two_loops(name, bumped(v, i), lambda x: np.sum(x, axis=(0, 2)))
     Np = c["Np"]
     if plan_entries is None:
         plan_entries = [("plan_x", r, i) for r in range(Np + 1) for i in range(6)] + \
                        [("plan_u", r, i) for r in range(Np) for i in range(2)]
     for name, r, i in plan_entries:
-        L = []
-        for sgn in (1.0, -1.0):
-            px, pu = c["plan_x"].copy(), c["plan_u"].copy()
-            (px if name == "plan_x" else pu)[i, r] += sgn * h
-            S, Ua, st = oracle_loop(c, c["x_init"], c["w"], c["noise"], px, pu, in_plant=in_plant)
-            ok = ok and bool(np.all(st == 0))
-            L.append(float(np.sum(GS * S) + np.sum(GU * Ua)))
-        out[name][(r, i)] = (L[0] - L[1]) / (2.0 * h)
+        out[name][(r, i)] = two_loops(name, bumped(c[name], (i, r)), lambda x: float(np.sum(x)))
     return out, ok
 
 
-def oracle_tape(c, in_plant=False):
+def oracle_fd(c, h=1e-4, in_plant=False, plan_entries=None):
+    """``central_differences`` of ``oracle_loop``.
+    -> (dict(x_init (B,6), w (B,8), noise (K,B,6), plan_x {(r, i): v}, plan_u {(r, i): v}), every status 0)."""
+    return central_differences(c, lambda i, owners: oracle_loop(c, i["x_init"], i["w"], i["noise"], i["plan_x"],
+                                                                i["plan_u"], in_plant=in_plant),
+                               ("x_init", "w", "noise"), None, h, plan_entries)
+
+
+def oracle_tape(c, in_plant=False, run=None):
     """The oracle's own run of the case with each step's solution and interior multipliers (mu / slack on every finite
-    relaxed bound, y from the stationarity least squares): what ``sweep`` needs.
-    -> dict(S, Ua, status, active, count, X (K,B,N+1,6), U (K,B,N,2), dual (K,B,N+1,22))."""
+    relaxed bound, y from the stationarity least squares): what ``sweep`` needs.  run(rec) -> (S, Ua, status): another
+    loop of the case that appends one dict(x_meas, X, U[, W, retried]) per step to rec, W (B,8) being the weights the
+    accepted solves used (default: ``oracle_loop``, whose weights are the case's).
+    -> dict(S, Ua, status, active, count, X (K,B,N+1,6), U (K,B,N,2), dual (K,B,N+1,22)[, W, retried, x_meas])."""
     from test_vjp_reference import _interior_dual
     nlp, N, B, K = c["nlp"], c["N"], c["B"], c["K"]
     rec = []
-    S, Ua, st = oracle_loop(c, c["x_init"], c["w"], c["noise"], in_plant=in_plant, tape=rec)
-    X, U = np.array([r[1] for r in rec]), np.array([r[2] for r in rec])
+    S, Ua, st = run(rec) if run else oracle_loop(c, c["x_init"], c["w"], c["noise"], in_plant=in_plant, tape=rec)
+    X, U = np.array([r["X"] for r in rec]), np.array([r["U"] for r in rec])
+    W = np.array([r["W"] for r in rec]) if run else np.broadcast_to(c["w"], (K, B, 8))
     dual = np.zeros((K, B, N + 1, 22))
     for t in range(K):
         Xr, Ur = to.reference_window(c["plan_x"], c["plan_u"], c["ks"][t], N)
         for b in range(B):
             z = nlp.pack(X[t, b], U[t, b])
-            y = nlp.kkt_residual(z, rec[t][0][b], Xr, Ur, c["w"][b, :6], c["w"][b, 6:])["y"].reshape(N + 1, 6)
+            y = nlp.kkt_residual(z, rec[t]["x_meas"][b], Xr, Ur, W[t, b, :6], W[t, b, 6:])["y"].reshape(N + 1, 6)
             dual[t, b] = _interior_dual(nlp, z, y)
-    return dict(S=S, Ua=Ua, status=st, active=np.ones((K, B), dtype=np.int32), count=np.zeros((K, B), dtype=np.int32),
-                X=X, U=U, dual=dual)
+    out = dict(S=S, Ua=Ua, status=st, active=np.ones((K, B), dtype=np.int32), count=np.zeros((K, B), dtype=np.int32),
+               X=X, U=U, dual=dual)
+    if run:
+        out.update(W=W, retried=np.array([r["retried"] for r in rec]), x_meas=np.array([r["x_meas"] for r in rec]))
+    return out

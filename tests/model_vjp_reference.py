@@ -13,7 +13,7 @@ c_{k+1} = x_{k+1} - x_k - dt f(x_k, u_k) and the -A_k' y_{k+1} part of the stati
   lam_y,k = r_k + A_k' lam_y,k+1 and the stage sums.
 * ``oracle_fd_model``: central differences of ``c_oracle.solve_batch`` on problems built with a perturbed parameter.
 * ``plant_model_vjp``: a' dS+/dtheta of ``to.plant_update``, as policy_plant_vjp_kernel's model instantiation forms it.
-* ``sweep_model``: the closed-loop chain, the solver's and the plant's geometry apart.
+* ``chain``: the closed-loop chain, ``loop_vjp_reference.sweep`` with the solver's and the plant's geometry terms.
 """
 from __future__ import annotations
 
@@ -184,42 +184,12 @@ def plant_model_vjp(q, a, p, dist=None):
 
 
 # ---- closed loop --------------------------------------------------------------------------------------------------
-def solve_vjp_from_tape(nlp, fn, X, U, dual, status, w=None):
-    """The callback for ``sweep_model``: fn = dense_model_vjp or riccati_model_vjp on step t's (X, U, dual) (K,B,...);
-    failed solves give zeros, as the kernel does.  -> cb(t, g_u0 (B,2)) = dict(x0 (B,6), model (B,3))."""
-    N = nlp.N
-
-    def cb(t, g_u0):
-        B = g_u0.shape[0]
-        out = {"x0": np.zeros((B, 6)), "model": np.zeros((B, 3))}
-        for b in range(B):
-            if status[t, b] > 1:
-                continue
-            gU = np.zeros((N, 2))
-            gU[0] = g_u0[b]
-            wq, wr = (None, None) if w is None else (w[b, :6], w[b, 6:])
-            r = fn(nlp, nlp.pack(X[t, b], U[t, b]), dual[t, b], np.zeros((N + 1, 6)), gU, wq, wr)
-            out["x0"][b], out["model"][b] = r["x0"], r["model"]
-        return out
-    return cb
-
-
-def sweep_model(solve_vjp, policy, S, status, active, count, GS, GU, p_plant, dist=None, in_plant=False):
-    """``loop_vjp_reference.sweep`` carrying the two geometry gradients: -> (g_model_solver (B,3), g_model_plant (B,3)).
-    The plant's term uses a = dL/dS_{t+1} before the J_q product; stopped and inactive instances add nothing."""
-    K, B = status.shape
-    a, abar = np.array(GS[K], dtype=np.float64), np.zeros((B, 2))
-    gs, gp = np.zeros((B, 3)), np.zeros((B, 3))
-    for t in range(K - 1, -1, -1):
-        before = np.ones(B, dtype=bool) if t == 0 else np.asarray(active[t - 1]) != 0
-        moved = before & (np.asarray(active[t]) != 0)
-        gp += np.where(moved[:, None], plant_model_vjp(S[t], a, p_plant, dist), 0.0)
-        a, abar, g_u0, _ = lv.policy_plant_vjp(policy, S[t], status[t], None if t == 0 else active[t - 1], active[t],
-                                               count[t], GU[t], a, abar, p_plant, dist, in_plant)
-        g = solve_vjp(t, g_u0)
-        a = (a + g["x0"]) + GS[t]
-        gs += g["model"]
-    return gs, gp
+def chain(c, fn, tp, policy="track", in_plant=False):
+    """``lv.chain`` with fn = dense_model_vjp or riccati_model_vjp, carrying the two geometry gradients: model_solver
+    (B,3), the solves' terms (fn behind the signature the tape callback calls: the window is no input of theirs), and
+    model_plant (B,3), ``plant_model_vjp`` of every step."""
+    return lv.chain(c, lambda nlp, z, dual, Xr, Ur, gX, gU, wq, wr: fn(nlp, z, dual, gX, gU, wq, wr), tp, policy,
+                    in_plant, keys=("x0", "model"), plant_model_vjp=plant_model_vjp)
 
 
 def oracle_loop(c, p_solver, p_plant, in_plant=False, tape=None, dist=lv.DIST):
@@ -234,15 +204,8 @@ def oracle_loop(c, p_solver, p_plant, in_plant=False, tape=None, dist=lv.DIST):
 def oracle_loop_fd(c, in_plant=False, h=1e-4):
     """Central differences of L = sum(GS * S) + sum(GU * Ua) per instance in the solver's and in the plant's geometry.
     -> (g_model_solver (B,3), g_model_plant (B,3), every status 0)."""
-    out, ok = [np.zeros((c["B"], 3)), np.zeros((c["B"], 3))], True
-    for who in (0, 1):
-        for i, name in enumerate(THETA):
-            L = []
-            for sgn in (1.0, -1.0):
-                ps, pp = dict(lv.P), dict(lv.P)
-                (ps, pp)[who][name] += sgn * h
-                S, Ua, st = oracle_loop(c, ps, pp, in_plant)
-                ok = ok and bool(np.all(st == 0))
-                L.append(np.sum(c["GS"] * S, axis=(0, 2)) + np.sum(c["GU"] * Ua, axis=(0, 2)))
-            out[who][:, i] = (L[0] - L[1]) / (2.0 * h)
-    return out[0], out[1], ok
+    params = lambda th: dict(lv.P, **dict(zip(THETA, (float(v) for v in th))))  # noqa: E731
+    fd, ok = lv.central_differences(
+        c, lambda i, owners: oracle_loop(c, params(i["model_solver"]), params(i["model_plant"]), in_plant), (),
+        {"model_solver": geometry(lv.P), "model_plant": geometry(lv.P)}, h, plan_entries=())
+    return fd["model_solver"], fd["model_plant"], ok

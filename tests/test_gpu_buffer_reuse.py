@@ -17,11 +17,12 @@ P = sr.P
 
 
 def _track_call(s, x0, xr, ur, w):
-    """solve_ex with every extra output and vjp on its outputs: all arrays of both results, by name."""
+    """solve_ex with every extra output and vjp (with the model gradient, so that every field of its result is an
+    array) on its outputs: all arrays of both results, by name."""
     r = s.solve_ex(x0, xr, ur, wq_wr=w, duals=True, gain=True, trajectory_sens=True)
     rng = np.random.default_rng(11)  # the same upstream gradient per instance at every B: rows are drawn in order
     gx, gu = rng.standard_normal((5,) + r.X.shape[1:])[:len(x0)], rng.standard_normal((5,) + r.U.shape[1:])[:len(x0)]
-    v = s.vjp(r.X, r.U, r.dual, xr, ur, r.status, gx, gu, wq_wr=w)
+    v = s.vjp(r.X, r.U, r.dual, xr, ur, r.status, gx, gu, wq_wr=w, model=True)
     out = {k: getattr(r, k) for k in r.__slots__}
     out.update({k: getattr(v, k) for k in v.__slots__})
     assert all(a is not None for a in out.values())

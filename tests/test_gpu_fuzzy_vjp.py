@@ -22,28 +22,19 @@ import numpy as np
 import pytest
 
 import fuzzy_vjp_reference as fr
+import vjp_harness as h
 import vjp_reference as vr
 
 pytestmark = pytest.mark.gpu
 
-P, DIST = fr.P, fr.DIST
-EPS = float(np.finfo(np.float64).eps)
+P, DIST, EPS = fr.P, fr.DIST, h.EPS
 SHAPES = [(1, 3, 0), (6, 8, 5), (6, 8, 9), (70, 100, 95)]
-
-
-def _t(a, dtype=None):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype or torch.float64).cuda()
-
-
-def _n(t):
-    return t.detach().cpu().numpy()
+_t, _n, _grads, _tape_np = h.t, h.n, h.grads, h.tape_np
 
 
 @functools.lru_cache(maxsize=None)
 def _case():
-    from conftest import GOLDEN
-    return fr.fuzzy_case(dict(np.load(GOLDEN / "reference_numpy.npz")))
+    return fr.fuzzy_case(h.golden())
 
 
 def _rule(theta=fr.THETA):
@@ -53,25 +44,8 @@ def _rule(theta=fr.THETA):
 
 def _loop(variant=None, tol=1e-8, per_instance=0, rule="case"):
     import ttmpc
-    from ttmpc import simulation as sim
-    c = _case()
-    nlp = c["nlp"]
-    solver = ttmpc.BatchSolver(nlp.N, P, nlp.Q, nlp.R, nlp.xlb, nlp.xub, nlp.ulb, nlp.uub, tol=tol,
-                               variant=ttmpc.TT_VARIANT_TRACK if variant is None else variant)
-    px, pu = c["plan_x"], c["plan_u"]
-    if per_instance:
-        px, pu = np.tile(px.T[None], (per_instance, 1, 1)), np.tile(pu.T[None], (per_instance, 1, 1))
-    return sim.ClosedLoop(solver, px, pu, P, DIST, policy="fuzzy", noise_in_plant=True,
-                          fuzzy_rule=_rule() if rule == "case" else rule)
-
-
-def _grads(g):
-    return {"x_init": _n(g["g_x_init"]), "w": _n(g["g_wq_wr"]), "noise": _n(g["g_noise"]), "plan_x": _n(g["g_plan_x"]),
-            "plan_u": _n(g["g_plan_u"]), "theta": _n(g["g_fuzzy_rule"])}
-
-
-def _tape_np(tape):
-    return {k: _n(getattr(tape, k)) for k in ("S", "Ua", "status", "active", "consec", "X", "U", "dual", "W", "retried")}
+    return h.loop(_case(), "fuzzy", True, per_instance, _rule() if rule == "case" else rule,
+                  solver_kw=dict(tol=tol, variant=ttmpc.TT_VARIANT_TRACK if variant is None else variant))
 
 
 def _states(n, rng):
@@ -216,21 +190,10 @@ def _oracle_fd(force=()):
     return fr.oracle_fd(_case(), h=1e-4, force=dict(force))
 
 
-def _shared(g):
-    g = dict(g)
-    g["plan_x"], g["plan_u"] = g["plan_x"].sum(axis=0, keepdims=True), g["plan_u"].sum(axis=0, keepdims=True)
-    return g
-
-
 def _compare_with_chain(tag, out, got):
-    c = _case()
-    tp = _tape_np(out["tape"])
-    dense, model = _shared(fr.chain(c, vr.dense_vjp, tp)), _shared(fr.chain(c, vr.riccati_vjp, tp))
-    e_gpu, e_model, big = fr.group_err(got, dense), fr.group_err(model, dense), fr.group_max(dense)
-    for k in fr.GROUPS:
-        print(f"{tag} {k:7s}: err_gpu {e_gpu[k]:.3e}, err_model {e_model[k]:.3e}, max|ref| {big[k]:.3e}")
-    for k in fr.GROUPS:
-        assert e_gpu[k] <= 10.0 * e_model[k] + 1e-12 * big[k], k
+    c, tp = _case(), _tape_np(out["tape"])
+    dense, model = (h.shared_plan(fr.chain(c, fn, tp)) for fn in (vr.dense_vjp, vr.riccati_vjp))
+    h.compare_with_chain(tag, got, dense, model, fr.GROUPS, per_group=True)
     return dense
 
 

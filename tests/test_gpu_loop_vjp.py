@@ -20,27 +20,13 @@ import numpy as np
 import pytest
 
 import loop_vjp_reference as lr
+import vjp_harness as h
 import vjp_reference as vr
 
 pytestmark = pytest.mark.gpu
 
-P = lr.P
-EPS = float(np.finfo(np.float64).eps)
-
-
-def _t(a, dtype=None):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype or torch.float64).cuda()
-
-
-def _n(t):
-    return t.detach().cpu().numpy()
-
-
-@functools.lru_cache(maxsize=None)
-def _golden():
-    from conftest import GOLDEN
-    return dict(np.load(GOLDEN / "reference_numpy.npz"))
+P, EPS = lr.P, h.EPS
+_t, _n, _golden, _solver, _grads = h.t, h.n, h.golden, h.solver, h.grads
 
 
 @functools.lru_cache(maxsize=None)
@@ -48,28 +34,8 @@ def _case():
     return lr.loop_case(_golden())
 
 
-def _solver(nlp, **kw):
-    import ttmpc
-    return ttmpc.BatchSolver(nlp.N, P, nlp.Q, nlp.R, nlp.xlb, nlp.xub, nlp.ulb, nlp.uub, **kw)
-
-
-def _loop(policy="track", in_plant=False, per_instance=0, **kw):
-    """The case's loop; per_instance = B gives every instance its own copy of the plan."""
-    from ttmpc import simulation as sim
-    c = _case()
-    px, pu = c["plan_x"], c["plan_u"]
-    if per_instance:
-        px, pu = np.tile(px.T[None], (per_instance, 1, 1)), np.tile(pu.T[None], (per_instance, 1, 1))
-    return sim.ClosedLoop(_solver(c["nlp"]), px, pu, P, lr.DIST, policy=policy, noise_in_plant=in_plant, **kw)
-
-
-def _grads(g):
-    return {"x_init": _n(g["g_x_init"]), "w": _n(g["g_wq_wr"]), "noise": _n(g["g_noise"]), "plan_x": _n(g["g_plan_x"]),
-            "plan_u": _n(g["g_plan_u"])}
-
-
-def _tape_np(tape):
-    return {k: _n(getattr(tape, k)) for k in ("S", "Ua", "status", "active", "consec", "X", "U", "dual")}
+def _loop(*a, **kw):
+    return h.loop(_case(), *a, **kw)
 
 
 @functools.lru_cache(maxsize=None)
@@ -87,24 +53,11 @@ def _run(policy="track", in_plant=False, fail=False):
     return loop, out, _grads(g), noise
 
 
-def _chain(fn, policy, in_plant, tp):
-    """The numpy sweep on a GPU tape with fn = dense_vjp or riccati_vjp per step; the plan is shared: sums over B."""
-    c = _case()
-    cb = lr.solve_vjp_from_tape(c["nlp"], fn, tp["X"], tp["U"], tp["dual"], tp["status"], c["ks"], c["plan_x"],
-                                c["plan_u"], c["w"])
-    g = lr.sweep(cb, policy, c["ks"], c["Np"], tp["S"], tp["status"], tp["active"], tp["consec"], c["GS"], c["GU"], P,
-                 lr.DIST, in_plant)
-    g["plan_x"], g["plan_u"] = g["plan_x"].sum(axis=0, keepdims=True), g["plan_u"].sum(axis=0, keepdims=True)
-    return g
-
-
 def _compare_with_chain(tag, policy, in_plant, out, got):
-    tp = _tape_np(out["tape"])
-    dense, model = _chain(vr.dense_vjp, policy, in_plant, tp), _chain(vr.riccati_vjp, policy, in_plant, tp)
-    e_gpu, e_model, big = lr.group_err(got, dense), lr.group_err(model, dense), lr.group_max(dense)
-    for k in lr.GROUPS:
-        print(f"{tag} {k:7s}: err_gpu {e_gpu[k]:.3e}, err_model {e_model[k]:.3e}, max|ref| {big[k]:.3e}")
-    assert max(e_gpu.values()) <= 10.0 * max(e_model.values()) + 1e-12 * max(big.values())
+    """Against the numpy sweep on the GPU's own tape, fn = dense_vjp and riccati_vjp per step; the plan is shared."""
+    c, tp = _case(), h.tape_np(out["tape"])
+    dense, model = (h.shared_plan(lr.chain(c, fn, tp, policy, in_plant)) for fn in (vr.dense_vjp, vr.riccati_vjp))
+    h.compare_with_chain(tag, got, dense, model, lr.GROUPS, per_group=False)
     return dense
 
 

@@ -23,6 +23,7 @@ import pytest
 
 import loop_vjp_reference as lr
 import lqr_vjp_reference as lv
+import vjp_harness as h
 
 pytestmark = pytest.mark.gpu
 
@@ -33,19 +34,7 @@ OUTS = ("g_x_cur", "g_x_goal", "g_Q", "g_R", "vjp_status", "doublings")
 GRADS = OUTS[:4]
 
 
-def _t(a, dtype=None):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype or torch.float64).cuda()
-
-
-def _n(t):
-    return t.detach().cpu().numpy()
-
-
-@functools.lru_cache(maxsize=None)
-def _golden():
-    from conftest import GOLDEN
-    return dict(np.load(GOLDEN / "reference_numpy.npz"))
+_t, _n, _golden = h.t, h.n, h.golden
 
 
 @functools.lru_cache(maxsize=None)
@@ -273,8 +262,7 @@ def test_composition_with_the_closed_loop(N, nb):
     from ttmpc import simulation as sim
     from ttmpc.diff import DifferentiableClosedLoop, DifferentiableLqrScore
     nlp, plan_x, plan_u, x_init, w, T = _loop_inputs(N, nb)
-    solver = ttmpc.BatchSolver(nlp.N, lr.P, nlp.Q, nlp.R, nlp.xlb, nlp.xub, nlp.ulb, nlp.uub)
-    loop = sim.ClosedLoop(solver, plan_x, plan_u, lr.P, lr.DIST, measurement_noise=False, policy="track")
+    loop = sim.ClosedLoop(h.solver(nlp), plan_x, plan_u, lr.P, lr.DIST, measurement_noise=False, policy="track")
     layer, score_layer = DifferentiableClosedLoop(loop), DifferentiableLqrScore(lr.P)
     px0, pu0 = _t(plan_x.T[None]), _t(plan_u.T[None])
 

@@ -24,6 +24,7 @@ import pytest
 import loop_vjp_reference as lv
 import model_vjp_reference as mr
 import sens_reference as sr
+import vjp_harness as h
 import vjp_reference as vr
 
 pytestmark = pytest.mark.gpu
@@ -36,22 +37,7 @@ OUTS = ("g_x0", "g_xref", "g_uref", "g_wq_wr", "vjp_status")
 CPU_FD_ERR = {("free", False): 3.3e-10, ("free", True): 4.3e-10, ("active", False): 4.6e-10, ("active", True): 5.2e-9}
 
 
-def _t(a, dtype=None):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype or torch.float64).cuda()
-
-
-def _n(t):
-    return t.detach().cpu().numpy()
-
-
-def _solver(nlp, params=P, **kw):
-    import ttmpc
-    return ttmpc.BatchSolver(nlp.N, params, nlp.Q, nlp.R, nlp.xlb, nlp.xub, nlp.ulb, nlp.uub, **kw)
-
-
-def _w(w, b):
-    return (None, None) if w is None else (w[b, :6], w[b, 6:])
+_t, _n, _solver, _w, _golden = h.t, h.n, h.solver, h.w_of, h.golden
 
 
 @functools.lru_cache(maxsize=None)
@@ -193,7 +179,7 @@ def test_neutrality(weighted):
     assert np.array_equal(v.g_model, model["g_model"])
     assert not plain["vjp_status"].any() and np.max(np.abs(model["g_model"])) > 1e-3
     old = s.vjp(r.X, r.U, r.dual, xr, ur, r.status, gX, gU, wq_wr=w)
-    assert type(old).__name__ == "TrackVjpResult" and not hasattr(old, "g_model")   # the old call's old result
+    assert type(old).__name__ == "TrackVjpResult" and old.g_model is None           # the old call asks for no g_model
     for k in OUTS:
         assert np.array_equal(getattr(old, k), plain[k]), k
 
@@ -300,12 +286,6 @@ def test_set_model_bad_calls():
 
 
 # ---- 6 ----------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _golden():
-    from conftest import GOLDEN
-    return dict(np.load(GOLDEN / "reference_numpy.npz"))
-
-
 @pytest.mark.parametrize("disturbed", [False, True])
 @pytest.mark.parametrize("policy", ["track", "nmpc", "fuzzy"])
 def test_plant_model_term_against_numpy_model(policy, disturbed):
@@ -354,14 +334,8 @@ def _case():
     return lv.loop_case(_golden())
 
 
-def _loop(policy="track", in_plant=False, per_instance=0, params=P, solver_params=P):
-    from ttmpc import simulation as sim
-    c = _case()
-    px, pu = c["plan_x"], c["plan_u"]
-    if per_instance:
-        px, pu = np.tile(px.T[None], (per_instance, 1, 1)), np.tile(pu.T[None], (per_instance, 1, 1))
-    return sim.ClosedLoop(_solver(c["nlp"], solver_params), px, pu, params, lv.DIST, policy=policy,
-                          noise_in_plant=in_plant)
+def _loop(*a, **kw):
+    return h.loop(_case(), *a, **kw)
 
 
 GROUPS = ("g_x_init", "g_wq_wr", "g_noise", "g_plan_x", "g_plan_u")
@@ -380,23 +354,12 @@ def _run(policy="track", in_plant=False, fail=False):
     return loop, out, g
 
 
-def _chain(fn, policy, in_plant, tape):
-    c = _case()
-    tp = {k: _n(getattr(tape, k)) for k in ("S", "status", "active", "consec", "X", "U", "dual")}
-    cb = mr.solve_vjp_from_tape(c["nlp"], fn, tp["X"], tp["U"], tp["dual"], tp["status"], c["w"])
-    return mr.sweep_model(cb, policy, tp["S"], tp["status"], tp["active"], tp["consec"], c["GS"], c["GU"], P, lv.DIST,
-                          in_plant)
-
-
 def _compare_with_chain(tag, policy, in_plant, out, g):
-    dense, model = (_chain(f, policy, in_plant, out["tape"]) for f in (mr.dense_model_vjp, mr.riccati_model_vjp))
-    big = 0.0
-    for name, got, d, m in zip(("solver", "plant"), (g["g_model_solver"], g["g_model_plant"]), dense, model):
-        e_gpu, e_model, smax = (float(np.max(np.abs(x))) for x in (got - d, m - d, d))
-        print(f"{tag} {name:6s}: err_gpu {e_gpu:.3e}, err_model {e_model:.3e}, max|ref| {smax:.3e}")
-        assert e_gpu <= 10.0 * e_model + 1e-12 * smax
-        big = max(big, smax)
-    return big
+    c, tp = _case(), h.tape_np(out["tape"])
+    dense, model = ({k: v[f"model_{k}"] for k in ("solver", "plant")} for v in
+                    (mr.chain(c, fn, tp, policy, in_plant) for fn in (mr.dense_model_vjp, mr.riccati_model_vjp)))
+    got = {k: g[f"g_model_{k}"] for k in ("solver", "plant")}
+    return max(h.compare_with_chain(tag, got, dense, model, ("solver", "plant"), per_group=True).values())
 
 
 @pytest.mark.parametrize("in_plant", [False, True])

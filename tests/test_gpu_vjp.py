@@ -15,24 +15,17 @@ import numpy as np
 import pytest
 
 import sens_reference as sr
+import vjp_harness as h
 import vjp_reference as vr
 
 pytestmark = pytest.mark.gpu
 
 P = sr.P
-
-
-def _solver(nlp, **kw):
-    import ttmpc
-    return ttmpc.BatchSolver(nlp.N, P, nlp.Q, nlp.R, nlp.xlb, nlp.xub, nlp.ulb, nlp.uub, **kw)
+_solver, _w = h.solver, h.w_of
 
 
 def _gpu(v, b):
     return {"x0": v.g_x0[b], "xref": v.g_xref[b], "uref": v.g_uref[b], "w": v.g_wq_wr[b]}
-
-
-def _w(w, b):
-    return (None, None) if w is None else (w[b, :6], w[b, 6:])
 
 
 @functools.lru_cache(maxsize=None)

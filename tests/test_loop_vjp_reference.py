@@ -47,10 +47,7 @@ def test_chain_against_oracle_loop_finite_differences(golden_ref, in_plant):
     assert np.all(tape["status"] == 0)
     umax = np.max(np.abs(tape["Ua"]), axis=(0, 1))
     print(f"in_plant={in_plant}: largest applied |u| {umax} against bounds (5, pi/2)")
-    cb = lr.solve_vjp_from_tape(c["nlp"], vr.dense_vjp, tape["X"], tape["U"], tape["dual"], tape["status"], c["ks"],
-                                c["plan_x"], c["plan_u"], c["w"])
-    g = lr.sweep(cb, "track", c["ks"], c["Np"], tape["S"], tape["status"], tape["active"], tape["count"], c["GS"],
-                 c["GU"], P, lr.DIST, in_plant)
+    g = lr.chain(c, vr.dense_vjp, tape, "track", in_plant)
     fd, ok = lr.oracle_fd(c, h=1e-4, in_plant=in_plant)
     assert ok
     gpx, gpu_ = g["plan_x"].sum(axis=0), g["plan_u"].sum(axis=0)   # the oracle's plan is shared

@@ -114,9 +114,8 @@ def test_chain_against_oracle_loop_finite_differences(golden_ref, in_plant):
     c = lv.loop_case(golden_ref)
     tape = lv.oracle_tape(c, in_plant)
     assert np.all(tape["status"] == 0)
-    cb = mr.solve_vjp_from_tape(c["nlp"], mr.dense_model_vjp, tape["X"], tape["U"], tape["dual"], tape["status"], c["w"])
-    gs, gp = mr.sweep_model(cb, "track", tape["S"], tape["status"], tape["active"], tape["count"], c["GS"], c["GU"],
-                            lv.P, lv.DIST, in_plant)
+    g = mr.chain(c, mr.dense_model_vjp, tape, "track", in_plant)
+    gs, gp = g["model_solver"], g["model_plant"]
     fs, fp, ok = mr.oracle_loop_fd(c, in_plant, h=1e-4)
     assert ok
     es, ep = np.max(np.abs(gs - fs), axis=0), np.max(np.abs(gp - fp), axis=0)
