@@ -22,14 +22,16 @@ RELAX = 1e-8  # IPOPT bound_relax_factor, as track_kernel applies it
 
 
 # ---- the two input sets -----------------------------------------------------------------------------------------
-def case_free():
-    """N = 8, B = 8, default box: no variable near a bound at the optimum."""
+def case_free(pattern="mpc_diag"):
+    """N = 8, B = 8, default box: no variable near a bound at the optimum.  pattern: a weight form / bound pattern of
+    tests/track_patterns.py (the inputs are the same under each)."""
+    from track_patterns import nlp_of
     from ttmpc.scenarios import synthetic_batch
     x0, xr, ur = synthetic_batch(8, 8, seed=3, psi_range=0.3)
-    return to.TrackingNLP(8, params=dict(P, horizon=8)), x0, xr, ur
+    return nlp_of(pattern, 8, P), x0, xr, ur
 
 
-def case_active():
+def case_active(pattern="mpc_diag"):
     """N = 10, B = 6, inputs boxed to -+(0.3, 0.02) (the finiteness pattern of the default box) and x_init moved away
     from the reference: 13 to 18 active input bounds per instance."""
     from ttmpc.scenarios import synthetic_batch
@@ -38,8 +40,12 @@ def case_active():
         x0[b, 0] += 2.0 * b
         x0[b, 1] += 3.0 * b
         x0[b, 5] += 1.5 * b
-    nlp = to.TrackingNLP(10, params=dict(P, horizon=10), ulb=np.array([-0.3, -0.02]), uub=np.array([0.3, 0.02]))
-    return nlp, x0, xr, ur
+    from track_patterns import nlp_of
+    return nlp_of(pattern, 10, P, ulb=np.array([-0.3, -0.02]), uub=np.array([0.3, 0.02])), x0, xr, ur
+
+
+def case(name, pattern="mpc_diag"):
+    return case_free(pattern) if name == "free" else case_active(pattern)
 
 
 # ---- pieces -----------------------------------------------------------------------------------------------------
@@ -91,6 +97,96 @@ def stationarity(nlp, z, xref, uref, dual, wq=None, wr=None):
     return g + nlp.jacobian(z).T @ y.reshape(-1) - zl + zu
 
 
+# ---- the multiplier export ----------------------------------------------------------------------------------------
+def check_multipliers(nlp, tol, x0, xr, ur, r, w=None, label=""):
+    """Signs, zeros and IPOPT's own stopping test at the exported multipliers of up to eight converged instances of a
+    ``solve_ex`` result r, in the export's layout and in CasADi's."""
+    from ttmpc import layout
+    N, B = nlp.N, x0.shape[0]
+    lb, ub = nlp.bounds()
+    lbr, ubr = relaxed_bounds(nlp)
+    fl, fu = np.isfinite(lb), np.isfinite(ub)
+    nb = int(fl.sum() + fu.sum())
+    m = 6 * (N + 1) + nb
+    ok = np.flatnonzero(r.status == 0)
+    assert ok.size > 0
+    pick = ok[:: max(1, ok.size // 8)][:8]
+    zz = layout.pack(r.X, r.U)
+    for b in pick:
+        y, zl, zu = dual_in_z_order(r.dual[b], N)
+        assert np.all(zl >= 0.0) and np.all(zu >= 0.0)
+        assert np.all(zl[~fl] == 0.0) and np.all(zu[~fu] == 0.0)
+        assert np.all(r.dual[b, N, 12:14] == 0.0) and np.all(r.dual[b, N, 20:22] == 0.0)
+        wq, wr = (None, None) if w is None else (w[b, :6], w[b, 6:])
+        res = stationarity(nlp, zz[b], xr[b], ur[b], r.dual[b], wq, wr)
+        sz = float(np.sum(zl) + np.sum(zu))
+        s_d = max(100.0, (float(np.sum(np.abs(y))) + sz) / m) / 100.0
+        s_c = max(100.0, sz / nb) / 100.0
+        dinf = float(np.max(np.abs(res)))
+        compl = max(float(np.max(zl[fl] * (zz[b][fl] - lbr[fl]))), float(np.max(zu[fu] * (ubr[fu] - zz[b][fu]))))
+        print(f"{label} N={N} instance {b}: dual inf {dinf:.3e} (bound {2 * tol * s_d:.3e}), "
+              f"compl {compl:.3e} (bound {2 * tol * s_c:.3e})")
+        assert dinf <= 2.0 * tol * s_d
+        assert compl <= 2.0 * tol * s_c
+        # CasADi's view of the same numbers
+        lam_g, lam_x = layout.casadi_multipliers(r.dual[b], N)
+        g = nlp.grad(zz[b], xr[b].T, ur[b].T, wq, wr)
+        assert np.max(np.abs(g + nlp.jacobian(zz[b]).T @ lam_g + lam_x)) <= 2.0 * tol * s_d
+
+
+def optimality_error(nlp, z, x0, xref, uref, dual, wq=None, wr=None):
+    """IPOPT's scaled optimality error E0 (s_max = 100) at a primal-dual point, as track_kernel's loop forms it from a
+    linearisation: xref (N+1,6), uref (N,2), dual in the export layout, bounds relaxed as the kernel relaxes them.
+
+        dinf = max |grad f + J' y - z_L + z_U|        pinf = max |c| (dynamics rows, x_0 - x_init among them)
+        c0   = max |z s| over the finite bounds       s_d  = max(100, (sum|y| + sum z) / m) / 100,  m = 6 (N+1) + nb
+        E0   = max(dinf / s_d, pinf, c0 / s_c)        s_c  = max(100, sum z / nb) / 100
+
+    ``scale`` is what rounding is measured against: the largest sum of the absolute values of the terms of any single
+    row of each piece (the products 2 Q_ij dx_j, y, J_ji y_j, z of a gradient row; x_{k+1}, x_k, dt f of a dynamics
+    row; z |v|, z |bound| of a complementarity product), each piece divided by the scale E0 divides it by.
+    Returns dict(E0, dinf, pinf, c0, s_d, s_c, scale)."""
+    N, dt = nlp.N, nlp.params["dt"]
+    z = np.asarray(z, dtype=np.float64)
+    X, U = nlp.unpack(z)
+    xref, uref = np.asarray(xref, dtype=np.float64), np.asarray(uref, dtype=np.float64)
+    y, zl, zu = dual_in_z_order(dual, N)
+    lb, ub = nlp.bounds()
+    lbr, ubr = relaxed_bounds(nlp)
+    fl, fu = np.isfinite(lb), np.isfinite(ub)
+    nb = int(fl.sum() + fu.sum())
+    m = 6 * (N + 1) + nb
+    # stationarity
+    res = stationarity(nlp, z, xref, uref, dual, wq, wr)
+    Qw, Rw = nlp.weights(wq, wr)
+    ax = 2.0 * np.abs(X - xref) @ np.abs(Qw) + np.abs(y)
+    au = 2.0 * np.abs(U - uref) @ np.abs(Rw)
+    for k in range(N):
+        ax[k] += np.abs(y[k + 1]) + dt * np.abs(to.jac_f(X[k], nlp.params)).T @ np.abs(y[k + 1])
+        au[k] += dt * np.abs(to.B_F).T @ np.abs(y[k + 1])
+    scale_d = float(np.max(nlp.pack(ax, au) + zl + zu))
+    # dynamics
+    c = nlp.constraints(z, x0).reshape(N + 1, 6)
+    ac = np.abs(X)
+    ac[0] += np.abs(np.asarray(x0, dtype=np.float64))
+    af = np.abs(to.f(X[:-1], U, nlp.params))
+    p, v, tphi = nlp.params, np.abs(X[:-1, 5]), np.abs(np.tan(X[:-1, 4]))
+    af[:, 3] = v * tphi / p["L1"] * (1.0 + p["M"] / p["L2"] * np.abs(np.cos(X[:-1, 3]))) \
+        + v * np.abs(np.sin(X[:-1, 3])) / p["L2"]          # the one row of f that is a sum: its terms, not their sum
+    ac[1:] += np.abs(X[:-1]) + dt * af
+    # complementarity
+    zs = np.concatenate([zl[fl] * (z[fl] - lbr[fl]), zu[fu] * (ubr[fu] - z[fu])])
+    azs = np.concatenate([zl[fl] * (np.abs(z[fl]) + np.abs(lbr[fl])), zu[fu] * (np.abs(ubr[fu]) + np.abs(z[fu]))])
+    sz = float(np.sum(zl[fl]) + np.sum(zu[fu]))
+    s_d = max(100.0, (float(np.sum(np.abs(y))) + sz) / m) / 100.0
+    s_c = max(100.0, sz / nb) / 100.0 if nb else 1.0
+    dinf, pinf = float(np.max(np.abs(res))), float(np.max(np.abs(c)))
+    c0 = float(np.max(np.abs(zs))) if nb else 0.0
+    scale = max(scale_d / s_d, float(np.max(ac)), float(np.max(azs)) / s_c if nb else 0.0)
+    return {"E0": max(dinf / s_d, pinf, c0 / s_c), "dinf": dinf, "pinf": pinf, "c0": c0, "s_d": s_d, "s_c": s_c,
+            "scale": scale}
+
+
 def _split(nlp, dz):
     N = nlp.N
     dX = np.empty((N + 1, 6, 6))
@@ -101,9 +197,10 @@ def _split(nlp, dz):
     return {"gain": dU[0].copy(), "dXdx0": dX, "dUdx0": dU}
 
 
-def dense_sensitivity(nlp, z, y, sig=None, pinned=None, wq=None, wr=None):
+def dense_sensitivity(nlp, z, y, sig=None, pinned=None, wq=None, wr=None, cond=True):
     """d z / d x_init from the dense Newton matrix.  sig: the barrier diagonal (``sigma``) or None; pinned: indices of
-    variables held fixed (active-set form).  Returns dict(gain (2,6), dXdx0 (N+1,6,6), dUdx0 (N,2,6), cond)."""
+    variables held fixed (active-set form).  Returns dict(gain (2,6), dXdx0 (N+1,6,6), dUdx0 (N,2,6), cond); cond(K) is
+    an SVD (skip it at long horizons: cond=False leaves None)."""
     n, m = nlp.n, nlp.m
     H = lagrangian_hessian(nlp, z, y, wq, wr)
     if sig is not None:
@@ -119,7 +216,7 @@ def dense_sensitivity(nlp, z, y, sig=None, pinned=None, wq=None, wr=None):
     rhs[n:n + 6] = np.eye(6)  # c_0 = x_0 - x_init: J dz = -dc/dx_init = +I in the first six rows
     sol = np.linalg.solve(K, rhs)
     out = _split(nlp, sol[:n])
-    out["cond"] = float(np.linalg.cond(K))
+    out["cond"] = float(np.linalg.cond(K)) if cond else None
     return out
 
 

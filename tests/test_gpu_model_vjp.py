@@ -3,7 +3,8 @@ tt_track_vjp_model*, tt_set_model / tt_get_model, tt_policy_plant_vjp_model_devi
 the ``model`` / ``plant_model`` tensors of ttmpc.diff.
 
 1. The kernel against dense algebra on the GPU's own duals (the numpy recursion as the yardstick) and against central
-   differences of the CPU oracle.
+   differences of the CPU oracle; against dense algebra under every weight form and bound pattern of
+   tests/track_patterns.py, its other four outputs bitwise those of the plain instantiation.
 2. Horizons, grid indexing, determinism.
 3. Neutrality: the other outputs with g_model, the NULL g_model call, the host call.
 4. accumulate, failed solves, a NaN upstream gradient.
@@ -26,6 +27,7 @@ import model_vjp_reference as mr
 import sens_reference as sr
 import vjp_harness as h
 import vjp_reference as vr
+from track_patterns import DERIVATIVE_CASES
 
 pytestmark = pytest.mark.gpu
 
@@ -84,6 +86,34 @@ def test_kernel_against_dense_algebra_and_oracle(name, weighted):
     print(f"{name} weighted={weighted}: gpu vs oracle FD (L1, L2, M) {worst} (bound {bound:.1e}), largest entries "
           f"{np.max(np.abs(v.g_model), axis=0)}")
     assert np.max(worst) <= bound
+
+
+@pytest.mark.parametrize("name,pattern,weighted", DERIVATIVE_CASES)
+def test_kernel_against_dense_algebra_patterns(name, pattern, weighted):
+    from ttmpc import layout
+    nlp, x0, xr, ur = sr.case(name, pattern)
+    B = x0.shape[0]
+    w = vr.random_weights(B) if weighted else None
+    s = _solver(nlp)
+    r = s.solve_ex(x0, xr, ur, wq_wr=w, duals=True, gain=False)
+    gX, gU = vr.random_upstream(B, nlp.N)
+    v = s.vjp(r.X, r.U, r.dual, xr, ur, r.status, gX, gU, wq_wr=w, model=True)
+    plain = s.vjp(r.X, r.U, r.dual, xr, ur, r.status, gX, gU, wq_wr=w)
+    assert np.all(r.status == 0) and np.all(v.vjp_status == 0)
+    for k in OUTS:
+        assert np.array_equal(getattr(v, k), getattr(plain, k)), k
+    zz = layout.pack(r.X, r.U)
+    err_gpu = err_model = smax = 0.0
+    for b in range(B):
+        dense = mr.dense_model_vjp(nlp, zz[b], r.dual[b], gX[b], gU[b], *_w(w, b), cond=False)
+        model = mr.riccati_model_vjp(nlp, zz[b], r.dual[b], gX[b], gU[b], *_w(w, b))
+        assert model["ok"]
+        err_gpu = max(err_gpu, float(np.max(np.abs(v.g_model[b] - dense["model"]))))
+        err_model = max(err_model, float(np.max(np.abs(model["model"] - dense["model"]))))
+        smax = max(smax, float(np.max(np.abs(dense["model"]))))
+    print(f"{name} {pattern} weighted={weighted}: err_gpu {err_gpu:.3e}, err_model {err_model:.3e}, max|ref| {smax:.3e}")
+    assert smax > 1e-3
+    assert err_gpu <= 10.0 * err_model + 1e-12 * smax
 
 
 # ---- 2 ----------------------------------------------------------------------------------------------------------

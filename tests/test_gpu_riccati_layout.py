@@ -16,29 +16,12 @@ import numpy as np
 import pytest
 
 from test_gpu_track_carry import _assert_tiles_bitwise, _bits, _gpu_solver, hard_batch
+from track_patterns import patterns as _patterns
 
 pytestmark = pytest.mark.gpu
 
 P = {"M": 0.15, "L1": 7.05, "L2": 12.45, "W1": 3.05, "W2": 2.95, "dt": 0.05}
 B = 8
-
-
-def _patterns():
-    from oracle import ttmpc_oracle as to
-    q_full = np.array(to.DEFAULT_Q, dtype=float)
-    q_full[0, 1] = q_full[1, 0] = 0.2   # symmetric, diagonally dominant: still positive definite
-    q_full[2, 3] = q_full[3, 2] = -0.1
-    r_full = np.array(to.DEFAULT_R, dtype=float)
-    r_full[0, 1] = r_full[1, 0] = 0.5
-    mpc = (to.MPC_XLB, to.MPC_XUB, to.MPC_ULB, to.MPC_UUB)
-    one_sided = np.array(to.MPC_XUB, dtype=float)
-    one_sided[2] = np.inf                # heading bounded below only: neither the MPC nor the OBCA pattern
-    return {
-        "mpc_diag": (to.DEFAULT_Q, to.DEFAULT_R) + mpc,
-        "mpc_full": (q_full, r_full) + mpc,
-        "obca": (to.DEFAULT_Q, to.DEFAULT_R, to.OBCA_XLB, to.OBCA_XUB, to.MPC_ULB, to.MPC_UUB),
-        "run_time": (to.DEFAULT_Q, to.DEFAULT_R, to.MPC_XLB, one_sided, to.MPC_ULB, to.MPC_UUB),
-    }
 
 
 def _rel(a, b):

@@ -2,9 +2,11 @@
 
 1. solve_ex returns bitwise the plain outputs of solve, for every build of track_kernel.
 2. The exported duals are the multipliers: signs, zeros, and IPOPT's own stopping test re-evaluated in numpy.
-3. The sensitivity kernel against dense algebra on the same duals, with the numpy Riccati as the yardstick.
+3. The sensitivity kernel against dense algebra on the same duals, with the numpy Riccati as the yardstick: the two
+   checked input sets under every weight form and bound pattern of tests/track_patterns.py, weighted and not; the
+   horizons at which the pre-pass wraps its lanes and the longest one; grid indexing; the device calls with weights.
 4. The gain against central finite differences of the CPU oracle.
-5. Status plumbing: failed instances, OBCA handles.
+5. Status plumbing: failed instances, undefined sensitivities (sens_status 1), OBCA handles.
 6. MPCTrackingControl.solve_with_gain.
 
 Every case prints its figures before it asserts (DESIGN.md "Multiplier export and x_init sensitivities" records them).
@@ -15,6 +17,8 @@ import numpy as np
 import pytest
 
 import sens_reference as sr
+import vjp_reference as vr
+from track_patterns import DERIVATIVE_CASES
 
 pytestmark = pytest.mark.gpu
 
@@ -40,13 +44,20 @@ def _shape_run(N, B):
     return nlp, x0, xr, ur, plain, ex
 
 
+def _case_run(name, pattern="mpc_diag", weighted=False):
+    """solve_ex with every output on one of the two checked input sets, shared by cases 3 and 4; with a pattern of
+    tests/track_patterns.py and ``random_weights`` the weights come seventh."""
+    out = _pattern_run(name, pattern, weighted)
+    return out if weighted or pattern != "mpc_diag" else out[:6]
+
+
 @functools.lru_cache(maxsize=None)
-def _case_run(name):
-    """solve_ex with every output on one of the two checked input sets, shared by cases 3 and 4."""
-    nlp, x0, xr, ur = sr.case_free() if name == "free" else sr.case_active()
+def _pattern_run(name, pattern, weighted):
+    nlp, x0, xr, ur = sr.case(name, pattern)
+    w = vr.random_weights(x0.shape[0]) if weighted else None
     s = _solver(nlp)
-    r = s.solve_ex(x0, xr, ur, duals=True, gain=True, trajectory_sens=True)
-    return nlp, x0, xr, ur, s, r
+    r = s.solve_ex(x0, xr, ur, wq_wr=w, duals=True, gain=True, trajectory_sens=True)
+    return nlp, x0, xr, ur, s, r, w
 
 
 # ---- 1 ----------------------------------------------------------------------------------------------------------
@@ -60,44 +71,10 @@ def test_plain_results_unchanged(N, B):
 
 
 # ---- 2 ----------------------------------------------------------------------------------------------------------
-def _check_multipliers(nlp, tol, x0, xr, ur, r, w=None, label=""):
-    from ttmpc import layout
-    N, B = nlp.N, x0.shape[0]
-    lb, ub = nlp.bounds()
-    lbr, ubr = sr.relaxed_bounds(nlp)
-    fl, fu = np.isfinite(lb), np.isfinite(ub)
-    nb = int(fl.sum() + fu.sum())
-    m = 6 * (N + 1) + nb
-    ok = np.flatnonzero(r.status == 0)
-    assert ok.size > 0
-    pick = ok[:: max(1, ok.size // 8)][:8]
-    zz = layout.pack(r.X, r.U)
-    for b in pick:
-        y, zl, zu = sr.dual_in_z_order(r.dual[b], N)
-        assert np.all(zl >= 0.0) and np.all(zu >= 0.0)
-        assert np.all(zl[~fl] == 0.0) and np.all(zu[~fu] == 0.0)
-        assert np.all(r.dual[b, N, 12:14] == 0.0) and np.all(r.dual[b, N, 20:22] == 0.0)
-        wq, wr = (None, None) if w is None else (w[b, :6], w[b, 6:])
-        res = sr.stationarity(nlp, zz[b], xr[b], ur[b], r.dual[b], wq, wr)
-        sz = float(np.sum(zl) + np.sum(zu))
-        s_d = max(100.0, (float(np.sum(np.abs(y))) + sz) / m) / 100.0
-        s_c = max(100.0, sz / nb) / 100.0
-        dinf = float(np.max(np.abs(res)))
-        compl = max(float(np.max(zl[fl] * (zz[b][fl] - lbr[fl]))), float(np.max(zu[fu] * (ubr[fu] - zz[b][fu]))))
-        print(f"{label} N={N} instance {b}: dual inf {dinf:.3e} (bound {2 * tol * s_d:.3e}), "
-              f"compl {compl:.3e} (bound {2 * tol * s_c:.3e})")
-        assert dinf <= 2.0 * tol * s_d
-        assert compl <= 2.0 * tol * s_c
-        # CasADi's view of the same numbers
-        lam_g, lam_x = layout.casadi_multipliers(r.dual[b], N)
-        g = nlp.grad(zz[b], xr[b].T, ur[b].T, wq, wr)
-        assert np.max(np.abs(g + nlp.jacobian(zz[b]).T @ lam_g + lam_x)) <= 2.0 * tol * s_d
-
-
 @pytest.mark.parametrize("N,B", SHAPES)
 def test_duals_are_the_multipliers(N, B):
     nlp, x0, xr, ur, _, ex = _shape_run(N, B)
-    _check_multipliers(nlp, 1e-8, x0, xr, ur, ex, label="track")
+    sr.check_multipliers(nlp, 1e-8, x0, xr, ur, ex, label="track")
 
 
 def test_duals_are_the_multipliers_fuzzy():
@@ -115,7 +92,7 @@ def test_duals_are_the_multipliers_fuzzy():
     r = s.solve_ex(x0, xr, ur, wq_wr=w)
     for a, b in zip(plain, (r.X, r.U, r.status, r.iters, r.kkt)):
         assert np.array_equal(a, b)
-    _check_multipliers(nlp, 1e-3, x0, xr, ur, r, w=w, label="fuzzy")
+    sr.check_multipliers(nlp, 1e-3, x0, xr, ur, r, w=w, label="fuzzy")
 
 
 # ---- 3 ----------------------------------------------------------------------------------------------------------
@@ -145,6 +122,131 @@ def test_kernel_against_dense_algebra(name):
     else:
         assert min(nact) >= 13
     assert err_gpu <= 10.0 * err_model + 1e-12 * smax
+
+
+def _against_dense(tag, nlp, r, w, rows, cond=True):
+    """err_gpu <= 10 err_model + 1e-12 max|ref| of the instances ``rows`` against dense algebra at the GPU's own
+    primal-dual point, with the numpy recursion as the yardstick; -> (err_gpu, err_model, max|ref|, active counts)."""
+    from ttmpc import layout
+    zz = layout.pack(r.X, r.U)
+    err_gpu = err_model = smax = 0.0
+    nact = []
+    for b in rows:
+        wq, wr = (None, None) if w is None else (w[b, :6], w[b, 6:])
+        y, _, _ = sr.dual_in_z_order(r.dual[b], nlp.N)
+        dense = sr.dense_sensitivity(nlp, zz[b], y, sig=sr.sigma(nlp, zz[b], r.dual[b]), wq=wq, wr=wr, cond=cond)
+        model = sr.riccati_sensitivity(nlp, zz[b], r.dual[b], wq, wr)
+        assert model["ok"]
+        gpu = {"gain": r.gain[b], "dXdx0": r.dXdx0[b], "dUdx0": r.dUdx0[b]}
+        assert np.array_equal(r.dUdx0[b, 0], r.gain[b]) and np.array_equal(r.dXdx0[b, 0], np.eye(6))
+        err_gpu = max(err_gpu, sr.max_err(gpu, dense))
+        err_model = max(err_model, sr.max_err(model, dense))
+        smax = max(smax, sr.max_abs(dense))
+        act = sr.active_set(nlp, zz[b])
+        nact.append(int(act[act >= 6].size))
+    print(f"{tag}: err_gpu {err_gpu:.3e}, err_model {err_model:.3e}, max|S_dense| {smax:.3e}, active {nact}")
+    assert err_gpu <= 10.0 * err_model + 1e-12 * smax
+    return err_gpu, err_model, smax, nact
+
+
+@pytest.mark.parametrize("name,pattern,weighted", DERIVATIVE_CASES)
+def test_kernel_against_dense_algebra_patterns(name, pattern, weighted):
+    nlp, x0, xr, ur, s, r, w = _pattern_run(name, pattern, weighted)
+    assert np.all(r.status == 0) and np.all(r.sens_status == 0)
+    _, _, _, nact = _against_dense(f"{name} {pattern} weighted={weighted}", nlp, r, w, range(x0.shape[0]))
+    if name == "free":
+        assert max(nact) == 0
+    else:
+        assert min(nact) >= 13
+    if weighted:   # the weights reach the kernel: the same points without them have other gains
+        from ttmpc import layout
+        zz = layout.pack(r.X, r.U)
+        plain = np.stack([sr.riccati_sensitivity(nlp, zz[b], r.dual[b])["gain"] for b in range(x0.shape[0])])
+        assert np.max(np.abs(plain - r.gain)) > 1e-4
+
+
+def _max_horizon():
+    import ttmpc
+    return int(ttmpc.lib().tt_max_horizon())
+
+
+@functools.lru_cache(maxsize=None)
+def _horizon_run(N, weighted):
+    from oracle import ttmpc_oracle as to
+    from ttmpc.scenarios import synthetic_batch
+    nlp = to.TrackingNLP(N, params=dict(P, horizon=N))
+    x0, xr, ur = synthetic_batch(4, N, seed=4000 + N, psi_range=0.3)
+    w = vr.random_weights(4) if weighted else None
+    s = _solver(nlp, tol=1e-8)
+    r = s.solve_ex(x0, xr, ur, wq_wr=w, duals=True, gain=True, trajectory_sens=True)
+    return nlp, x0, xr, ur, w, s, r
+
+
+@pytest.mark.parametrize("weighted", [False, True])
+@pytest.mark.parametrize("N", [1, 2, 20, 63, 64, 65, "max"])
+def test_horizons(N, weighted):
+    """The pre-pass gives lane k the stages k, k + 64, ...: one trip up to N = 63, a second from N = 64 on, a third at
+    the longest horizon, whose launch is also the largest dynamic LDS request (sens_lds_doubles)."""
+    N = _max_horizon() if N == "max" else N
+    nlp, x0, xr, ur, w, s, r = _horizon_run(N, weighted)
+    print(f"N={N} weighted={weighted}: status {r.status.tolist()}, sens_status {r.sens_status.tolist()}")
+    ok = np.flatnonzero(r.status <= 1)
+    assert ok.size >= 3
+    for b in np.flatnonzero(r.status > 1):
+        assert r.sens_status[b] == 2 and not r.gain[b].any() and not r.dXdx0[b].any() and not r.dUdx0[b].any()
+    assert np.all(r.sens_status[ok] == 0)
+    _, _, smax, _ = _against_dense(f"N={N} weighted={weighted}", nlp, r, w, ok, cond=False)
+    assert np.max(np.abs(r.gain[ok])) > 1e-3 and smax >= 1.0
+
+
+def _dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _sens_device(s, N, X, U, D, st, w=None, gain=True, traj=True):
+    """tt_track_sens_device on host arrays staged by torch -> (gain, dXdx0, dUdx0, sens_status), NaN / -1 prefilled."""
+    import torch
+    B = X.shape[0]
+    dev = torch.device("cuda")
+    tX, tU, tD, tst = _dev(X), _dev(U), _dev(D), _dev(np.asarray(st, dtype=np.int32))
+    tw = None if w is None else _dev(w)
+    g = torch.full((B, 2, 6), np.nan, dtype=torch.float64, device=dev)
+    dX = torch.full((B, N + 1, 6, 6), np.nan, dtype=torch.float64, device=dev)
+    dU = torch.full((B, N, 2, 6), np.nan, dtype=torch.float64, device=dev)
+    ss = torch.full((B,), -1, dtype=torch.int32, device=dev)
+    s.sens_device(B, tX.data_ptr(), tU.data_ptr(), tD.data_ptr(), tst.data_ptr(), gain=g.data_ptr() if gain else 0,
+                  dxdx0=dX.data_ptr() if traj else 0, dudx0=dU.data_ptr() if traj else 0, sens_status=ss.data_ptr(),
+                  wq_wr=0 if tw is None else tw.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    return g.cpu().numpy(), dX.cpu().numpy(), dU.cpu().numpy(), ss.cpu().numpy()
+
+
+def test_grid_indexing():
+    """One B = 2304 launch on 576 copies of the N = 20 batch: every block finds its own instance."""
+    nlp, x0, xr, ur, w, s, r = _horizon_run(20, True)
+    rep = lambda a: np.tile(a, (576,) + (1,) * (a.ndim - 1))  # noqa: E731
+    g, dX, dU, ss = _sens_device(s, 20, rep(r.X), rep(r.U), rep(r.dual), rep(r.status), w=rep(w))
+    for got, ref in ((g, r.gain), (dX, r.dXdx0), (dU, r.dUdx0), (ss, r.sens_status)):
+        assert got.shape[0] == 2304
+        assert np.array_equal(got[:4], ref)
+        assert np.array_equal(got, rep(ref))
+
+
+def test_weighted_sens_device_is_bitwise_the_fused_call():
+    """tt_track_sens_device with wq_wr on the outputs of a weighted solve, and the gain alone."""
+    nlp, x0, xr, ur, s, r, w = _pattern_run("active", "mpc_full", True)
+    assert np.all(r.sens_status == 0)
+    g, dX, dU, ss = _sens_device(s, nlp.N, r.X, r.U, r.dual, r.status, w=w)
+    assert np.array_equal(g, r.gain) and np.array_equal(dX, r.dXdx0) and np.array_equal(dU, r.dUdx0)
+    assert np.array_equal(ss, r.sens_status)
+    g1, dX1, dU1, ss1 = _sens_device(s, nlp.N, r.X, r.U, r.dual, r.status, w=w, traj=False)
+    assert np.array_equal(g1, r.gain) and np.array_equal(ss1, r.sens_status)
+    assert np.isnan(dX1).all() and np.isnan(dU1).all()            # outputs not asked for are not written
+    g0, _, _, _ = _sens_device(s, nlp.N, r.X, r.U, r.dual, r.status)   # without the weights: another gain
+    assert np.max(np.abs(g0 - r.gain)) > 1e-4
+    one = s.solve_ex(x0, xr, ur, wq_wr=w, duals=False, gain=True, trajectory_sens=False)
+    assert np.array_equal(one.gain, r.gain) and np.array_equal(one.sens_status, r.sens_status)
 
 
 def test_sens_device_is_bitwise_the_fused_call():
@@ -230,6 +332,34 @@ def test_status_plumbing():
     none = s.solve_ex(x0, xr, ur, duals=False, gain=False)
     assert np.array_equal(plain[0], none.X) and none.dual is None and none.sens_status is None
     assert s._L.tt_track_dual_len(N) == 22 * (N + 1)
+
+
+def test_undefined_sensitivity_reports_status_1():
+    """The kernel's handled path: a point at which the sweep has no positive definite G_k, or is not finite, reports
+    sens_status 1 with zeroed outputs and leaves its neighbours alone."""
+    from oracle import ttmpc_oracle as to
+    from ttmpc import layout
+    from ttmpc.scenarios import synthetic_batch
+    N = 12
+    nlp = to.TrackingNLP(N, params=dict(P, horizon=N))
+    x0, xr, ur = synthetic_batch(5, N, seed=8)
+    s = _solver(nlp)
+    good = s.solve_ex(x0, xr, ur, trajectory_sens=True)
+    assert list(good.status) == [0] * 5 and list(good.sens_status) == [0] * 5
+    dual = good.dual.copy()
+    dual[1, 4, 2] = np.nan          # a multiplier of the dynamics: the curvature it scales is not a number
+    dual[3, N - 1, 14 + 6] = -1e9   # z_U of a_{N-1}: Sigma = z_U / (ub - a) takes G_00 = 2 R_00 + Sigma + ... below 0
+    zz = layout.pack(good.X, good.U)
+    assert not sr.riccati_sensitivity(nlp, zz[3], dual[3])["ok"] and sr.riccati_sensitivity(nlp, zz[2], dual[2])["ok"]
+    for traj in (True, False):
+        g, dX, dU, ss = _sens_device(s, N, good.X, good.U, dual, good.status, traj=traj)
+        assert list(ss) == [0, 1, 0, 1, 0]
+        for b in (1, 3):
+            assert not g[b].any()
+            assert not traj or (not dX[b].any() and not dU[b].any())
+        for b in (0, 2, 4):
+            assert np.array_equal(g[b], good.gain[b])
+            assert not traj or (np.array_equal(dX[b], good.dXdx0[b]) and np.array_equal(dU[b], good.dUdx0[b]))
 
 
 def test_obca_handle_is_rejected():

@@ -1,6 +1,8 @@
 """GPU suite: the adjoint of the tracking solve (tt_track_vjp*, track_vjp_kernel) and the autograd layer on it.
 
-1. The kernel against dense algebra on the GPU's own duals, with the numpy recursion as the yardstick.
+1. The kernel against dense algebra on the GPU's own duals, with the numpy recursion as the yardstick: the default
+   problem, then every weight form and bound pattern of tests/track_patterns.py, group by group; an asymmetric Q, R
+   against its symmetric part, bit for bit.
 2. The horizons at which the kernel takes another path, and grid indexing.
 3. dL/dx_init against the forward sensitivities of track_sens_kernel.
 4. All four gradients against central finite differences of the CPU oracle.
@@ -17,6 +19,7 @@ import pytest
 import sens_reference as sr
 import vjp_harness as h
 import vjp_reference as vr
+from track_patterns import DERIVATIVE_CASES
 
 pytestmark = pytest.mark.gpu
 
@@ -29,9 +32,9 @@ def _gpu(v, b):
 
 
 @functools.lru_cache(maxsize=None)
-def _case_run(name, weighted):
+def _case_run(name, weighted, pattern="mpc_diag"):
     """solve_ex with every output and one adjoint call on one of the two checked input sets, shared by cases 1, 3, 4."""
-    nlp, x0, xr, ur = sr.case_free() if name == "free" else sr.case_active()
+    nlp, x0, xr, ur = sr.case(name, pattern)
     B = x0.shape[0]
     w = vr.random_weights(B) if weighted else None
     s = _solver(nlp)
@@ -78,6 +81,62 @@ def test_kernel_against_dense_algebra(name, weighted):
     else:
         assert min(nact) >= 13
     assert err_gpu <= 10.0 * err_model + 1e-12 * smax
+
+
+@pytest.mark.parametrize("name,pattern,weighted", DERIVATIVE_CASES)
+def test_kernel_against_dense_algebra_patterns(name, pattern, weighted):
+    """Group by group, so that the weight gradient's cross terms (non-diagonal Q, R) cannot hide behind a larger group."""
+    from ttmpc import layout
+    nlp, x0, xr, ur, w, s, r, gX, gU, v = _case_run(name, weighted, pattern)
+    assert np.all(r.status == 0) and np.all(v.vjp_status == 0)
+    zz = layout.pack(r.X, r.U)
+    e_gpu, e_model, big = ({k: 0.0 for k in vr.KEYS} for _ in range(3))
+    nact = []
+    for b in range(x0.shape[0]):
+        dense = vr.dense_vjp(nlp, zz[b], r.dual[b], xr[b], ur[b], gX[b], gU[b], *_w(w, b), cond=False)
+        model = vr.riccati_vjp(nlp, zz[b], r.dual[b], xr[b], ur[b], gX[b], gU[b], *_w(w, b))
+        assert model["ok"]
+        g = _gpu(v, b)
+        for k in vr.KEYS:
+            e_gpu[k] = max(e_gpu[k], float(np.max(np.abs(g[k] - dense[k]))))
+            e_model[k] = max(e_model[k], float(np.max(np.abs(model[k] - dense[k]))))
+            big[k] = max(big[k], float(np.max(np.abs(dense[k]))))
+        act = sr.active_set(nlp, zz[b])
+        nact.append(int(act[act >= 6].size))
+        assert not v.g_xref[b, 0].any()  # x_0 is pinned
+    for k in vr.KEYS:
+        print(f"{name} {pattern} weighted={weighted} {k:5s}: err_gpu {e_gpu[k]:.3e}, err_model {e_model[k]:.3e}, "
+              f"max|ref| {big[k]:.3e}")
+    print(f"{name} {pattern} weighted={weighted}: active {nact}")
+    assert (max(nact) == 0) if name == "free" else (min(nact) >= 13)
+    for k in vr.KEYS:
+        assert big[k] > 1e-3, k
+        assert e_gpu[k] <= 10.0 * e_model[k] + 1e-12 * big[k], k
+
+
+@pytest.mark.parametrize("name", ["free", "active"])
+def test_asymmetric_weights_are_their_symmetric_part(name):
+    """``mpc_asym`` has dyadic off-diagonals whose mean is ``mpc_full`` exactly: every kernel symmetrises on its own, so
+    a handle built with either returns the same bits from the solve, the export, the sensitivities and the adjoints."""
+    runs = []
+    for pattern in ("mpc_full", "mpc_asym"):
+        nlp, x0, xr, ur = sr.case(name, pattern)
+        B = x0.shape[0]
+        w = vr.random_weights(B)
+        s = _solver(nlp)
+        r = s.solve_ex(x0, xr, ur, wq_wr=w, duals=True, gain=True, trajectory_sens=True)
+        gX, gU = vr.random_upstream(B, nlp.N)
+        v = s.vjp(r.X, r.U, r.dual, xr, ur, r.status, gX, gU, wq_wr=w, model=True)
+        assert np.all(r.status == 0) and np.all(r.sens_status == 0) and np.all(v.vjp_status == 0)
+        runs.append((nlp, r, v))
+    (nf, rf, vf), (na, ra, va) = runs
+    assert not np.array_equal(nf.Q, na.Q) and np.array_equal(nf.Q, 0.5 * (na.Q + na.Q.T))
+    assert not np.array_equal(nf.R, na.R) and np.array_equal(nf.R, 0.5 * (na.R + na.R.T))
+    for k in ("X", "U", "status", "iters", "kkt", "dual", "gain", "dXdx0", "dUdx0", "sens_status"):
+        assert np.array_equal(getattr(rf, k), getattr(ra, k)), k
+    for k in ("g_x0", "g_xref", "g_uref", "g_wq_wr", "g_model", "vjp_status"):
+        assert np.array_equal(getattr(vf, k), getattr(va, k)), k
+    assert np.max(np.abs(vf.g_wq_wr)) > 1e-3 and np.max(np.abs(vf.g_model)) > 1e-3
 
 
 # ---- 2 ----------------------------------------------------------------------------------------------------------
@@ -172,6 +231,24 @@ def test_against_oracle_finite_differences(weighted):
             worst[k] = max(worst[k], float(np.max(np.abs(g[k] - fd[b][k]))))
             big[k] = max(big[k], float(np.max(np.abs(g[k]))))
     print(f"weighted={weighted}: gpu vs oracle FD {worst}, largest entries {big}")
+    assert max(worst.values()) <= 1e-5
+    assert min(big.values()) > 1e-3
+
+
+def test_against_oracle_finite_differences_full_weights():
+    """The non-diagonal ``mpc_full`` weights, weighted, at the bound of the cases above (the CPU references reach
+    2.4e-9 there, tests/test_vjp_reference.py)."""
+    nlp, x0, xr, ur, w, s, r, gX, gU, v = _case_run("free", True, "mpc_full")
+    z, st, fd = vr.oracle_fd_vjp(nlp, x0, xr, ur, gX, gU, w=w, h=1e-4)
+    assert np.all(st == 0) and np.all(r.status == 0) and np.all(v.vjp_status == 0)
+    worst = {k: 0.0 for k in vr.KEYS}
+    big = {k: 0.0 for k in vr.KEYS}
+    for b in range(x0.shape[0]):
+        g = _gpu(v, b)
+        for k in vr.KEYS:
+            worst[k] = max(worst[k], float(np.max(np.abs(g[k] - fd[b][k]))))
+            big[k] = max(big[k], float(np.max(np.abs(g[k]))))
+    print(f"mpc_full weighted: gpu vs oracle FD {worst}, largest entries {big}")
     assert max(worst.values()) <= 1e-5
     assert min(big.values()) > 1e-3
 

@@ -83,6 +83,33 @@ def test_riccati_model_vjp_is_the_dense_solve(case, weighted):
         assert err_0 <= tol_y
 
 
+def test_full_weights_dense_and_riccati_against_the_oracle():
+    """Cases 1 and 2 under the non-diagonal ``mpc_full`` weights of tests/track_patterns.py, weighted, free inputs."""
+    from oracle import c_oracle as co
+    nlp, x0, xr, ur = sr.case_free("mpc_full")
+    B, N = x0.shape[0], nlp.N
+    w = vr.random_weights(B)
+    gX, gU = vr.random_upstream(B, N)
+    z, st, fd = mr.oracle_fd_model(nlp, x0, xr, ur, gX, gU, w=w, h=1e-4)
+    assert np.all(st == 0)
+    ref = np.zeros((B, 3))
+    for b in range(B):
+        wq, wr = w[b, :6], w[b, 6:]
+        dual = _dual(nlp, z[b], x0[b], xr[b], ur[b], wq, wr)
+        dense = mr.dense_model_vjp(nlp, z[b], dual, gX[b], gU[b], wq, wr)
+        model = mr.riccati_model_vjp(nlp, z[b], dual, gX[b], gU[b], wq, wr)
+        assert model["ok"]
+        ref[b] = dense["model"]
+        err = float(np.max(np.abs(model["model"] - dense["model"])))
+        tol = 10.0 * np.finfo(float).eps * dense["cond"] * float(np.max(np.abs(dense["model"])))
+        print(f"mpc_full weighted instance {b}: Riccati vs dense {err:.3e} (bound {tol:.3e})")
+        assert err <= tol
+    worst, big = np.max(np.abs(fd - ref), axis=0), np.max(np.abs(ref), axis=0)
+    print(f"mpc_full weighted: FD vs dense (L1, L2, M) {worst}, largest entries {big}")
+    assert np.max(worst) <= 1e-7
+    assert np.min(big) > 1e-3
+
+
 # ---- 3 ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("disturbed", [False, True])
 def test_plant_term_against_central_differences(golden_ref, disturbed):

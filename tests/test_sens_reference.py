@@ -7,6 +7,10 @@
   synthetic interior primal-dual point they agree to the accuracy a backward-stable dense solve has,
   10 eps cond(KKT) max|S|.
 * ``layout.casadi_multipliers`` orders and signs the export as CasADi's lam_g / lam_x.
+* The same two pins under non-diagonal weights (``mpc_full`` of tests/track_patterns.py) scaled by ``random_weights``,
+  where the GPU suites lean on the references' off-diagonal terms.
+* ``optimality_error`` (the E0 of track_kernel's loop, restated) on interior points of the oracle's optima: its
+  complementarity is the mu the point was built with, its dual infeasibility is ``kkt_residual``'s stationarity.
 """
 import numpy as np
 import pytest
@@ -80,6 +84,64 @@ def test_riccati_model_is_the_dense_barrier_form(case):
         err, tol = sr.max_err(model, dense), 10.0 * np.finfo(float).eps * dense["cond"] * sr.max_abs(dense)
         print(f"{case} instance {b}: Riccati vs dense {err:.3e} (bound {tol:.3e}, cond {dense['cond']:.2e})")
         assert err <= tol
+
+
+def test_full_weights_dense_and_riccati_against_the_oracle():
+    """``mpc_full`` weighted, free inputs: dense vs oracle FD <= 1e-5, Riccati vs dense <= 10 eps cond max|S|."""
+    import vjp_reference as vr
+    from test_vjp_reference import _interior_dual
+    nlp, x0, xr, ur = sr.case_free("mpc_full")
+    assert nlp.Q[0, 1] == 0.25 and nlp.R[0, 1] == 0.5
+    w = vr.random_weights(x0.shape[0])
+    z, st, dz = sr.oracle_fd(nlp, x0, xr, ur, h=1e-4, wq=w[:, :6], wr=w[:, 6:])
+    assert np.all(st == 0)
+    for b in range(x0.shape[0]):
+        wq, wr = w[b, :6], w[b, 6:]
+        y = nlp.kkt_residual(z[b], x0[b], xr[b].T, ur[b].T, wq, wr)["y"].reshape(nlp.N + 1, 6)
+        assert sr.active_set(nlp, z[b]).size == 0
+        ref = sr.dense_sensitivity(nlp, z[b], y, wq=wq, wr=wr)
+        err = sr.max_err(sr._split(nlp, dz[b]), ref)
+        dual = _interior_dual(nlp, z[b], y)
+        dense = sr.dense_sensitivity(nlp, z[b], y, sig=sr.sigma(nlp, z[b], dual), wq=wq, wr=wr)
+        model = sr.riccati_sensitivity(nlp, z[b], dual, wq, wr)
+        assert model["ok"]
+        e2, tol = sr.max_err(model, dense), 10.0 * np.finfo(float).eps * dense["cond"] * sr.max_abs(dense)
+        plain = sr.riccati_sensitivity(nlp, z[b], dual)
+        print(f"mpc_full weighted instance {b}: FD vs dense {err:.3e}, Riccati vs dense {e2:.3e} (bound {tol:.3e}), "
+              f"weights move the gain by {np.max(np.abs(plain['gain'] - model['gain'])):.3e}")
+        assert err <= 1e-5
+        assert e2 <= tol
+        assert np.max(np.abs(plain["gain"] - model["gain"])) > 1e-4   # a reference that ignored the weights would differ
+
+
+@pytest.mark.parametrize("pattern,weighted", [("mpc_diag", False), ("mpc_full", True), ("obca", False)])
+def test_optimality_error_on_interior_points(pattern, weighted):
+    import vjp_reference as vr
+    from oracle import c_oracle as co
+    from test_vjp_reference import _interior_dual
+    nlp, x0, xr, ur = sr.case_free(pattern)
+    w = vr.random_weights(x0.shape[0]) if weighted else None
+    z, st, _, _ = co.solve_batch(sr.oracle_problem(nlp), x0, xr, ur, wq=None if w is None else w[:, :6],
+                                 wr=None if w is None else w[:, 6:])
+    assert np.all(st == 0)
+    eps, mu = np.finfo(float).eps, 1e-9
+    for b in range(x0.shape[0]):
+        wq, wr = (None, None) if w is None else (w[b, :6], w[b, 6:])
+        k = nlp.kkt_residual(z[b], x0[b], xr[b].T, ur[b].T, wq, wr)
+        dual = _interior_dual(nlp, z[b], k["y"].reshape(nlp.N + 1, 6), mu=mu)
+        e = sr.optimality_error(nlp, z[b], x0[b], xr[b], ur[b], dual, wq, wr)
+        _, zl, zu = sr.dual_in_z_order(dual, nlp.N)
+        print(f"{pattern} weighted={weighted} instance {b}: E0 {e['E0']:.3e} dinf {e['dinf']:.3e} (stat {k['stat']:.3e}) "
+              f"pinf {e['pinf']:.3e} (prim {k['prim']:.3e}) c0 {e['c0']:.3e} s_d {e['s_d']} s_c {e['s_c']} "
+              f"scale {e['scale']:.3e}")
+        assert abs(e["c0"] - mu) <= 4.0 * eps * mu                    # z s = (mu / s) s: one division, one product
+        assert e["pinf"] == k["prim"]
+        # no bound is active on this input set, so kkt_residual's residual is grad f + J' y: ours adds -z_L + z_U
+        assert sr.active_set(nlp, z[b]).size == 0
+        assert abs(e["dinf"] - k["stat"]) <= float(np.max(zl + zu)) + 64.0 * eps * e["scale"]
+        assert e["s_d"] == 1.0 and e["s_c"] == 1.0
+        assert e["E0"] == max(e["dinf"], e["pinf"], e["c0"])
+        assert 1.0 < e["scale"] < 1e3
 
 
 def test_casadi_multipliers_order_and_sign():

@@ -4,6 +4,8 @@
   the weights to <= 1e-6 absolute, for L = g . z with a fixed random g, on the free input set with and without weights.
 * ``riccati_vjp`` (the CPU model of track_vjp_kernel) and ``dense_vjp`` are the same linear algebra: on an interior
   primal-dual point of both input sets they agree to 10 eps cond(K) max|ref|.
+* Both once more under the non-diagonal ``mpc_full`` weights of tests/track_patterns.py, weighted, at the same bounds:
+  the symmetrised off-diagonal terms and the cross terms of the weight gradient.
 * dL/dxref[0] is exactly 0 (x_0 is pinned), and a loss on x_0 alone gives dL/dx_init = gX_0 exactly.
 """
 import numpy as np
@@ -78,3 +80,28 @@ def test_riccati_vjp_is_the_dense_solve(case, weighted):
         only = vr.riccati_vjp(nlp, z[b], dual, xr[b], ur[b], g0, np.zeros_like(gU[b]), wq, wr)
         assert np.array_equal(only["x0"], gX[b, 0])
         assert not only["xref"].any() and not only["uref"].any() and not only["w"].any()
+
+
+def test_full_weights_dense_and_riccati_against_the_oracle():
+    nlp, x0, xr, ur = sr.case_free("mpc_full")
+    B, N = x0.shape[0], nlp.N
+    w = vr.random_weights(B)
+    gX, gU = vr.random_upstream(B, N)
+    z, st, fd = vr.oracle_fd_vjp(nlp, x0, xr, ur, gX, gU, w=w, h=1e-4)
+    assert np.all(st == 0)
+    diag = sr.case_free()[0]
+    for b in range(B):
+        wq, wr = w[b, :6], w[b, 6:]
+        y = nlp.kkt_residual(z[b], x0[b], xr[b].T, ur[b].T, wq, wr)["y"].reshape(N + 1, 6)
+        dual = _interior_dual(nlp, z[b], y)
+        dense = vr.dense_vjp(nlp, z[b], dual, xr[b], ur[b], gX[b], gU[b], wq, wr)
+        model = vr.riccati_vjp(nlp, z[b], dual, xr[b], ur[b], gX[b], gU[b], wq, wr)
+        assert model["ok"]
+        errs = {k: float(np.max(np.abs(fd[b][k] - dense[k]))) for k in vr.KEYS}
+        err, tol = vr.max_err(model, dense), 10.0 * np.finfo(float).eps * dense["cond"] * vr.max_abs(dense)
+        off = vr.max_err(vr.riccati_vjp(diag, z[b], dual, xr[b], ur[b], gX[b], gU[b], wq, wr), model)
+        print(f"mpc_full weighted instance {b}: FD vs dense " + ", ".join(f"{k} {v:.3e}" for k, v in errs.items())
+              + f"; Riccati vs dense {err:.3e} (bound {tol:.3e}); the off-diagonals move the gradient by {off:.3e}")
+        assert max(errs.values()) <= 1e-6
+        assert err <= tol
+        assert off > 1e-4   # a reference that dropped the off-diagonal terms would differ by this much
