@@ -884,6 +884,70 @@ int tt_obca_solve_batch(void* handle, int B, const double* x0, const double* xgo
                                        kkt_res, nullptr);
 }
 
+// the MPC+OBCA adjoint keeps its whole record in LDS
+static int obca_vjp_horizon(Handle* h) {
+    if (h->cfg.N <= ttmpc::obca_vjp_max_horizon()) return 0;
+    return fail(h, -EINVAL, "the MPC+OBCA adjoint keeps its record in LDS: horizon must be <= %s",
+                std::to_string(ttmpc::obca_vjp_max_horizon()).c_str());
+}
+
+int tt_obca_vjp_device(void* handle, int B, const double* d_iterate, const int* d_status, const double* d_grad_x,
+                       const double* d_grad_u, const tt_obca_vjp_out* d_out, void* stream) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (const int rc = prelude(h, B, kHandle | kObcaOnly | kNotPlan | kSign)) return rc;
+    if (!d_grad_x && !d_grad_u) return fail(h, -EINVAL, "grad_x and grad_u are both NULL: no loss to differentiate%s");
+    if (const int rc = obca_vjp_horizon(h)) return rc;
+    if (const int rc = prelude(h, B, kEmpty | kRange)) return result(rc);
+    if (!d_iterate || !d_status || !d_out) return fail(h, -EINVAL, "NULL device buffer%s");
+    DeviceGuard dg(h->device);
+    if (dg.err != hipSuccess) return hip_fail(h, dg.err, "hipSetDevice");
+    ttmpc::ObcaVjpArgs a = diff_args<ttmpc::ObcaVjpArgs>(h, B, nullptr, nullptr, nullptr, nullptr, d_status);
+    a.M = h->cfg.M;
+    a.W1 = h->cfg.W1;
+    a.W2 = h->cfg.W2;
+    a.eq_tol = 1e-5;  // trajectory_optimization.py:136-139, as the solve sets it
+    memcpy(a.obs, h->obs, sizeof a.obs);
+    a.iterate = d_iterate;
+    a.gx = d_grad_x;
+    a.gu = d_grad_u;
+    a.g_x0 = d_out->g_x0;
+    a.g_xref = d_out->g_xref;
+    a.g_uref = d_out->g_uref;
+    a.vjp_status = d_out->vjp_status;
+    const hipError_t e = ttmpc::launch_obca_vjp(a, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(h, e, "OBCA adjoint kernel launch");
+    return 0;
+}
+
+int tt_obca_vjp(void* handle, int B, const double* iterate, const int* status, const double* grad_x,
+                const double* grad_u, const tt_obca_vjp_out* out) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (const int rc = prelude(h, B, kHandle | kObcaOnly | kNotPlan | kSign)) return rc;
+    if (!grad_x && !grad_u) return fail(h, -EINVAL, "grad_x and grad_u are both NULL: no loss to differentiate%s");
+    if (const int rc = obca_vjp_horizon(h)) return rc;   // (before anything is staged)
+    if (const int rc = prelude(h, B, kEmpty | kRange)) return result(rc);
+    if (!iterate || !status || !out) return fail(h, -EINVAL, "NULL host buffer%s");
+    DeviceGuard dg(h->device);
+    if (dg.err != hipSuccess) return hip_fail(h, dg.err, "hipSetDevice");
+    const size_t N = h->cfg.N, b = (size_t)B, nx = b * (N + 1) * 6, nu = b * N * 2;
+    Stager st;
+    const double *d_it, *d_gx, *d_gu;
+    const int* d_st;
+    tt_obca_vjp_out dout;
+    st.in(iterate, b * ttmpc::obca_iterate_len(h->cfg.N, h->cfg.M), &d_it);
+    st.in(grad_x, nx, &d_gx);
+    st.in(grad_u, nu, &d_gu);
+    st.in(status, b, &d_st);
+    st.out(out->g_x0, b * 6, &dout.g_x0);
+    st.out(out->g_xref, nx, &dout.g_xref);
+    st.out(out->g_uref, nu, &dout.g_uref);
+    st.out(out->vjp_status, b, &dout.vjp_status);
+    if (!st.carve(h->xfer)) return no_memory(h, "adjoint staging");
+    hipStream_t s = h->stream;
+    return st.run(h, s, "OBCA adjoint",
+                  [&] { return tt_obca_vjp_device(handle, B, d_it, d_st, d_gx, d_gu, &dout, s); });
+}
+
 /* diagnostics only (not part of include/ttmpc.h): per-instance phase cycle sums of the handle's next OBCA
  * launches into d_stamps[B][kObcaPhases] (device pointer; NULL switches it off).  Returns the phase count. */
 int ttx_obca_set_stamps(void* handle, unsigned long long* d_stamps) {

@@ -184,4 +184,29 @@ __host__ __device__ inline size_t obca_iterate_len(int N, int M) { return (size_
 
 hipError_t launch_obca(const ObcaArgs& a, hipStream_t stream);
 
+// adjoint of an MPC+OBCA solve: dL/d(x_init, xref, uref) (tt_obca_vjp.hip).  The DiffArgs head carries the model, the
+// weights, the bounds and the solve's status; its x, u, dual and wqwr stay nullptr: the point comes from `iterate`
+struct ObcaVjpArgs : DiffArgs {
+    int M;
+    double W1, W2, eq_tol;
+    double obs[4 * kObcaMaxM];  // cx, cy, w, h
+    const double* iterate;      // [B][obca_iterate_len(N, M)]
+    const double* gx;           // [B][N+1][6] upstream dL/dX, or nullptr (zeros)
+    const double* gu;           // [B][N][2]   upstream dL/dU, or nullptr (zeros)
+    double* g_x0;               // [B][6] or nullptr
+    double* g_xref;             // [B][N+1][6] or nullptr
+    double* g_uref;             // [B][N][2] or nullptr
+    int* vjp_status;            // [B] or nullptr
+};
+constexpr int kObcaVjpThreads = 256;  // sixteen 16-lane groups: one OBCA block each per round
+// LDS doubles of one instance: the adjoint's stage record, the dense 4x4 pose addend and the refinement's fields (87
+// per stage), 12 per input stage (K), the tiles, one slot per group and the obstacle list: 43.1 KB at N = 50 for any M
+constexpr int kObcaVjpStage = 87;
+constexpr int kObcaVjpFixed = kVjpTiles + 16 * (kObcaVjpThreads / 16) + 4 * kObcaMaxM;  // tiles, slots, obstacles
+inline int obca_vjp_lds_doubles(int N) { return kObcaVjpStage * (N + 1) + 12 * N + kObcaVjpFixed; }
+inline int obca_vjp_max_horizon() {  // (512 bytes stay free for the compiler's own LDS)
+    return ((64 * 1024 - 512) / 8 - kObcaVjpFixed - kObcaVjpStage) / (kObcaVjpStage + 12);
+}
+hipError_t launch_obca_vjp(const ObcaVjpArgs& a, hipStream_t stream);
+
 }  // namespace ttmpc

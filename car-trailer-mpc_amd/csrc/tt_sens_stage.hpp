@@ -18,8 +18,14 @@
 // gain, lanes 48..53 p and lanes 54, 55 kappa.  Four barriers per stage with or without the vector lanes: kappa's
 // division runs beside K's, and p_k is formed beside P_k as gX_k + A' p_{k+1} - (B' M)' kappa (A' P B = M' B because P
 // is symmetric).  Plain IEEE arithmetic (division, no contraction).
+//
+// A layout that has a member sDH adds a dense symmetric 4x4 block r[sDH + 4 i + j] to the pose entries (i, j < 4:
+// X, Y, theta, psi) of every stage Hessian: the eliminated OBCA blocks of tt_obca_vjp.hip.  Layouts without it compile
+// to the code they compiled to before.  With the addend the 2x2 solves with G_k eliminate on the larger diagonal.
 #pragma once
 #include <math.h>
+
+#include <type_traits>
 
 #include "tt_kernel.hpp"
 
@@ -88,6 +94,11 @@ __device__ __forceinline__ void linearise_stage(const DiffArgs& a, double* r, co
     }
 }
 
+template <class L, class = void>
+struct has_dense : std::false_type {};
+template <class L>
+struct has_dense<L, std::void_t<decltype(L::sDH)>> : std::true_type {};
+
 // entry-parallel roles of the serial sweeps: matrix entry (i, j), gain entry (gr, gc), p entry pi, kappa entry kr
 struct Roles {
     bool ent, gl, pl, kl;
@@ -125,7 +136,9 @@ __device__ __forceinline__ int backward_sweep(const DiffArgs& a, const Roles& ro
     }
     __syncthreads();
     if (ent) {
-        const double p = q2 + (i == j ? stg[N * kStage + sSG + i] : 0.0);
+        double p = q2 + (i == j ? stg[N * kStage + sSG + i] : 0.0);
+        if constexpr (has_dense<L>::value)
+            if (i < 4 && j < 4) p += stg[N * kStage + L::sDH + i * 4 + j];
         T[tP + lane] = p;
         bad |= !isfinite(p);
     }
@@ -161,8 +174,20 @@ __device__ __forceinline__ int backward_sweep(const DiffArgs& a, const Roles& ro
                 h1 = gl ? h1 : r[L::sG + 7] + dt * T[pc + 4];
                 row = gl ? gr : ro.kr;
             }
-            const double kv = row == 0 ? (g11 * h0 - g01 * h1) / det : (g00 * h1 - g01 * h0) / det;
-            if (!(g00 > 0.0) || !(det > 0.0) || !isfinite(g00) || !isfinite(det) || !isfinite(kv)) bad = true;
+            double kv;
+            if constexpr (has_dense<L>::value) {
+                // The eliminated blocks put entries of 1e13 on P, and B' P B is then close to rank one: the determinant
+                // form cancels.  Eliminate on the larger diagonal instead (G is positive definite or the solve fails).
+                const bool sw = g11 > g00;
+                const double d0 = sw ? g11 : g00, d1 = sw ? g00 : g11, b0 = sw ? h1 : h0, b1 = sw ? h0 : h1;
+                const double m = g01 / d0, sc = d1 - m * g01;
+                const double x1 = (b1 - m * b0) / sc, x0 = (b0 - g01 * x1) / d0;
+                kv = (row == 0) == sw ? x1 : x0;
+                if (!(d0 > 0.0) || !(sc > 0.0) || !isfinite(d0) || !isfinite(sc) || !isfinite(kv)) bad = true;
+            } else {
+                kv = row == 0 ? (g11 * h0 - g01 * h1) / det : (g00 * h1 - g01 * h0) / det;
+                if (!(g00 > 0.0) || !(det > 0.0) || !isfinite(g00) || !isfinite(det) || !isfinite(kv)) bad = true;
+            }
             if (gl) Ks[k * 12 + gr * 6 + gc] = kv;
             if constexpr (L::kVec)
                 if (!gl) T[L::tKP + ro.kr] = kv;
@@ -170,6 +195,8 @@ __device__ __forceinline__ int backward_sweep(const DiffArgs& a, const Roles& ro
         __syncthreads();
         if (ent && k > 0) {  // P_k = W_k + Sigma_x + A' M - H' K,  H = B' M
             double p = q2 + (wi >= 0 ? r[sWC + wi] : 0.0) + (i == j ? r[sSG + i] : 0.0);
+            if constexpr (has_dense<L>::value)
+                if (i < 4 && j < 4) p += r[L::sDH + i * 4 + j];
             double am = 0.0;
             for (int l = 0; l < 6; ++l) am += T[tA + l * 6 + i] * T[tM + l * 6 + j];
             const double hk = dt * T[tM + 5 * 6 + i] * Ks[k * 12 + j] + dt * T[tM + 4 * 6 + i] * Ks[k * 12 + 6 + j];

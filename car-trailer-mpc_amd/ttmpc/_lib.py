@@ -63,6 +63,11 @@ class TTTrackVjpModelOut(C.Structure):
                 ("g_model", C.c_void_p), ("vjp_status", C.c_void_p)]
 
 
+class TTObcaVjpOut(C.Structure):
+    """tt_obca_vjp_out (include/ttmpc.h): the outputs of tt_obca_vjp*; NULL members are skipped."""
+    _fields_ = [("g_x0", C.c_void_p), ("g_xref", C.c_void_p), ("g_uref", C.c_void_p), ("vjp_status", C.c_void_p)]
+
+
 class TTLqrVjpOut(C.Structure):
     """tt_lqr_vjp_out (include/ttmpc.h): the outputs of tt_lqr_score_vjp_device; NULL members are skipped."""
     _fields_ = [("g_x_cur", C.c_void_p), ("g_x_goal", C.c_void_p), ("g_Q", C.c_void_p), ("g_R", C.c_void_p),
@@ -183,6 +188,11 @@ def lib():
         L.tt_obca_solve_batch_iterate_device.restype = C.c_int
         L.tt_obca_iterate_len.argtypes = [C.c_int, C.c_int]
         L.tt_obca_iterate_len.restype = C.c_longlong
+    if not os.environ.get("TTMPC_LIB") or hasattr(L, "tt_obca_vjp_device"):  # (A/B against a build without them)
+        L.tt_obca_vjp_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.POINTER(TTObcaVjpOut), C.c_void_p]
+        L.tt_obca_vjp_device.restype = C.c_int
+        L.tt_obca_vjp.argtypes = [C.c_void_p, C.c_int, _dp, _ip, _dp, _dp, C.POINTER(TTObcaVjpOut)]
+        L.tt_obca_vjp.restype = C.c_int
     L.tt_obca_n.argtypes = [C.c_int, C.c_int]
     L.tt_obca_n.restype = C.c_longlong
     L.tt_obca_workspace_bytes.argtypes = [C.c_int, C.c_int]
@@ -245,7 +255,8 @@ EXPORTED_SYMBOLS = ("tt_create", "tt_solve_batch", "tt_solve_batch_device", "tt_
                     "tt_track_vjp_device", "tt_track_vjp", "tt_policy_plant_vjp_device", "tt_sim_window_vjp_device",
                     "tt_lqr_score_vjp_device", "tt_track_vjp_model_device", "tt_track_vjp_model", "tt_set_model",
                     "tt_get_model", "tt_policy_plant_vjp_model_device", "tt_fuzzy_weights_rule_device",
-                    "tt_fuzzy_weights_vjp_device", "tt_sim_window_vjp_fuzzy_device")
+                    "tt_fuzzy_weights_vjp_device", "tt_sim_window_vjp_fuzzy_device", "tt_obca_vjp_device",
+                    "tt_obca_vjp")
 
 
 def _ptr(a):
@@ -583,10 +594,53 @@ class ObcaSolver(_Solver):
         if rc != 0:
             self._err(rc, "ttx_obca_set_handoff_debug")
 
-    def solve_device(self, B, x0, x_goal, xref, uref, z_guess, x_out, u_out, z_out, status, iters=0, kkt=0, stream=0):
-        """Device pointers (ints), enqueued on ``stream``."""
+    def solve_device(self, B, x0, x_goal, xref, uref, z_guess, x_out, u_out, z_out, status, iters=0, kkt=0, stream=0,
+                     iterate=0):
+        """Device pointers (ints), enqueued on ``stream``.  iterate: (B, tt_obca_iterate_len) for the final primal-dual
+        iterate, the device twin of ``solve(iterate=True)`` (0 = not wanted); the other outputs are bitwise the same
+        with or without it."""
+        if iterate:
+            rc = self._L.tt_obca_solve_batch_iterate_device(self._h, int(B), x0, x_goal or None, xref or None,
+                                                            uref or None, z_guess or None, x_out, u_out, z_out or None,
+                                                            status, iters or None, kkt or None, iterate, stream or None)
+            if rc != 0:
+                self._err(rc, "tt_obca_solve_batch_iterate_device")
+            return
         rc = self._L.tt_obca_solve_batch_device(self._h, int(B), x0, x_goal or None, xref or None, uref or None,
                                                 z_guess or None, x_out, u_out, z_out or None, status, iters or None,
                                                 kkt or None, stream or None)
         if rc != 0:
             self._err(rc, "tt_obca_solve_batch_device")
+
+    def iterate_len(self):
+        """tt_obca_iterate_len of this handle's (N, M)."""
+        return int(self._L.tt_obca_iterate_len(self.N, self.M))
+
+    def vjp_device(self, B, iterate, status, grad_x=0, grad_u=0, g_x0=0, g_xref=0, g_uref=0, vjp_status=0, stream=0):
+        """tt_obca_vjp_device (TT_VARIANT_TRACK_OBCA): the adjoint kernel on the device iterate and status of an earlier
+        ``solve_device(..., iterate=ptr)`` and the upstream gradients grad_x = dL/dX, grad_u = dL/dU (0 = zeros, not
+        both).  Outputs (0 = not wanted): g_x0, g_xref, g_uref, vjp_status.  Uses no buffer of the handle: any stream
+        will do, behind the solve whose iterate it reads."""
+        out = TTObcaVjpOut(g_x0 or None, g_xref or None, g_uref or None, vjp_status or None)
+        rc = self._L.tt_obca_vjp_device(self._h, int(B), iterate or None, status or None, grad_x or None,
+                                        grad_u or None, C.byref(out), stream or None)
+        if rc != 0:
+            self._err(rc, "tt_obca_vjp_device")
+
+    def vjp(self, iterate, status, grad_x, grad_u):
+        """Host arrays: the gradient of a scalar loss L(X, U) with respect to x_init, xref and uref of the MPC+OBCA
+        solve that returned iterate (B, tt_obca_iterate_len) and status (B,); grad_x (B,N+1,6) = dL/dX and grad_u (B,N,2) =
+        dL/dU (either may be None for zeros).  Returns a ``TrackVjpResult`` (g_wq_wr and g_model are None)."""
+        N = self.N
+        I = _f64(iterate).reshape(-1, self.iterate_len())
+        B = I.shape[0]
+        st = np.ascontiguousarray(np.asarray(status, dtype=np.int32)).reshape(B)
+        gx = None if grad_x is None else _f64(grad_x, (B, N + 1, 6))
+        gu = None if grad_u is None else _f64(grad_u, (B, N, 2))
+        r = TrackVjpResult(g_x0=np.empty((B, 6)), g_xref=np.empty((B, N + 1, 6)), g_uref=np.empty((B, N, 2)),
+                           vjp_status=np.empty(B, dtype=np.int32))
+        out = TTObcaVjpOut(r.g_x0.ctypes.data, r.g_xref.ctypes.data, r.g_uref.ctypes.data, r.vjp_status.ctypes.data)
+        rc = self._L.tt_obca_vjp(self._h, B, _ptr(I), st.ctypes.data_as(_ip), _ptr(gx), _ptr(gu), C.byref(out))
+        if rc != 0:
+            self._err(rc, "tt_obca_vjp")
+        return r

@@ -6,6 +6,10 @@ L(X, U) it returns dL/d(x0, xref, uref, wq_wr) as sIPOPT defines the sensitivity
 at the returned primal-dual point (include/ttmpc.h, "Reverse mode").  First order: the active set is taken as fixed.
 Both run on ``torch.cuda.current_stream()`` without any host synchronisation.
 
+``DifferentiableObcaTracking(solver)`` is the same layer over an ``ObcaSolver`` of TT_VARIANT_TRACK_OBCA: forward one
+``solve_device(..., iterate=ptr)``, backward one ``ObcaSolver.vjp_device`` (obca_vjp_kernel), differentiable with
+respect to x0, xref and uref.
+
 ``DifferentiableClosedLoop(loop)`` wraps a ``ttmpc.simulation.ClosedLoop``: forward is ``run_tape`` (K closed-loop steps
 with every solve taped on the device), backward is ``ClosedLoop.backward`` (the plant, policy and window adjoints around
 one ``vjp_device`` per step).  For a scalar loss on the visited states S and the applied controls Ua it returns
@@ -33,7 +37,8 @@ import torch
 
 from . import simulation as sim
 
-__all__ = ["TrackingSolveFunction", "TrackingSolveModelFunction", "DifferentiableTracking", "ClosedLoopFunction",
+__all__ = ["TrackingSolveFunction", "TrackingSolveModelFunction", "DifferentiableTracking", "ObcaTrackingSolveFunction",
+           "DifferentiableObcaTracking", "ClosedLoopFunction",
            "ClosedLoopModelFunction", "ClosedLoopRuleFunction", "DifferentiableClosedLoop", "FuzzyWeightsFunction",
            "fuzzy_weights", "LqrScoreFunction", "DifferentiableLqrScore"]
 
@@ -155,6 +160,65 @@ class DifferentiableTracking:
         return TrackingSolveFunction.apply(self.solver, x0, xref, uref, wq_wr, z_guess, model)
 
 
+class ObcaTrackingSolveFunction(torch.autograd.Function):
+    """``X, U, status = ObcaTrackingSolveFunction.apply(solver, x0, xref, uref)`` for an ``ObcaSolver`` of
+    TT_VARIANT_TRACK_OBCA: x0 (B,6), xref (B,N+1,6), uref (B,N,2) float64 CUDA tensors on the solver's device.  X and U
+    are differentiable with respect to all three (tt_obca_vjp_device: first order, the active set fixed); an instance
+    whose solve status is above TT_ACCEPTABLE, or whose adjoint is undefined, contributes a zero gradient."""
+
+    @staticmethod
+    def forward(ctx, solver, x0, xref, uref):
+        N, B = solver.N, x0.shape[0]
+        x0 = _check("x0", x0, (B, 6))
+        xref = _check("xref", xref, (B, N + 1, 6))
+        uref = _check("uref", uref, (B, N, 2))
+        dev = x0.device
+        X = torch.empty((B, N + 1, 6), dtype=torch.float64, device=dev)
+        U = torch.empty((B, N, 2), dtype=torch.float64, device=dev)
+        iterate = torch.empty((B, solver.iterate_len()), dtype=torch.float64, device=dev)
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        solver.solve_device(B, x0.data_ptr(), 0, xref.data_ptr(), uref.data_ptr(), 0, X.data_ptr(), U.data_ptr(), 0,
+                            status.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream,
+                            iterate=iterate.data_ptr())
+        ctx.solver = solver
+        ctx.save_for_backward(iterate, status)
+        ctx.mark_non_differentiable(status)
+        return X, U, status
+
+    @staticmethod
+    def backward(ctx, grad_X, grad_U, _grad_status):
+        need = ctx.needs_input_grad  # (solver, x0, xref, uref)
+        if grad_X is None and grad_U is None:
+            return None, None, None, None
+        iterate, status = ctx.saved_tensors
+        B, N, dev = status.shape[0], ctx.solver.N, status.device
+        gX = None if grad_X is None else grad_X.to(torch.float64).contiguous()
+        gU = None if grad_U is None else grad_U.to(torch.float64).contiguous()
+        new = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)  # noqa: E731
+        g_x0 = new(B, 6) if need[1] else None
+        g_xref = new(B, N + 1, 6) if need[2] else None
+        g_uref = new(B, N, 2) if need[3] else None
+        ctx.solver.vjp_device(B, iterate.data_ptr(), status.data_ptr(), grad_x=_ptr(gX), grad_u=_ptr(gU),
+                              g_x0=_ptr(g_x0), g_xref=_ptr(g_xref), g_uref=_ptr(g_uref),
+                              stream=torch.cuda.current_stream(dev).cuda_stream)
+        return None, g_x0, g_xref, g_uref
+
+
+class DifferentiableObcaTracking:
+    """``X, U, status = layer(x0, xref, uref)`` with float64 CUDA tensors: a thin callable over
+    ``ObcaTrackingSolveFunction`` for one ``ObcaSolver`` of TT_VARIANT_TRACK_OBCA.  The forward uses the handle's solver
+    workspace (one stream per handle); the backward uses no buffer of the handle.  Failed instances give zeros."""
+
+    def __init__(self, solver):
+        from ._lib import TT_VARIANT_TRACK_OBCA
+        if getattr(solver, "variant", None) != TT_VARIANT_TRACK_OBCA or not hasattr(solver, "iterate_len"):
+            raise TypeError("DifferentiableObcaTracking needs an ObcaSolver of TT_VARIANT_TRACK_OBCA")
+        self.solver = solver
+
+    def __call__(self, x0, xref, uref):
+        return ObcaTrackingSolveFunction.apply(self.solver, x0, xref, uref)
+
+
 class ClosedLoopFunction(torch.autograd.Function):
     """``S, Ua, status = ClosedLoopFunction.apply(loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise[, model,
     plant_model[, fuzzy_rule]])``.
@@ -269,7 +333,9 @@ class DifferentiableClosedLoop:
     A thin callable over ``ClosedLoopFunction`` for one ``ClosedLoop`` whose solver is TT_VARIANT_TRACK or
     TT_VARIANT_NMPC (any of the three failure policies, warm start on or off, measurement or in-plant noise, shared or
     per-instance plan), or any tracking variant with a ``FuzzyRule`` (ClosedLoop(..., fuzzy_rule=...)).  A
-    TT_VARIANT_FUZZY solver on the built-in rule and a switch solver raise ValueError.  A plan given here replaces
+    TT_VARIANT_FUZZY solver on the built-in rule raises ValueError, and so does a switch solver unless the loop was
+    built with ``switch_adjoint=True`` (then x_init, the plan and the noise get gradients through the MPC+OBCA solves too;
+    model, plant_model and fuzzy_rule are not available on such a loop).  A plan given here replaces
     the loop's.  The forward synchronises once at its end, as ``run`` does; the backward does not.  Zero gradient comes
     from: failed solves (whatever the policy then applies), stopped instances, variables sitting on a bound, and the
     warm start (z_guess does not move a converged solution).  With ``model`` and / or ``plant_model`` (float64 (3,)

@@ -32,7 +32,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import TT_ACCEPTABLE, TT_VARIANT_FUZZY, TTError, TTFuzzyRule, TTPlant, lib
+from ._lib import TT_ACCEPTABLE, TT_MAX_ITER, TT_VARIANT_FUZZY, TTError, TTFuzzyRule, TTPlant, lib
 
 # closed-loop failure policies (include/ttmpc.h TT_POLICY_*): what a driver does after a failed solve
 POLICIES = {"track": 0, "nmpc": 1, "fuzzy": 2}
@@ -301,9 +301,11 @@ class LoopTape:
     wq_wr (B,8) or None are the run's weights, plan_x / plan_u the plan it saw, model_solver / model_plant the
     (L1, L2, M) of the solver's handle and of the plant during a taped run.  The taped run of a loop with a
     ``FuzzyRule`` also keeps rule (that rule), W (K,B,8), the weights each step's accepted solve used (ones where the
-    unit-weight retry was taken), and retried (K,B) int32, where it was: 68 bytes per instance and step."""
+    unit-weight retry was taken), and retried (K,B) int32, where it was: 68 bytes per instance and step.  The taped run
+    of a switch loop (``switch_adjoint=True``) keeps switched: per step None, or (idx (n,) int64, the flagged instances;
+    iterate (n, tt_obca_iterate_len), the MPC+OBCA solve's exported iterates of those instances; status (n,) int32)."""
     __slots__ = ("ks", "S", "Ua", "status", "iters", "collide", "active", "consec", "X", "U", "dual", "noise", "wq_wr",
-                 "plan_x", "plan_u", "model_solver", "model_plant", "W", "retried", "rule")
+                 "plan_x", "plan_u", "model_solver", "model_plant", "W", "retried", "rule", "switched")
     # (log field, the loop's buffer a step leaves it in), in the order record() copies them; the solve writes dual
     STEP = (("S", "state"), ("Ua", "u_applied"), ("status", "st"), ("iters", "it"), ("collide", "flag"),
             ("active", "active"), ("consec", "consec"), ("X", "X"), ("U", "U"), ("W", "wq"), ("retried", "retried"))
@@ -384,11 +386,16 @@ class ClosedLoop:
     simulation_fuzzy.py): the solver sees the exact state and, with disturbances on, the process noise
     N(0, process_noise_std) enters the plant as q_ += noise * dt (tt_policy_plant_noise_device); the default is
     simulation.py's (noise on the measured state, simulation.py:509-513).  Default: True for the "nmpc" and
-    "fuzzy" policies."""
+    "fuzzy" policies.
+
+    switch_adjoint=True makes a loop with a switch_solver differentiable (``run_tape`` / ``backward``): the switch step
+    then exports the MPC+OBCA solve's iterate, and the backward runs tt_obca_vjp_device on the switched instances.  The
+    default keeps such a loop refusing ``run_tape``."""
 
     def __init__(self, solver, plan_x, plan_u, params, disturbance_params=None, measurement_noise=None,
                  obstacles=None, check_collision=True, switch_solver=None, warm_start=False, bug_compatible=True,
-                 zero_on_fail=False, device=None, seed=0, policy=None, noise_in_plant=None, fuzzy_rule=None):
+                 zero_on_fail=False, device=None, seed=0, policy=None, noise_in_plant=None, fuzzy_rule=None,
+                 switch_adjoint=False):
         self.solver = solver
         self.N = solver.N
         self.dev = torch.device("cuda", solver.device if device is None else device)
@@ -404,6 +411,8 @@ class ClosedLoop:
                                                              self.dev)
         self.check_collision = check_collision and self.obstacles is not None
         self.switch = switch_solver
+        self.switch_adjoint = bool(switch_adjoint)   # run_tape / backward through the switch solve (tt_obca_vjp_device)
+        self._switched = None                         # a taped run's per-step record of the switch solves
         self.warm, self.bug_compatible, self.zero_on_fail = warm_start, bug_compatible, zero_on_fail
         self._fuzzy_variant = getattr(solver, "variant", None) == TT_VARIANT_FUZZY
         self.set_fuzzy_rule(fuzzy_rule)
@@ -595,10 +604,24 @@ class ClosedLoop:
                 self.wq[idx] = 1.0
 
     def _switch_solve(self, s):
-        """USE_SWITCH_MPC: instances whose check collided use MPCTrackingControlObs (simulation.py:506-512)."""
-        self._resolve(torch.nonzero(self.flag, as_tuple=True)[0],
-                      lambda n, x0, xr, ur, X, U, st, it, kk: self.switch.solve_device(
-                          n, x0, 0, xr, ur, 0, X, U, 0, st, it, kk, stream=s.cuda_stream))
+        """USE_SWITCH_MPC: instances whose check collided use MPCTrackingControlObs (simulation.py:506-512).  In a taped
+        run the solve also exports its iterates (the other outputs are bitwise the same), and the step's record
+        (flagged indices, compacted iterates and statuses) joins the tape."""
+        idx = torch.nonzero(self.flag, as_tuple=True)[0]
+        rec = self._switched
+        if rec is None:
+            self._resolve(idx, lambda n, x0, xr, ur, X, U, st, it, kk: self.switch.solve_device(
+                n, x0, 0, xr, ur, 0, X, U, 0, st, it, kk, stream=s.cuda_stream))
+            return
+        kept = []
+
+        def solve(n, x0, xr, ur, X, U, st, it, kk, dual=0):   # (dual: the tracking solve's export, not the switch's)
+            I = torch.empty((n, self.switch.iterate_len()), dtype=torch.float64, device=self.dev)
+            self.switch.solve_device(n, x0, 0, xr, ur, 0, X, U, 0, st, it, kk, stream=s.cuda_stream,
+                                     iterate=I.data_ptr())
+            kept.append(I)
+        self._resolve(idx, solve)
+        rec.append((idx, kept[0], self.st[idx].contiguous()) if kept else None)
 
     def _resolve(self, idx, solve, dual=None):
         """Solve the instances idx again as a compacted batch and put the results in their places: gathers x_meas,
@@ -739,8 +762,12 @@ class ClosedLoop:
             raise ValueError("the closed loop of a TT_VARIANT_FUZZY solver on the built-in weight rule is not "
                              "differentiable: give the rule as data, ClosedLoop(..., fuzzy_rule=FuzzyRule()), whose "
                              "adjoint and taped retry exist")
-        if self.switch is not None:
-            raise ValueError("the closed loop with a switch solver is not differentiable: the OBCA solve has no adjoint")
+        if self.switch is not None and not self.switch_adjoint:
+            raise ValueError("the closed loop with a switch solver is differentiable only on request: the OBCA solve's "
+                             "adjoint joins the backward with ClosedLoop(..., switch_solver=..., switch_adjoint=True)")
+        if self.switch is not None and self.rule is not None:
+            raise ValueError("a switch (OBCA) loop with a fuzzy_rule is not differentiable: the rule's adjoint "
+                             "(rule=True) is not carried through the switch solve")
 
     def run_tape(self, x_init, T_sim, noise=None, wq_wr=None):
         """``run`` that also keeps what ``backward`` needs: the same steps with the solve's multipliers exported
@@ -748,12 +775,19 @@ class ClosedLoop:
         (30 (N+1) - 2) * 8 bytes per instance and step.  wq_wr: constant per-instance weights (B,8), host or device.
         Returns run()'s dict plus "tape".  Solver variants TT_VARIANT_TRACK and TT_VARIANT_NMPC, or any tracking
         variant with a ``FuzzyRule`` (then the weights come from the rule and wq_wr must be None; the unit-weight retry
-        exports its multipliers into the step's dual, and the tape keeps W and retried); no switch solver."""
+        exports its multipliers into the step's dual, and the tape keeps W and retried).  A switch solver needs
+        ``switch_adjoint=True``: its step then calls the iterate-exporting MPC+OBCA solve and the tape keeps, per step,
+        the flagged indices and the compacted iterates and statuses (``LoopTape.switched``)."""
         self._check_differentiable()
         if self.rule is not None and wq_wr is not None:
             raise ValueError("a loop with a fuzzy_rule takes its weights from the rule: wq_wr must be None")
         tape, drawn = self._begin(x_init, T_sim, noise, wq_wr, taped=True)
-        self._steps(tape, drawn)
+        if self.switch is not None and self.check_collision:
+            self._switched = tape.switched = []
+        try:
+            self._steps(tape, drawn)
+        finally:
+            self._switched = None
         torch.cuda.synchronize(self.dev)
         return dict(self._policy_logs(), **tape.result(), tape=tape)
 
@@ -774,8 +808,17 @@ class ClosedLoop:
         adjoint (and the measurement-noise gradient) unless the step took the unit-weight retry: still four launches.
         g_wq_wr is then the sum over the steps of dL/dW_t, the gradient for a constant offset added to every step's
         weights.  rule=True adds g_fuzzy_rule (B,7): dL/dtheta per instance.  Raises if the loop's rule is no longer the
-        tape's."""
+        tape's.
+        The tape of a switch loop (``switch_adjoint=True``): the step's tracking adjoint runs on a copy of the statuses
+        in which the switched instances carry TT_MAX_ITER, so it writes zeros for them (and nothing into g_wq_wr);
+        tt_obca_vjp_device then runs on the taped iterates of the compacted set with the gathered dL/dU, and its g_x0,
+        g_xref, g_uref take those rows before the window adjoint.  The compaction sizes are the tape's: no host
+        synchronisation.  model=True and rule=True raise on such a loop (the OBCA adjoint has no geometry or rule
+        gradient)."""
         self._check_differentiable()
+        if self.switch is not None and (model or rule):
+            raise ValueError("a switch (OBCA) loop has no model=True or rule=True gradient: the OBCA adjoint "
+                             "(switch_adjoint) gives dL/d(x_init, xref, uref) only")
         if tape.rule != self.rule:
             raise ValueError(f"the fuzzy rule changed since the tape was made: {tape.rule} -> {self.rule}; run the tape "
                              "again, or set the rule back before the backward")
@@ -831,6 +874,12 @@ class ClosedLoop:
             at = lambda t: plain  # noqa: E731
         plant_name, win_name = plant_vjp.__name__, win_vjp.__name__
         s.wait_stream(torch.cuda.current_stream(d))
+        sw, status = tape.switched or [None] * K, [tape.status[t] for t in range(K)]
+        with torch.cuda.stream(s):
+            for t in range(K):   # the tracking adjoint skips the switched instances
+                if sw[t] is not None:
+                    status[t] = tape.status[t].clone()
+                    status[t][sw[t][0]] = TT_MAX_ITER
         for t in range(K - 1, -1, -1):
             meas_in, w_t, win_tail = at(t)
             _check(plant_vjp(B, N, C.byref(p), POLICIES[self.policy], tape.S[t].data_ptr(), tape.status[t].data_ptr(),
@@ -842,10 +891,20 @@ class ClosedLoop:
                                           uref.data_ptr(), sp),
                    "tt_sim_window_device")
             self.solver.vjp_device(B, tape.X[t].data_ptr(), tape.U[t].data_ptr(), tape.dual[t].data_ptr(),
-                                   xref.data_ptr(), uref.data_ptr(), tape.status[t].data_ptr(), grad_u=gU.data_ptr(),
+                                   xref.data_ptr(), uref.data_ptr(), status[t].data_ptr(), grad_u=gU.data_ptr(),
                                    g_x0=g_x0.data_ptr(), g_xref=g_xr.data_ptr(), g_uref=g_ur.data_ptr(),
                                    g_wq_wr=g_ws.data_ptr(), wq_wr=w_t, stream=s.cuda_stream, g_model=g_model,
                                    accumulate=True)
+            if sw[t] is not None:
+                idx, it_c, st_c = sw[t]
+                n = int(idx.shape[0])
+                with torch.cuda.stream(s):
+                    gu_c = gU[idx].contiguous()
+                    o0, oxr, our = z(n, 6), z(n, N + 1, 6), z(n, N, 2)
+                    self.switch.vjp_device(n, it_c.data_ptr(), st_c.data_ptr(), grad_u=gu_c.data_ptr(),
+                                           g_x0=o0.data_ptr(), g_xref=oxr.data_ptr(), g_uref=our.data_ptr(),
+                                           stream=s.cuda_stream)
+                    g_x0[idx], g_xr[idx], g_ur[idx] = o0, oxr, our
             _check(win_vjp(B, N, int(tape.ks[t]), int(Np), g_xr.data_ptr(), g_ur.data_ptr(), g_px.data_ptr(),
                            g_pu.data_ptr(), g_x0.data_ptr(), GS[t].data_ptr(), a.data_ptr(), g_ws.data_ptr(),
                            g_w.data_ptr(), g_n[t].data_ptr() if meas else None, *win_tail), win_name)

@@ -267,6 +267,47 @@ int tt_obca_solve_batch_iterate_device(void* handle, int B, const double* d_x0, 
                                        double* d_kkt_res, double* d_iterate_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Reverse mode (vector-Jacobian product) of an MPC+OBCA solve (TT_VARIANT_TRACK_OBCA): for a scalar loss L(X, U) over
+ * the outputs of a solve, its gradient with respect to x_init, xref and uref in one pass.  The definition is the
+ * tracking adjoint's: with K the Newton matrix of the barrier problem at the exported primal-dual iterate (over
+ * x, u, the OBCA duals w, the row slacks s | the dynamics and OBCA row multipliers; bound multipliers eliminated into
+ * Sigma with the solver's relaxed bounds) and the upstream gradient g = dL/d(X, U),
+ *     K lam = (g, 0),     dL/dtheta = -lam' dF/dtheta.
+ * Every OBCA block (w 8, s 4, y_d 4) is eliminated onto the pose (X, Y, theta, psi) of its stage by a partially
+ * pivoted elimination, the stage system is solved by one un-regularised Riccati pass, and three refinement steps on
+ * the un-condensed system follow (obca_vjp_kernel).
+ *
+ * Inputs: iterate [B][tt_obca_iterate_len(N, M)] and status [B] exactly as tt_obca_solve_batch_iterate* returned
+ * them, and
+ *     grad_x [B][N+1][6]  dL/dx_k          grad_u [B][N][2]  dL/du_k
+ *   A NULL grad_x or grad_u stands for zeros; both NULL is -EINVAL.  Obstacles, geometry, bounds, Q and R are the
+ *   handle's.  xref and uref are not inputs: no output needs them.
+ * Outputs (tt_obca_vjp_out; every member may be NULL):
+ *     g_x0    [B][6]        dL/dx_init
+ *     g_xref  [B][N+1][6]   dL/dxref_k = 2 Q lam_x,k   (row k = 0 is exactly 0: x_0 is pinned to x_init)
+ *     g_uref  [B][N][2]     dL/duref_k = 2 R lam_u,k
+ *     vjp_status [B]        0 ok; 1 a block pivot or a reduced input Hessian failed, or a value (an upstream gradient
+ *                           entry included) was not finite; 2 the solve's status is above TT_ACCEPTABLE (skipped).
+ *                           For 1 and 2 the instance's three arrays are zeroed, so a failed instance contributes
+ *                           nothing to a batch gradient.
+ *   Signs: the arrays are gradients of L (descent moves a parameter against them).
+ *   First order only, the active set fixed: an obstacle row that is active stays active, one that is not stays out,
+ *   and a variable sitting on a bound carries (numerically) zero lam.
+ *   Only TT_VARIANT_TRACK_OBCA: a plan handle and a tracking handle return -EINVAL.  Gradients with respect to the
+ *   obstacles, d_min and the geometry are not formed.  The horizon must keep the instance's record in 64 KB of LDS
+ *   (N <= 76), else -EINVAL.
+ *
+ * tt_obca_vjp_device: device pointers (inside the host-side struct too), asynchronous on `stream`.  It uses no buffer
+ * of the handle, so it may run on any stream; the caller orders it behind the solve whose iterate it reads.
+ * tt_obca_vjp: the same with host pointers, synchronous (it stages through a buffer of the handle: one host call per
+ * handle at a time). */
+typedef struct { double* g_x0; double* g_xref; double* g_uref; int* vjp_status; } tt_obca_vjp_out;
+int tt_obca_vjp_device(void* handle, int B, const double* d_iterate, const int* d_status, const double* d_grad_x,
+                       const double* d_grad_u, const tt_obca_vjp_out* d_out, void* stream);
+int tt_obca_vjp(void* handle, int B, const double* iterate, const int* status, const double* grad_x,
+                const double* grad_u, const tt_obca_vjp_out* out);
+
+/* ---------------------------------------------------------------------------------------------
  * Closed-loop simulation step, device pointers, asynchronous on `stream`.
  * The per-timestep glue of python-files/simulation.py:484-531 around the solve, batched over B
  * Monte-Carlo instances so that the whole loop stays in HBM:

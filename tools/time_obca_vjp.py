@@ -1,0 +1,87 @@
+#!/usr/bin/env python3
+"""Time the MPC+OBCA adjoint (tt_obca_vjp_device) next to the solve it differentiates, with device events.
+
+Two shapes: the drivers' (B = 64, N = 50, M = 11: the golden windows, tiled) and B = 1024 on case A of
+tests/obca_vjp_reference.py (N = 6, M = 1).  Solve and adjoint alternate for several rounds, as tools/time_vjp.py does;
+the line per shape gives the median of each and the adjoint / solve ratio.
+
+    python tools/time_obca_vjp.py [--rounds 5]
+"""
+import argparse
+import json
+import sys
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path[:0] = [str(ROOT / "car-trailer-mpc_amd"), str(ROOT), str(ROOT / "tests")]
+
+
+def shapes():
+    import obca_vjp_reference as orf
+    from ttmpc import scenarios as sc
+    g = np.load(ROOT / "tests" / "golden" / "reference_numpy.npz")
+    x0, xr, ur = sc.mpc_obs_batch(g["state_traj"], g["input_traj"], 16, 50, seed=0)
+    t = 4
+    bnd = (sc.XLB, sc.XUB, sc.ULB, sc.UUB)
+    yield ("windows B=64 N=50 M=11", 50, dict(sc.OBCA_PARAMS, dt=0.05), bnd, g["obstacles"], np.tile(x0, (t, 1)),
+           np.tile(xr, (t, 1, 1)), np.tile(ur, (t, 1, 1)))
+    N, p, Q, R, bnd, obs, a, b, c = orf.case_a()
+    yield ("case A B=1024 N=6 M=1", N, p, bnd, obs, np.tile(a, (1024, 1)), np.tile(b, (1024, 1, 1)),
+           np.tile(c, (1024, 1, 1)))
+
+
+def main():
+    import torch
+    import ttmpc
+    from ttmpc import scenarios as sc
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    a = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    for name, N, p, bnd, obs, x0, xr, ur in shapes():
+        s = ttmpc.ObcaSolver(N, p, sc.OBCA_Q, sc.OBCA_R, *bnd, obs, variant=ttmpc.TT_VARIANT_TRACK_OBCA, device=0)
+        B = x0.shape[0]
+        t = lambda v: torch.as_tensor(np.ascontiguousarray(v), device=dev)  # noqa: E731
+        dx0, dxr, dur = t(x0), t(xr), t(ur)
+        new = lambda *sh: torch.empty(sh, dtype=torch.float64, device=dev)  # noqa: E731
+        X, U, I = new(B, N + 1, 6), new(B, N, 2), new(B, s.iterate_len())
+        st = torch.empty(B, dtype=torch.int32, device=dev)
+        gX = torch.rand(B, N + 1, 6, dtype=torch.float64, device=dev)
+        gU = torch.rand(B, N, 2, dtype=torch.float64, device=dev)
+        g0, gr, gu = new(B, 6), new(B, N + 1, 6), new(B, N, 2)
+        vs = torch.empty(B, dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+
+        def solve():
+            s.solve_device(B, dx0.data_ptr(), 0, dxr.data_ptr(), dur.data_ptr(), 0, X.data_ptr(), U.data_ptr(), 0,
+                           st.data_ptr(), stream=stream, iterate=I.data_ptr())
+
+        def adjoint():
+            s.vjp_device(B, I.data_ptr(), st.data_ptr(), grad_x=gX.data_ptr(), grad_u=gU.data_ptr(), g_x0=g0.data_ptr(),
+                         g_xref=gr.data_ptr(), g_uref=gu.data_ptr(), vjp_status=vs.data_ptr(), stream=stream)
+
+        def timed(fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            return e0.elapsed_time(e1)
+
+        solve()
+        adjoint()
+        torch.cuda.synchronize(dev)
+        ts, ta = [], []
+        for _ in range(a.rounds):
+            ts.append(timed(solve))
+            ta.append(timed(adjoint))
+        ms, ma = float(np.median(ts)), float(np.median(ta))
+        print(json.dumps({"shape": name, "solve_ms": round(ms, 3), "adjoint_ms": round(ma, 4),
+                          "adjoint_over_solve": round(ma / ms, 5), "solved": int((st <= 1).sum().item()),
+                          "adjoint_ok": int((vs == 0).sum().item()), "rounds": a.rounds}))
+
+
+if __name__ == "__main__":
+    main()
