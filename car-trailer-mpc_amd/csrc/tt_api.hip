@@ -52,6 +52,7 @@ struct Handle {
     tt_config cfg;
     double Q[36], R[4], xlb[6], xub[6], ulb[2], uub[2];
     double obs[4 * ttmpc::kObcaMaxM] = {};
+    double dmin = 0.2;  // trajectory_optimization.py:95, mpc_control_obs.py:67 (tt_set_scene)
     int device = 0;
     hipStream_t stream = nullptr;
     // tracking host calls: one packed device input / output block and its pinned host mirror, so a
@@ -795,7 +796,7 @@ int tt_obca_solve_batch_iterate_device(void* handle, int B, const double* d_x0, 
     a.W2 = h->cfg.W2;
     a.tol = h->cfg.tol;
     a.acc_tol = h->cfg.acc_tol;
-    a.dmin = 0.2;      // trajectory_optimization.py:95, mpc_control_obs.py:67
+    a.dmin = h->dmin;
     a.eq_tol = 1e-5;   // trajectory_optimization.py:136-139
     a.fin_tol = 1e-2;  // trajectory_optimization.py:172-173
     a.tfac = plan ? 100.0 : 1.0;  // trajectory_optimization.py:180 / mpc_control_obs.py:39
@@ -946,6 +947,119 @@ int tt_obca_vjp(void* handle, int B, const double* iterate, const int* status, c
     hipStream_t s = h->stream;
     return st.run(h, s, "OBCA adjoint",
                   [&] { return tt_obca_vjp_device(handle, B, d_it, d_st, d_gx, d_gu, &dout, s); });
+}
+
+// tt_obca_vjp_params*: the checks both entries share, in tt_obca_vjp's order
+static int obca_vjp_params_checks(Handle* h, int B, const void* grad_x, const void* grad_u, const void* xref,
+                                  const void* uref, const tt_obca_vjp_params_out* out) {
+    if (const int rc = prelude(h, B, kHandle | kObcaOnly | kNotPlan | kSign)) return rc;
+    if (!grad_x && !grad_u) return fail(h, -EINVAL, "grad_x and grad_u are both NULL: no loss to differentiate%s");
+    if (const int rc = obca_vjp_horizon(h)) return rc;
+    if (out && ((out->g_Q && !xref) || (out->g_R && !uref)))
+        return fail(h, -EINVAL, "g_Q needs xref and g_R needs uref%s");
+    return 0;
+}
+
+long long tt_obca_vjp_params_work_bytes(int N, int M) {
+    return (N < 1 || M < 1) ? -EINVAL : (long long)(8 * ttmpc::obca_vjp_params_work_doubles(N, M));
+}
+
+int tt_obca_vjp_params_device(void* handle, int B, const double* d_iterate, const int* d_status, const double* d_xref,
+                              const double* d_uref, const double* d_grad_x, const double* d_grad_u,
+                              const tt_obca_vjp_params_out* d_out, void* d_work, void* stream) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (const int rc = obca_vjp_params_checks(h, B, d_grad_x, d_grad_u, d_xref, d_uref, d_out)) return rc;
+    if (!d_work) return fail(h, -EINVAL, "NULL work buffer (tt_obca_vjp_params_work_bytes per instance)%s");
+    if (const int rc = prelude(h, B, kEmpty | kRange)) return result(rc);
+    if (!d_iterate || !d_status || !d_out) return fail(h, -EINVAL, "NULL device buffer%s");
+    DeviceGuard dg(h->device);
+    if (dg.err != hipSuccess) return hip_fail(h, dg.err, "hipSetDevice");
+    ttmpc::ObcaVjpParamsArgs a =
+        diff_args<ttmpc::ObcaVjpParamsArgs>(h, B, nullptr, nullptr, nullptr, nullptr, d_status);
+    a.M = h->cfg.M;
+    a.W1 = h->cfg.W1;
+    a.W2 = h->cfg.W2;
+    a.eq_tol = 1e-5;  // trajectory_optimization.py:136-139, as the solve sets it
+    memcpy(a.obs, h->obs, sizeof a.obs);
+    a.iterate = d_iterate;
+    a.gx = d_grad_x;
+    a.gu = d_grad_u;
+    a.g_x0 = d_out->g_x0;
+    a.g_xref = d_out->g_xref;
+    a.g_uref = d_out->g_uref;
+    a.vjp_status = d_out->vjp_status;
+    a.xref = d_xref;
+    a.uref = d_uref;
+    a.g_obs = d_out->g_obstacles;
+    a.g_dmin = d_out->g_dmin;
+    a.g_Q = d_out->g_Q;
+    a.g_R = d_out->g_R;
+    a.work = static_cast<double*>(d_work);
+    const hipError_t e = ttmpc::launch_obca_vjp_params(a, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(h, e, "OBCA params adjoint kernel launch");
+    return 0;
+}
+
+int tt_obca_vjp_params(void* handle, int B, const double* iterate, const int* status, const double* xref,
+                       const double* uref, const double* grad_x, const double* grad_u,
+                       const tt_obca_vjp_params_out* out) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (const int rc = obca_vjp_params_checks(h, B, grad_x, grad_u, xref, uref, out)) return rc;  // (nothing staged yet)
+    if (const int rc = prelude(h, B, kEmpty | kRange)) return result(rc);
+    if (!iterate || !status || !out) return fail(h, -EINVAL, "NULL host buffer%s");
+    DeviceGuard dg(h->device);
+    if (dg.err != hipSuccess) return hip_fail(h, dg.err, "hipSetDevice");
+    const size_t N = h->cfg.N, M = h->cfg.M, b = (size_t)B, nx = b * (N + 1) * 6, nu = b * N * 2;
+    Stager st;
+    const double *d_it, *d_gx, *d_gu, *d_xr, *d_ur;
+    const int* d_st;
+    double* d_work;
+    tt_obca_vjp_params_out dout;
+    st.in(iterate, b * ttmpc::obca_iterate_len(h->cfg.N, h->cfg.M), &d_it);
+    st.in(grad_x, nx, &d_gx);
+    st.in(grad_u, nu, &d_gu);
+    st.in(status, b, &d_st);
+    st.in(out->g_Q ? xref : nullptr, nx, &d_xr);  // (read for g_Q / g_R only)
+    st.in(out->g_R ? uref : nullptr, nu, &d_ur);
+    st.out(out->g_x0, b * 6, &dout.g_x0);
+    st.out(out->g_xref, nx, &dout.g_xref);
+    st.out(out->g_uref, nu, &dout.g_uref);
+    st.out(out->vjp_status, b, &dout.vjp_status);
+    st.out(out->g_obstacles, b * M * 4, &dout.g_obstacles);
+    st.out(out->g_dmin, b, &dout.g_dmin);
+    st.out(out->g_Q, b * 36, &dout.g_Q);
+    st.out(out->g_R, b * 4, &dout.g_R);
+    st.out((double*)nullptr, b * ttmpc::obca_vjp_params_work_doubles(h->cfg.N, h->cfg.M), &d_work, true);
+    if (!st.carve(h->xfer)) return no_memory(h, "adjoint staging");
+    hipStream_t s = h->stream;
+    return st.run(h, s, "OBCA params adjoint", [&] {
+        return tt_obca_vjp_params_device(handle, B, d_it, d_st, d_xr, d_ur, d_gx, d_gu, &dout, d_work, s);
+    });
+}
+
+int tt_set_scene(void* handle, const double* obstacles, const double* d_min) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (const int rc = prelude(h, 0, kHandle | kObcaOnly)) return rc;
+    const int M = h->cfg.M;
+    if (obstacles)
+        for (int m = 0; m < M; ++m) {
+            const double* o = obstacles + 4 * m;
+            if (!isfinite(o[0]) || !isfinite(o[1]) || !isfinite(o[2]) || !isfinite(o[3]) || !(o[2] > 0) || !(o[3] > 0))
+                return fail(h, -EINVAL, "obstacles must be finite with w, h > 0%s");
+        }
+    if (d_min && (!isfinite(*d_min) || *d_min < 0)) return fail(h, -EINVAL, "d_min must be finite and >= 0%s");
+    // every launch fills its kernel arguments from the handle: nothing on the device holds the old scene
+    if (obstacles) memcpy(h->obs, obstacles, sizeof(double) * 4 * M);
+    if (d_min) h->dmin = *d_min;
+    return 0;
+}
+
+int tt_get_scene(void* handle, double* obstacles, double* d_min) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (const int rc = prelude(h, 0, kHandle | kObcaOnly)) return rc;
+    if (obstacles) memcpy(obstacles, h->obs, sizeof(double) * 4 * h->cfg.M);
+    if (d_min) *d_min = h->dmin;
+    return 0;
 }
 
 /* diagnostics only (not part of include/ttmpc.h): per-instance phase cycle sums of the handle's next OBCA

@@ -208,5 +208,19 @@ inline int obca_vjp_max_horizon() {  // (512 bytes stay free for the compiler's 
     return ((64 * 1024 - 512) / 8 - kObcaVjpFixed - kObcaVjpStage) / (kObcaVjpStage + 12);
 }
 hipError_t launch_obca_vjp(const ObcaVjpArgs& a, hipStream_t stream);
+// the same adjoint plus dL/d(obstacles, d_min, Q, R): the kernel's params instantiation (the same LDS record).  The
+// members sit behind ObcaVjpArgs so that the plain instantiation's argument block, and with it its code, stays what it
+// was.  The block unknowns (16 per block) are carried across the refinement steps in `work`
+struct ObcaVjpParamsArgs : ObcaVjpArgs {
+    const double* xref;   // [B][N+1][6]; read for g_Q only
+    const double* uref;   // [B][N][2];   read for g_R only
+    double* g_obs;        // [B][M][4] (cx, cy, w, h) or nullptr
+    double* g_dmin;       // [B] or nullptr
+    double* g_Q;          // [B][6][6] or nullptr
+    double* g_R;          // [B][2][2] or nullptr
+    double* work;         // [B][2M(N+1)][16]: one 128-byte record per block, never nullptr here
+};
+__host__ __device__ inline size_t obca_vjp_params_work_doubles(int N, int M) { return (size_t)32 * M * (N + 1); }
+hipError_t launch_obca_vjp_params(const ObcaVjpParamsArgs& a, hipStream_t stream);
 
 }  // namespace ttmpc

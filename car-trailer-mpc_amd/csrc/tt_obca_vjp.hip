@@ -34,7 +34,19 @@
 // LDS: 87 doubles per stage (the adjoint's record 33, the addend 16, the refinement's fields 38), 12 per input stage,
 // 164 tile doubles, 256 slot doubles and the 64 obstacle doubles: 43.1 KB at N = 50 for any M.  No buffer of the handle
 // is used.  Plain IEEE arithmetic, no contraction: tests/obca_vjp_reference.py (model_obca_vjp) is the numpy model.
+//
+// The params instantiation (tt_obca_vjp_params_device) also forms dL/d(obstacles, d_min, Q, R).  Only row 1 of a block
+// and the stationarity rows of lam depend on the obstacle's offsets b and on d_min, linearly, so the gradients are sums
+// over the blocks of entries of v, the block's 16 entries of lam.  Recomputing v from the final pose adjoint loses three
+// to four digits where a row is active (v_yd1 is 4e13 times a 1e-12 component of the pose adjoint), so this
+// instantiation CARRIES v across the refinement steps (carry_block): u = v + t per block in a caller-provided HBM
+// workspace, one 128-byte record per block; a pass takes v = u - K_b^-1 C dlx_pose with the last correction, then the
+// residual against that v; one closing pass after the last step applies the last correction and reduces the blocks'
+// five terms per obstacle in block order (slots, then registers: no atomics, no LDS beyond the record above).
+// tests/obca_scene_reference.py (model_scene_vjp) is its numpy model.
 #include <math.h>
+
+#include <type_traits>
 
 #include "tt_kernel.hpp"
 #include "tt_sens_stage.hpp"
@@ -310,6 +322,81 @@ __device__ __forceinline__ bool refine_block(double (&row)[20], const double (&h
     return ok;
 }
 
+// The params instantiation's block pass (one row of K_b per lane, C in row[16 ..]), with the block unknowns carried:
+// uin is entry r of the block's record u = v + t of the previous pass (zero before the first), dlx the pose part of the
+// last correction (of the first solve before the first pass), lxp the running pose adjoint.  Factor K_b; the previous
+// step's correction v = u - K_b^-1 C dlx (it enters through dlx, never through the rounded sum lxp: v_yd1 is 4e13 times
+// a 1e-12 component of the pose adjoint); then the residual r = -(C lxp + K_b v) against the carried v and
+// t = K_b^-1 r.  Lane r leaves with entry r of v in vr and of v + t in ur (the order of the unknowns: w 8, s 4, y_d 4),
+// every lane with out[0..3] = H_xx lxp + C' v and out[4..7] = -C' t.  kClosing: v alone (the pass after the last step).
+template <bool kClosing>
+__device__ __forceinline__ bool carry_block(double (&row)[20], const double (&hxx)[3], int r, const double (&dlx)[4],
+                                            const double (&lxp)[4], double uin, double& vr, double& ur,
+                                            double (&out)[8]) {
+    double orig[16], c0[4];
+#pragma unroll
+    for (int t = 0; t < 16; ++t) orig[t] = row[t];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) c0[t] = row[16 + t];
+    int mycol;
+    unsigned long long rows;
+    bool ok = factor_rows<16, true>(row, r, mycol, rows);
+    const int holder = (int)((rows >> (4 * r)) & 15ull);  // the lane that pivoted on column r holds unknown r
+    // one right-hand side (equation r in lane r) through the factors; lane r leaves with the unknown r
+    auto solve = [&](double y) {
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            const double yp = __shfl(y, (int)((rows >> (4 * c)) & 15ull), kGL);
+            if (mycol > c) y = y - row[c] * yp;
+        }
+#pragma unroll
+        for (int c = 15; c >= 0; --c) {
+            if (mycol == c) y = y / row[c];
+            const double xc = __shfl(y, (int)((rows >> (4 * c)) & 15ull), kGL);
+            if (mycol < c) y = y - row[c] * xc;
+        }
+        return __shfl(y, holder, kGL);
+    };
+    double bd = 0.0;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) bd += c0[t] * dlx[t];
+    vr = uin + solve(-bd);
+    ur = vr;
+    ok = ok && isfinite(vr);
+    if (kClosing) return ok;
+    double b0 = 0.0, kv = 0.0;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) b0 += c0[t] * lxp[t];
+    b0 = -b0;
+#pragma unroll
+    for (int jn = 0; jn < 16; ++jn) kv += orig[jn] * __shfl(vr, jn, kGL);
+    const double tt = solve(b0 - kv);
+    ur = vr + tt;
+#pragma unroll
+    for (int aa = 0; aa < 4; ++aa) {
+        double sv = c0[aa] * vr, st = c0[aa] * tt;  // (K is symmetric: row r of C belongs to unknown r)
+        for (int m = kGL / 2; m > 0; m >>= 1) {
+            sv += __shfl_xor(sv, m, kGL);
+            st += __shfl_xor(st, m, kGL);
+        }
+        const double h = aa < 2 ? 0.0 : hxx[aa - 2] * lxp[2] + hxx[aa - 1] * lxp[3];  // rows 2, 3 of H_xx
+        out[aa] = h + sv;
+        out[4 + aa] = -st;
+        ok = ok && isfinite(out[aa]) && isfinite(out[4 + aa]);
+    }
+    return ok && isfinite(ur);
+}
+
+__device__ __forceinline__ void zero_params(const ObcaVjpParamsArgs& a, int b, int tid) {
+    if (a.g_obs)
+        for (int t = tid; t < 4 * a.M; t += kT) a.g_obs[(size_t)b * 4 * a.M + t] = 0.0;
+    if (a.g_dmin && tid == 0) a.g_dmin[b] = 0.0;
+    if (a.g_Q)
+        for (int t = tid; t < 36; t += kT) a.g_Q[(size_t)b * 36 + t] = 0.0;
+    if (a.g_R)
+        for (int t = tid; t < 4; t += kT) a.g_R[(size_t)b * 4 + t] = 0.0;
+}
+
 // forward sweep: lx_0 = 0; lu_k = -K_k lx_k + kappa_k; lx_{k+1} = A_k lx_k + B lu_k, into the Sigma slots of the stages
 __device__ __forceinline__ void forward_sweep(double* stg, const double* Ks, int N, double dt, int tid, bool& bad) {
     if (tid < 6) stg[sSG + tid] = 0.0;
@@ -343,12 +430,16 @@ __device__ __forceinline__ void forward_sweep(double* stg, const double* Ks, int
     }
 }
 
-__global__ __launch_bounds__(kT) void obca_vjp_kernel(ObcaVjpArgs a) {
+// kParams: the instantiation that also forms dL/d(obstacles, d_min, Q, R) (tt_obca_vjp_params*); everything it adds sits
+// behind `if constexpr`, so the plain instantiation is the kernel it was
+template <bool kParams>
+__global__ __launch_bounds__(kT) void obca_vjp_kernel(std::conditional_t<kParams, ObcaVjpParamsArgs, ObcaVjpArgs> a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int N = a.N, S = N + 1, nbk = 2 * a.M, nblk = S * nbk;
     if (a.status[b] > 1) {  // > TT_ACCEPTABLE: no optimum to differentiate
         zero_outputs(a, b, tid);
+        if constexpr (kParams) zero_params(a, b, tid);
         if (a.vjp_status && tid == 0) a.vjp_status[b] = 2;
         return;
     }
@@ -446,6 +537,7 @@ __global__ __launch_bounds__(kT) void obca_vjp_kernel(ObcaVjpArgs a) {
     forward_sweep(stg, Ks, N, dt, tid, bad);
     if (__syncthreads_or(bad)) {
         zero_outputs(a, b, tid);
+        if constexpr (kParams) zero_params(a, b, tid);
         if (a.vjp_status && tid == 0) a.vjp_status[b] = 1;
         return;
     }
@@ -463,30 +555,69 @@ __global__ __launch_bounds__(kT) void obca_vjp_kernel(ObcaVjpArgs a) {
             for (int v = 0; v < 8; ++v) stg[k * kStage + sW + v] = 0.0;
         }
         __syncthreads();
-        for (int f0 = nbk; f0 < nblk; f0 += kGroups) {
-            const int f = min(f0 + grp, nblk - 1);
-            const int k = f / nbk, j = f - k * nbk;
-            double row[20], hxx[3], lxp[4], out[8];
-            build_row(a, obs, it + 30 * (size_t)k, j, blk + 32 * (size_t)f, r16, row, hxx);
+        if constexpr (kParams) {
+            // the carried pass: the records of the next round are loaded before this round's are stored (a load issued
+            // behind a store waits for it)
+            double* wk = a.work + (size_t)b * nblk * 16;
+            double ucur = step > 0 ? wk[(size_t)min(nbk + grp, nblk - 1) * 16 + r16] : 0.0;
+            for (int f0 = nbk; f0 < nblk; f0 += kGroups) {
+                const int f = min(f0 + grp, nblk - 1);
+                const int k = f / nbk, j = f - k * nbk;
+                double unext = 0.0;
+                if (step > 0 && f0 + kGroups < nblk) unext = wk[(size_t)min(f0 + kGroups + grp, nblk - 1) * 16 + r16];
+                double row[20], hxx[3], dlx[4], lxp[4], out[8], vr, ur;
+                build_row(a, obs, it + 30 * (size_t)k, j, blk + 32 * (size_t)f, r16, row, hxx);
 #pragma unroll
-            for (int t = 0; t < 4; ++t) lxp[t] = stg[k * kStage + sL + t];
-            const bool ok = refine_block(row, hxx, r16, lxp, out);
-            if (f0 + grp < nblk) {
-                bad |= !ok;
-                if (r16 == 0) {
+                for (int t = 0; t < 4; ++t) {
+                    lxp[t] = stg[k * kStage + sL + t];
+                    dlx[t] = stg[k * kStage + sSG + t];  // (the last correction; the first solve itself in step 0)
+                }
+                const bool ok = carry_block<false>(row, hxx, r16, dlx, lxp, ucur, vr, ur, out);
+                if (f0 + grp < nblk) {
+                    bad |= !ok;
+                    wk[(size_t)f * 16 + r16] = ur;
+                    if (r16 == 0) {
 #pragma unroll
-                    for (int t = 0; t < 8; ++t) slot[grp * 16 + t] = out[t];
+                        for (int t = 0; t < 8; ++t) slot[grp * 16 + t] = out[t];
+                    }
                 }
-            }
-            __syncthreads();
-            if (tid < 8) {
-                const int ng = min(kGroups, nblk - f0);
-                for (int g = 0; g < ng; ++g) {
-                    const int kk = (f0 + g) / nbk;
-                    stg[kk * kStage + sW + tid] += slot[g * 16 + tid];
+                __syncthreads();
+                if (tid < 8) {
+                    const int ng = min(kGroups, nblk - f0);
+                    for (int g = 0; g < ng; ++g) {
+                        const int kk = (f0 + g) / nbk;
+                        stg[kk * kStage + sW + tid] += slot[g * 16 + tid];
+                    }
                 }
+                __syncthreads();
+                ucur = unext;
             }
-            __syncthreads();
+        } else {
+            for (int f0 = nbk; f0 < nblk; f0 += kGroups) {
+                const int f = min(f0 + grp, nblk - 1);
+                const int k = f / nbk, j = f - k * nbk;
+                double row[20], hxx[3], lxp[4], out[8];
+                build_row(a, obs, it + 30 * (size_t)k, j, blk + 32 * (size_t)f, r16, row, hxx);
+#pragma unroll
+                for (int t = 0; t < 4; ++t) lxp[t] = stg[k * kStage + sL + t];
+                const bool ok = refine_block(row, hxx, r16, lxp, out);
+                if (f0 + grp < nblk) {
+                    bad |= !ok;
+                    if (r16 == 0) {
+#pragma unroll
+                        for (int t = 0; t < 8; ++t) slot[grp * 16 + t] = out[t];
+                    }
+                }
+                __syncthreads();
+                if (tid < 8) {
+                    const int ng = min(kGroups, nblk - f0);
+                    for (int g = 0; g < ng; ++g) {
+                        const int kk = (f0 + g) / nbk;
+                        stg[kk * kStage + sW + tid] += slot[g * 16 + tid];
+                    }
+                }
+                __syncthreads();
+            }
         }
         // ---- stage part: lam_y from the x-rows, the input rows' residual, the correction's right-hand side ----
         for (int k = tid; k <= N; k += kT) {  // rr_k = gX_k - H0_k lx_k - w_k into sY
@@ -560,8 +691,43 @@ __global__ __launch_bounds__(kT) void obca_vjp_kernel(ObcaVjpArgs a) {
         }
         __syncthreads();
     }
+    // ---- the closing block pass: the last correction into v; the blocks' scene terms per obstacle in block order ----
+    double acc = 0.0;  // thread 5 m + i: g_b[i] (i < 4) or the d_min sum (i = 4) of obstacle m
+    if constexpr (kParams) {
+        const double* wk = a.work + (size_t)b * nblk * 16;
+        const int am = tid / 5, ai = tid - 5 * am;
+        for (int f0 = nbk; f0 < nblk; f0 += kGroups) {
+            const int f = min(f0 + grp, nblk - 1);
+            const int k = f / nbk, j = f - k * nbk;
+            const double uin = wk[(size_t)f * 16 + r16];
+            double row[20], hxx[3], dlx[4], out[8], vr, ur;
+            const double* q = blk + 32 * (size_t)f;
+            build_row(a, obs, it + 30 * (size_t)k, j, q, r16, row, hxx);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) dlx[t] = stg[k * kStage + sSG + t];
+            const bool ok = carry_block<true>(row, hxx, r16, dlx, dlx, uin, vr, ur, out);
+            const double vl = __shfl(vr, 4 + (r16 & 3), kGL), vy = __shfl(vr, 12, kGL);
+            if (f0 + grp < nblk) {
+                bad |= !ok;
+                // row 1 of the block: g' mu - (A p - b)' lam + d_min - s_1 = 0, and b also in the lam rows through y_d1
+                if (r16 < 4) slot[grp * 16 + r16] = -(q[28] * vl + q[4 + r16] * vy);
+                if (r16 == 4) slot[grp * 16 + 4] = -vy;
+            }
+            __syncthreads();
+            if (tid < 5 * kObcaMaxM) {
+                const int ng = min(kGroups, nblk - f0);
+                int jj = f0 % nbk;
+                for (int g = 0; g < ng; ++g) {
+                    if ((jj >> 1) == am) acc += slot[g * 16 + ai];
+                    if (++jj == nbk) jj = 0;
+                }
+            }
+            __syncthreads();
+        }
+    }
     if (__syncthreads_or(bad)) {
         zero_outputs(a, b, tid);
+        if constexpr (kParams) zero_params(a, b, tid);
         if (a.vjp_status && tid == 0) a.vjp_status[b] = 1;
         return;
     }
@@ -586,8 +752,58 @@ __global__ __launch_bounds__(kT) void obca_vjp_kernel(ObcaVjpArgs a) {
             }
         }
     }
+    if constexpr (kParams) {
+        if (tid < 5 * kObcaMaxM) slot[tid] = acc;
+        __syncthreads();
+        if (tid < a.M) {  // b = (cx + w/2, cy + h/2, -cx + w/2, -cy + h/2)
+            const double g0 = slot[5 * tid], g1 = slot[5 * tid + 1], g2 = slot[5 * tid + 2], g3 = slot[5 * tid + 3];
+            const double o0 = g0 - g2, o1 = g1 - g3, o2 = 0.5 * (g0 + g2), o3 = 0.5 * (g1 + g3);
+            bad |= !isfinite(o0) || !isfinite(o1) || !isfinite(o2) || !isfinite(o3);
+            if (a.g_obs) {
+                double* go = a.g_obs + ((size_t)b * a.M + tid) * 4;
+                go[0] = o0;
+                go[1] = o1;
+                go[2] = o2;
+                go[3] = o3;
+            }
+        }
+        if (tid == 64) {
+            double s = 0.0;
+            for (int m = 0; m < a.M; ++m) s += slot[5 * m + 4];
+            bad |= !isfinite(s);
+            if (a.g_dmin) a.g_dmin[b] = s;
+        }
+        // dL/dQ[i][l] = -sum_k (lx_k[i] e_k[l] + lx_k[l] e_k[i]), e = x - xref; dL/dR alike on the inputs
+        if (a.g_Q && tid >= 128 && tid < 164) {
+            const int i = (tid - 128) / 6, l = (tid - 128) % 6;
+            const double* xr = a.xref + (size_t)b * S * 6;
+            double s = 0.0;
+            for (int k = 0; k <= N; ++k) {
+                const double* r = stg + k * kStage + sL;
+                const double* q = it + 30 * (size_t)k;
+                s = s - (r[i] * (q[l] - xr[k * 6 + l]) + r[l] * (q[i] - xr[k * 6 + i]));
+            }
+            bad |= !isfinite(s);
+            a.g_Q[(size_t)b * 36 + tid - 128] = s;
+        }
+        if (a.g_R && tid >= 192 && tid < 196) {
+            const int i = (tid - 192) / 2, l = (tid - 192) % 2;
+            const double* ur = a.uref + (size_t)b * N * 2;
+            double s = 0.0;
+            for (int k = 0; k < N; ++k) {
+                const double* r = stg + k * kStage + sL + 6;
+                const double* q = it + 30 * (size_t)k + 6;
+                s = s - (r[i] * (q[l] - ur[k * 2 + l]) + r[l] * (q[i] - ur[k * 2 + i]));
+            }
+            bad |= !isfinite(s);
+            a.g_R[(size_t)b * 4 + tid - 192] = s;
+        }
+    }
     const bool late = __syncthreads_or(bad) != 0;  // an overflow in the output products (the barrier orders the stores)
     if (late) zero_outputs(a, b, tid);
+    if constexpr (kParams) {
+        if (late) zero_params(a, b, tid);
+    }
     if (a.vjp_status && tid == 0) a.vjp_status[b] = late ? 1 : 0;
 }
 
@@ -596,7 +812,14 @@ __global__ __launch_bounds__(kT) void obca_vjp_kernel(ObcaVjpArgs a) {
 hipError_t launch_obca_vjp(const ObcaVjpArgs& a, hipStream_t stream) {
     const int bytes = 8 * obca_vjp_lds_doubles(a.N);
     if (bytes > 64 * 1024 - 512 || a.M < 1 || a.M > kObcaMaxM) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(obca_vjp_kernel, dim3(a.B), dim3(kT), bytes, stream, a);
+    hipLaunchKernelGGL(obca_vjp_kernel<false>, dim3(a.B), dim3(kT), bytes, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_obca_vjp_params(const ObcaVjpParamsArgs& a, hipStream_t stream) {
+    const int bytes = 8 * obca_vjp_lds_doubles(a.N);
+    if (bytes > 64 * 1024 - 512 || a.M < 1 || a.M > kObcaMaxM || !a.work) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(obca_vjp_kernel<true>, dim3(a.B), dim3(kT), bytes, stream, a);
     return hipGetLastError();
 }
 

@@ -68,6 +68,12 @@ class TTObcaVjpOut(C.Structure):
     _fields_ = [("g_x0", C.c_void_p), ("g_xref", C.c_void_p), ("g_uref", C.c_void_p), ("vjp_status", C.c_void_p)]
 
 
+class TTObcaVjpParamsOut(C.Structure):
+    """tt_obca_vjp_params_out (include/ttmpc.h): tt_obca_vjp_out and the scene and weight gradients behind it."""
+    _fields_ = TTObcaVjpOut._fields_ + [("g_obstacles", C.c_void_p), ("g_dmin", C.c_void_p), ("g_Q", C.c_void_p),
+                                        ("g_R", C.c_void_p)]
+
+
 class TTLqrVjpOut(C.Structure):
     """tt_lqr_vjp_out (include/ttmpc.h): the outputs of tt_lqr_score_vjp_device; NULL members are skipped."""
     _fields_ = [("g_x_cur", C.c_void_p), ("g_x_goal", C.c_void_p), ("g_Q", C.c_void_p), ("g_R", C.c_void_p),
@@ -95,6 +101,17 @@ class TrackVjpResult:
 
 
 TrackVjpModelResult = TrackVjpResult
+
+
+class ObcaVjpParamsResult:
+    """What ``ObcaSolver.vjp(..., params=True)`` returns: g_x0, g_xref, g_uref and vjp_status as ``TrackVjpResult``,
+    and g_obstacles (B,M,4) = dL/d(cx, cy, w, h), g_dmin (B,), g_Q (B,6,6) and g_R (B,2,2) (None without xref / uref),
+    all per instance; the arrays of a failed instance are zeros."""
+    __slots__ = ("g_x0", "g_xref", "g_uref", "vjp_status", "g_obstacles", "g_dmin", "g_Q", "g_R")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
 
 
 class TrackExResult:
@@ -193,6 +210,18 @@ def lib():
         L.tt_obca_vjp_device.restype = C.c_int
         L.tt_obca_vjp.argtypes = [C.c_void_p, C.c_int, _dp, _ip, _dp, _dp, C.POINTER(TTObcaVjpOut)]
         L.tt_obca_vjp.restype = C.c_int
+    if not os.environ.get("TTMPC_LIB") or hasattr(L, "tt_obca_vjp_params_device"):
+        po = C.POINTER(TTObcaVjpParamsOut)
+        L.tt_obca_vjp_params_work_bytes.argtypes = [C.c_int, C.c_int]
+        L.tt_obca_vjp_params_work_bytes.restype = C.c_longlong
+        L.tt_obca_vjp_params_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [po, C.c_void_p, C.c_void_p]
+        L.tt_obca_vjp_params_device.restype = C.c_int
+        L.tt_obca_vjp_params.argtypes = [C.c_void_p, C.c_int, _dp, _ip, _dp, _dp, _dp, _dp, po]
+        L.tt_obca_vjp_params.restype = C.c_int
+        L.tt_set_scene.argtypes = [C.c_void_p, _dp, _dp]
+        L.tt_set_scene.restype = C.c_int
+        L.tt_get_scene.argtypes = [C.c_void_p, _dp, _dp]
+        L.tt_get_scene.restype = C.c_int
     L.tt_obca_n.argtypes = [C.c_int, C.c_int]
     L.tt_obca_n.restype = C.c_longlong
     L.tt_obca_workspace_bytes.argtypes = [C.c_int, C.c_int]
@@ -256,7 +285,8 @@ EXPORTED_SYMBOLS = ("tt_create", "tt_solve_batch", "tt_solve_batch_device", "tt_
                     "tt_lqr_score_vjp_device", "tt_track_vjp_model_device", "tt_track_vjp_model", "tt_set_model",
                     "tt_get_model", "tt_policy_plant_vjp_model_device", "tt_fuzzy_weights_rule_device",
                     "tt_fuzzy_weights_vjp_device", "tt_sim_window_vjp_fuzzy_device", "tt_obca_vjp_device",
-                    "tt_obca_vjp")
+                    "tt_obca_vjp", "tt_obca_vjp_params_work_bytes", "tt_obca_vjp_params_device", "tt_obca_vjp_params",
+                    "tt_set_scene", "tt_get_scene")
 
 
 def _ptr(a):
@@ -616,21 +646,63 @@ class ObcaSolver(_Solver):
         """tt_obca_iterate_len of this handle's (N, M)."""
         return int(self._L.tt_obca_iterate_len(self.N, self.M))
 
-    def vjp_device(self, B, iterate, status, grad_x=0, grad_u=0, g_x0=0, g_xref=0, g_uref=0, vjp_status=0, stream=0):
+    def set_scene(self, obstacles=None, d_min=None):
+        """tt_set_scene: the handle's obstacles (M,4) of (cx, cy, w, h) (M is fixed) and its safety margin d_min (0.2
+        unless set); a value left None keeps the current one.  Host-side state only: every later call uses it."""
+        ob = None if obstacles is None else _f64(obstacles, (self.M, 4))
+        dm = None if d_min is None else np.array([float(d_min)])
+        rc = self._L.tt_set_scene(self._h, _ptr(ob), _ptr(dm))
+        if rc != 0:
+            self._err(rc, "tt_set_scene")
+        if ob is not None:
+            self.obstacles = ob.copy()
+
+    def scene(self):
+        """tt_get_scene -> (obstacles (M,4), d_min)."""
+        ob, dm = np.empty((self.M, 4)), np.empty(1)
+        rc = self._L.tt_get_scene(self._h, _ptr(ob), _ptr(dm))
+        if rc != 0:
+            self._err(rc, "tt_get_scene")
+        return ob, float(dm[0])
+
+    def vjp_params_work_bytes(self):
+        """tt_obca_vjp_params_work_bytes of this handle's (N, M): bytes of ``work`` per instance."""
+        return int(self._L.tt_obca_vjp_params_work_bytes(self.N, self.M))
+
+    def vjp_device(self, B, iterate, status, grad_x=0, grad_u=0, g_x0=0, g_xref=0, g_uref=0, vjp_status=0, stream=0,
+                   xref=0, uref=0, g_obstacles=0, g_dmin=0, g_Q=0, g_R=0, work=0):
         """tt_obca_vjp_device (TT_VARIANT_TRACK_OBCA): the adjoint kernel on the device iterate and status of an earlier
         ``solve_device(..., iterate=ptr)`` and the upstream gradients grad_x = dL/dX, grad_u = dL/dU (0 = zeros, not
         both).  Outputs (0 = not wanted): g_x0, g_xref, g_uref, vjp_status.  Uses no buffer of the handle: any stream
-        will do, behind the solve whose iterate it reads."""
+        will do, behind the solve whose iterate it reads.
+
+        With ``work`` (B * vjp_params_work_bytes() bytes) or one of g_obstacles (B,M,4), g_dmin (B,), g_Q (B,6,6),
+        g_R (B,2,2) the call is tt_obca_vjp_params_device: the same adjoint with the block unknowns carried, plus the
+        scene and weight gradients; xref / uref are the solve's (needed for g_Q / g_R only)."""
+        if work or g_obstacles or g_dmin or g_Q or g_R:
+            pout = TTObcaVjpParamsOut(g_x0 or None, g_xref or None, g_uref or None, vjp_status or None,
+                                      g_obstacles or None, g_dmin or None, g_Q or None, g_R or None)
+            rc = self._L.tt_obca_vjp_params_device(self._h, int(B), iterate or None, status or None, xref or None,
+                                                   uref or None, grad_x or None, grad_u or None, C.byref(pout),
+                                                   work or None, stream or None)
+            if rc != 0:
+                self._err(rc, "tt_obca_vjp_params_device")
+            return
         out = TTObcaVjpOut(g_x0 or None, g_xref or None, g_uref or None, vjp_status or None)
         rc = self._L.tt_obca_vjp_device(self._h, int(B), iterate or None, status or None, grad_x or None,
                                         grad_u or None, C.byref(out), stream or None)
         if rc != 0:
             self._err(rc, "tt_obca_vjp_device")
 
-    def vjp(self, iterate, status, grad_x, grad_u):
+    def vjp(self, iterate, status, grad_x, grad_u, xref=None, uref=None, params=False):
         """Host arrays: the gradient of a scalar loss L(X, U) with respect to x_init, xref and uref of the MPC+OBCA
         solve that returned iterate (B, tt_obca_iterate_len) and status (B,); grad_x (B,N+1,6) = dL/dX and grad_u (B,N,2) =
-        dL/dU (either may be None for zeros).  Returns a ``TrackVjpResult`` (g_wq_wr and g_model are None)."""
+        dL/dU (either may be None for zeros).  Returns a ``TrackVjpResult`` (g_wq_wr and g_model are None).
+
+        ``params=True``: tt_obca_vjp_params, an ``ObcaVjpParamsResult`` with g_obstacles and g_dmin and, where the
+        solve's xref (B,N+1,6) / uref (B,N,2) are given, g_Q / g_R."""
+        if params:
+            return self._vjp_params(iterate, status, grad_x, grad_u, xref, uref)
         N = self.N
         I = _f64(iterate).reshape(-1, self.iterate_len())
         B = I.shape[0]
@@ -643,4 +715,25 @@ class ObcaSolver(_Solver):
         rc = self._L.tt_obca_vjp(self._h, B, _ptr(I), st.ctypes.data_as(_ip), _ptr(gx), _ptr(gu), C.byref(out))
         if rc != 0:
             self._err(rc, "tt_obca_vjp")
+        return r
+
+    def _vjp_params(self, iterate, status, grad_x, grad_u, xref, uref):
+        N, M = self.N, self.M
+        I = _f64(iterate).reshape(-1, self.iterate_len())
+        B = I.shape[0]
+        st = np.ascontiguousarray(np.asarray(status, dtype=np.int32)).reshape(B)
+        gx = None if grad_x is None else _f64(grad_x, (B, N + 1, 6))
+        gu = None if grad_u is None else _f64(grad_u, (B, N, 2))
+        xr = None if xref is None else _f64(xref, (B, N + 1, 6))
+        ur = None if uref is None else _f64(uref, (B, N, 2))
+        r = ObcaVjpParamsResult(g_x0=np.empty((B, 6)), g_xref=np.empty((B, N + 1, 6)), g_uref=np.empty((B, N, 2)),
+                                vjp_status=np.empty(B, dtype=np.int32), g_obstacles=np.empty((B, M, 4)),
+                                g_dmin=np.empty(B), g_Q=None if xr is None else np.empty((B, 6, 6)),
+                                g_R=None if ur is None else np.empty((B, 2, 2)))
+        out = TTObcaVjpParamsOut(*[None if a is None else a.ctypes.data for a in
+                                   (r.g_x0, r.g_xref, r.g_uref, r.vjp_status, r.g_obstacles, r.g_dmin, r.g_Q, r.g_R)])
+        rc = self._L.tt_obca_vjp_params(self._h, B, _ptr(I), st.ctypes.data_as(_ip), _ptr(xr), _ptr(ur), _ptr(gx),
+                                        _ptr(gu), C.byref(out))
+        if rc != 0:
+            self._err(rc, "tt_obca_vjp_params")
         return r

@@ -164,10 +164,28 @@ class ObcaTrackingSolveFunction(torch.autograd.Function):
     """``X, U, status = ObcaTrackingSolveFunction.apply(solver, x0, xref, uref)`` for an ``ObcaSolver`` of
     TT_VARIANT_TRACK_OBCA: x0 (B,6), xref (B,N+1,6), uref (B,N,2) float64 CUDA tensors on the solver's device.  X and U
     are differentiable with respect to all three (tt_obca_vjp_device: first order, the active set fixed); an instance
-    whose solve status is above TT_ACCEPTABLE, or whose adjoint is undefined, contributes a zero gradient."""
+    whose solve status is above TT_ACCEPTABLE, or whose adjoint is undefined, contributes a zero gradient.
+
+    obstacles (float64 (M,4) of (cx, cy, w, h)) and d_min (float64 ()), if given, make the handle's scene an input, on
+    the CPU or on a device (then the forward reads them to the host once).  The forward applies them with
+    ``solver.set_scene`` when they differ from the handle's, and they stay applied; the backward then runs the adjoint
+    kernel's params instantiation (tt_obca_vjp_params_device) and returns the per-instance rows summed over B on each
+    tensor's device.  It raises if the handle's scene was changed between the forward and the backward."""
 
     @staticmethod
-    def forward(ctx, solver, x0, xref, uref):
+    def forward(ctx, solver, x0, xref, uref, obstacles=None, d_min=None):
+        ctx.scene = None
+        if obstacles is not None or d_min is not None:
+            ob, dm = solver.scene()
+            for name, t, shape in (("obstacles", obstacles, (solver.M, 4)), ("d_min", d_min, ())):
+                if t is not None and not (torch.is_tensor(t) and t.dtype == torch.float64 and tuple(t.shape) == shape):
+                    raise TypeError(f"{name} must be a float64 tensor of shape {shape}")
+            new_ob = None if obstacles is None else obstacles.detach().cpu().numpy()
+            new_dm = None if d_min is None else float(d_min.detach().cpu())
+            if (new_ob is not None and not (new_ob == ob).all()) or (new_dm is not None and new_dm != dm):
+                solver.set_scene(new_ob, new_dm)
+            ctx.scene = solver.scene()
+            ctx.like = (None if obstacles is None else obstacles.device, None if d_min is None else d_min.device)
         N, B = solver.N, x0.shape[0]
         x0 = _check("x0", x0, (B, 6))
         xref = _check("xref", xref, (B, N + 1, 6))
@@ -187,9 +205,13 @@ class ObcaTrackingSolveFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_X, grad_U, _grad_status):
-        need = ctx.needs_input_grad  # (solver, x0, xref, uref)
+        need = ctx.needs_input_grad  # (solver, x0, xref, uref[, obstacles, d_min])
+        if ctx.scene is not None:
+            ob, dm = ctx.solver.scene()
+            if not (ob == ctx.scene[0]).all() or dm != ctx.scene[1]:
+                raise RuntimeError("the solver's scene changed since the forward")
         if grad_X is None and grad_U is None:
-            return None, None, None, None
+            return (None,) * len(need)
         iterate, status = ctx.saved_tensors
         B, N, dev = status.shape[0], ctx.solver.N, status.device
         gX = None if grad_X is None else grad_X.to(torch.float64).contiguous()
@@ -198,16 +220,29 @@ class ObcaTrackingSolveFunction(torch.autograd.Function):
         g_x0 = new(B, 6) if need[1] else None
         g_xref = new(B, N + 1, 6) if need[2] else None
         g_uref = new(B, N, 2) if need[3] else None
+        if ctx.scene is not None:
+            g_ob = new(B, ctx.solver.M, 4) if len(need) > 4 and need[4] else None
+            g_dm = new(B) if len(need) > 5 and need[5] else None
+            work = torch.empty((B * ctx.solver.vjp_params_work_bytes() // 8,), dtype=torch.float64, device=dev)
+            ctx.solver.vjp_device(B, iterate.data_ptr(), status.data_ptr(), grad_x=_ptr(gX), grad_u=_ptr(gU),
+                                  g_x0=_ptr(g_x0), g_xref=_ptr(g_xref), g_uref=_ptr(g_uref), g_obstacles=_ptr(g_ob),
+                                  g_dmin=_ptr(g_dm), work=work.data_ptr(),
+                                  stream=torch.cuda.current_stream(dev).cuda_stream)
+            return (None, g_x0, g_xref, g_uref, None if g_ob is None else _batch_sum(g_ob, ctx.like[0]),
+                    None if g_dm is None else _batch_sum(g_dm, ctx.like[1]))[:len(need)]
         ctx.solver.vjp_device(B, iterate.data_ptr(), status.data_ptr(), grad_x=_ptr(gX), grad_u=_ptr(gU),
                               g_x0=_ptr(g_x0), g_xref=_ptr(g_xref), g_uref=_ptr(g_uref),
                               stream=torch.cuda.current_stream(dev).cuda_stream)
-        return None, g_x0, g_xref, g_uref
+        return (None, g_x0, g_xref, g_uref, None, None)[:len(need)]
 
 
 class DifferentiableObcaTracking:
-    """``X, U, status = layer(x0, xref, uref)`` with float64 CUDA tensors: a thin callable over
-    ``ObcaTrackingSolveFunction`` for one ``ObcaSolver`` of TT_VARIANT_TRACK_OBCA.  The forward uses the handle's solver
-    workspace (one stream per handle); the backward uses no buffer of the handle.  Failed instances give zeros."""
+    """``X, U, status = layer(x0, xref, uref, obstacles=None, d_min=None)`` with float64 CUDA tensors: a thin callable
+    over ``ObcaTrackingSolveFunction`` for one ``ObcaSolver`` of TT_VARIANT_TRACK_OBCA.  The forward uses the handle's
+    solver workspace (one stream per handle); the backward uses no buffer of the handle.  Failed instances give zeros.
+    With ``obstacles`` (float64 (M,4)) and / or ``d_min`` (float64 ()), CPU or device, the handle's scene is an input
+    too: ``obstacles.grad`` and ``d_min.grad`` are the batch sums of tt_obca_vjp_params_device's rows.  Q and R are not
+    inputs (there is no setter for them); ``ObcaSolver.vjp(..., params=True)`` returns their gradients."""
 
     def __init__(self, solver):
         from ._lib import TT_VARIANT_TRACK_OBCA
@@ -215,8 +250,8 @@ class DifferentiableObcaTracking:
             raise TypeError("DifferentiableObcaTracking needs an ObcaSolver of TT_VARIANT_TRACK_OBCA")
         self.solver = solver
 
-    def __call__(self, x0, xref, uref):
-        return ObcaTrackingSolveFunction.apply(self.solver, x0, xref, uref)
+    def __call__(self, x0, xref, uref, obstacles=None, d_min=None):
+        return ObcaTrackingSolveFunction.apply(self.solver, x0, xref, uref, obstacles, d_min)
 
 
 class ClosedLoopFunction(torch.autograd.Function):

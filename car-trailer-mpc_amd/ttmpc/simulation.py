@@ -791,7 +791,7 @@ class ClosedLoop:
         torch.cuda.synchronize(self.dev)
         return dict(self._policy_logs(), **tape.result(), tape=tape)
 
-    def backward(self, tape, GS, GU, model=False, rule=False):
+    def backward(self, tape, GS, GU, model=False, rule=False, scene=False):
         """The adjoint of a taped run for a scalar loss L(S, Ua): GS = dL/dS (K+1,B,6), GU = dL/dUa (K,B,2), float64
         device tensors.  Per step, backwards: tt_policy_plant_vjp_device, the step's window again,
         tt_track_vjp_device on the taped solve, tt_sim_window_vjp_device (include/ttmpc.h, "Reverse mode of the closed
@@ -814,8 +814,16 @@ class ClosedLoop:
         tt_obca_vjp_device then runs on the taped iterates of the compacted set with the gathered dL/dU, and its g_x0,
         g_xref, g_uref take those rows before the window adjoint.  The compaction sizes are the tape's: no host
         synchronisation.  model=True and rule=True raise on such a loop (the OBCA adjoint has no geometry or rule
-        gradient)."""
+        gradient).
+        scene=True (a switch loop with ``switch_adjoint=True`` only, else it raises) adds g_obstacles (B,M,4) and g_dmin
+        (B,): dL/d(cx, cy, w, h) and dL/dd_min of the switch solver's scene per instance, accumulated over the switched
+        instance-steps from the same compacted adjoint call, which is then tt_obca_vjp_params_device (its g_x0, g_xref,
+        g_uref agree with the plain call's to rounding).  The switch solver's scene must still be the run's.  The
+        collision switch itself is piecewise constant in the scene and contributes nothing: the gradient holds while no
+        flag changes.  No host synchronisation is added."""
         self._check_differentiable()
+        if scene and (self.switch is None or not self.switch_adjoint):
+            raise ValueError("scene=True needs a switch loop: ClosedLoop(..., switch_solver=..., switch_adjoint=True)")
         if self.switch is not None and (model or rule):
             raise ValueError("a switch (OBCA) loop has no model=True or rule=True gradient: the OBCA adjoint "
                              "(switch_adjoint) gives dL/d(x_init, xref, uref) only")
@@ -844,6 +852,8 @@ class ClosedLoop:
         fz = tape.rule is not None
         g_th = z(B, 7) if rule else None
         x_meas = z(B, 6) if fz else None
+        g_ob, g_dm = (z(B, self.switch.M, 4), z(B)) if scene else (None, None)
+        wbytes = self.switch.vjp_params_work_bytes() if scene else 0
         rs = _rule_ref(tape.rule)
         in_plant = self.noise_in_plant and tape.noise is not None
         meas = self.measurement_noise and tape.noise is not None
@@ -901,9 +911,19 @@ class ClosedLoop:
                 with torch.cuda.stream(s):
                     gu_c = gU[idx].contiguous()
                     o0, oxr, our = z(n, 6), z(n, N + 1, 6), z(n, N, 2)
-                    self.switch.vjp_device(n, it_c.data_ptr(), st_c.data_ptr(), grad_u=gu_c.data_ptr(),
-                                           g_x0=o0.data_ptr(), g_xref=oxr.data_ptr(), g_uref=our.data_ptr(),
-                                           stream=s.cuda_stream)
+                    if scene:  # (idx has no repeats: the indexed += is one add per row)
+                        oob, odm = z(n, self.switch.M, 4), z(n)
+                        work = torch.empty((n * wbytes // 8,), dtype=torch.float64, device=d)
+                        self.switch.vjp_device(n, it_c.data_ptr(), st_c.data_ptr(), grad_u=gu_c.data_ptr(),
+                                               g_x0=o0.data_ptr(), g_xref=oxr.data_ptr(), g_uref=our.data_ptr(),
+                                               g_obstacles=oob.data_ptr(), g_dmin=odm.data_ptr(), work=work.data_ptr(),
+                                               stream=s.cuda_stream)
+                        g_ob[idx] += oob
+                        g_dm[idx] += odm
+                    else:
+                        self.switch.vjp_device(n, it_c.data_ptr(), st_c.data_ptr(), grad_u=gu_c.data_ptr(),
+                                               g_x0=o0.data_ptr(), g_xref=oxr.data_ptr(), g_uref=our.data_ptr(),
+                                               stream=s.cuda_stream)
                     g_x0[idx], g_xr[idx], g_ur[idx] = o0, oxr, our
             _check(win_vjp(B, N, int(tape.ks[t]), int(Np), g_xr.data_ptr(), g_ur.data_ptr(), g_px.data_ptr(),
                            g_pu.data_ptr(), g_x0.data_ptr(), GS[t].data_ptr(), a.data_ptr(), g_ws.data_ptr(),
@@ -917,6 +937,8 @@ class ClosedLoop:
             out.update(g_model_solver=g_ms, g_model_plant=g_mp)
         if rule:
             out["g_fuzzy_rule"] = g_th
+        if scene:
+            out.update(g_obstacles=g_ob, g_dmin=g_dm)
         return out
 
     def _policy_logs(self):

@@ -294,7 +294,8 @@ int tt_obca_solve_batch_iterate_device(void* handle, int B, const double* d_x0, 
  *   First order only, the active set fixed: an obstacle row that is active stays active, one that is not stays out,
  *   and a variable sitting on a bound carries (numerically) zero lam.
  *   Only TT_VARIANT_TRACK_OBCA: a plan handle and a tracking handle return -EINVAL.  Gradients with respect to the
- *   obstacles, d_min and the geometry are not formed.  The horizon must keep the instance's record in 64 KB of LDS
+ *   obstacles, d_min, Q and R come from tt_obca_vjp_params* below; those with respect to the geometry (L1, L2, M, W1,
+ *   W2) are not formed.  The horizon must keep the instance's record in 64 KB of LDS
  *   (N <= 76), else -EINVAL.
  *
  * tt_obca_vjp_device: device pointers (inside the host-side struct too), asynchronous on `stream`.  It uses no buffer
@@ -306,6 +307,42 @@ int tt_obca_vjp_device(void* handle, int B, const double* d_iterate, const int* 
                        const double* d_grad_u, const tt_obca_vjp_out* d_out, void* stream);
 int tt_obca_vjp(void* handle, int B, const double* iterate, const int* status, const double* grad_x,
                 const double* grad_u, const tt_obca_vjp_out* out);
+
+/* The same adjoint plus the gradient with respect to the scene and the weights (tt_obca_vjp_params_out; every member
+ * may be NULL; the first four are tt_obca_vjp_out's):
+ *     g_obstacles [B][M][4]  dL/d(cx, cy, w, h) of every obstacle      g_dmin [B]  dL/dd_min
+ *     g_Q [B][6][6], g_R [B][2][2]  gradients in the raw entries given to tt_create (which symmetrises), so
+ *                                   g_Q[a][b] = -sum_k (lam_x,k[a] e_k[b] + lam_x,k[b] e_k[a]), e_k = x_k - xref_k
+ *   With v the 16 entries of lam of one block (stage k >= 1, obstacle m, body), y_d1 and lam the block's iterate values
+ *   and b = (cx + w/2, cy + h/2, -cx + w/2, -cy + h/2) the obstacle's half-space offsets, only row 1 of the block
+ *   (g' mu - (A p - b)' lam + d_min - s_1 = 0) and the stationarity rows of lam depend on b and d_min, linearly:
+ *     g_b[i] = -sum (y_d1 v_lam[i] + lam[i] v_yd1),   g_dmin = -sum v_yd1,
+ *     g_cx = g_b0 - g_b2, g_cy = g_b1 - g_b3, g_w = (g_b0 + g_b2) / 2, g_h = (g_b1 + g_b3) / 2.
+ *   On a face contact g_cx = -g_dmin and g_w = g_dmin / 2: moving the face and widening the margin are one motion.
+ *   The block unknowns are carried across the refinement steps in d_work ([B] x tt_obca_vjp_params_work_bytes(N, M),
+ *   one 128-byte record per block; contents undefined afterwards): recomputing them from the final pose adjoint loses
+ *   three to four digits where a row is active.  The x0 / xref / uref members agree with tt_obca_vjp's to
+ *   rounding, not bitwise.
+ *   xref, uref: as given to the solve; read for g_Q and g_R only (NULL while one of those is wanted: -EINVAL).
+ *   d_work NULL: -EINVAL.  Failed or skipped instances get zeros in every array.  Only TT_VARIANT_TRACK_OBCA, N <= 76.
+ * tt_obca_vjp_params_device uses no buffer of the handle; tt_obca_vjp_params stages through the handle (its work
+ * buffer included), synchronous. */
+typedef struct { double* g_x0; double* g_xref; double* g_uref; int* vjp_status;
+                 double* g_obstacles; double* g_dmin; double* g_Q; double* g_R; } tt_obca_vjp_params_out;
+long long tt_obca_vjp_params_work_bytes(int N, int M);  /* per instance */
+int tt_obca_vjp_params_device(void* handle, int B, const double* d_iterate, const int* d_status, const double* d_xref,
+                              const double* d_uref, const double* d_grad_x, const double* d_grad_u,
+                              const tt_obca_vjp_params_out* d_out, void* d_work, void* stream);
+int tt_obca_vjp_params(void* handle, int B, const double* iterate, const int* status, const double* xref,
+                       const double* uref, const double* grad_x, const double* grad_u,
+                       const tt_obca_vjp_params_out* out);
+
+/* The scene of an OBCA handle (both variants) without rebuilding it: obstacles M x (cx, cy, w, h) (M is fixed at
+ * tt_create; NULL keeps them) and the safety margin d_min (default 0.2; NULL keeps it).  Applies to every later call;
+ * a handle that never calls it solves bitwise as before.  -EINVAL on a tracking handle, on a non-finite value, on
+ * w or h <= 0 and on d_min < 0 (nothing is changed then).  tt_get_scene: either pointer may be NULL. */
+int tt_set_scene(void* handle, const double* obstacles, const double* d_min);
+int tt_get_scene(void* handle, double* obstacles, double* d_min);
 
 /* ---------------------------------------------------------------------------------------------
  * Closed-loop simulation step, device pointers, asynchronous on `stream`.

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
-"""Time the MPC+OBCA adjoint (tt_obca_vjp_device) next to the solve it differentiates, with device events.
+"""Time the MPC+OBCA adjoint (tt_obca_vjp_device) and its params entry (tt_obca_vjp_params_device: the scene and weight
+gradients, the block unknowns carried in HBM) next to the solve they differentiate, with device events.
 
 Two shapes: the drivers' (B = 64, N = 50, M = 11: the golden windows, tiled) and B = 1024 on case A of
-tests/obca_vjp_reference.py (N = 6, M = 1).  Solve and adjoint alternate for several rounds, as tools/time_vjp.py does;
-the line per shape gives the median of each and the adjoint / solve ratio.
+tests/obca_vjp_reference.py (N = 6, M = 1).  Solve, adjoint and params adjoint alternate for several rounds, as
+tools/time_vjp.py does; the line per shape gives the median of each and the ratios adjoint / solve, params / adjoint
+and params / solve.
 
     python tools/time_obca_vjp.py [--rounds 5]
 """
@@ -52,6 +54,9 @@ def main():
         gU = torch.rand(B, N, 2, dtype=torch.float64, device=dev)
         g0, gr, gu = new(B, 6), new(B, N + 1, 6), new(B, N, 2)
         vs = torch.empty(B, dtype=torch.int32, device=dev)
+        vp = torch.empty(B, dtype=torch.int32, device=dev)
+        gob, gdm, gQ, gR = new(B, s.M, 4), new(B), new(B, 6, 6), new(B, 2, 2)
+        work = new(B * s.vjp_params_work_bytes() // 8)
         stream = torch.cuda.current_stream(dev).cuda_stream
 
         def solve():
@@ -61,6 +66,12 @@ def main():
         def adjoint():
             s.vjp_device(B, I.data_ptr(), st.data_ptr(), grad_x=gX.data_ptr(), grad_u=gU.data_ptr(), g_x0=g0.data_ptr(),
                          g_xref=gr.data_ptr(), g_uref=gu.data_ptr(), vjp_status=vs.data_ptr(), stream=stream)
+
+        def params():
+            s.vjp_device(B, I.data_ptr(), st.data_ptr(), grad_x=gX.data_ptr(), grad_u=gU.data_ptr(), g_x0=g0.data_ptr(),
+                         g_xref=gr.data_ptr(), g_uref=gu.data_ptr(), vjp_status=vp.data_ptr(), stream=stream,
+                         xref=dxr.data_ptr(), uref=dur.data_ptr(), g_obstacles=gob.data_ptr(), g_dmin=gdm.data_ptr(),
+                         g_Q=gQ.data_ptr(), g_R=gR.data_ptr(), work=work.data_ptr())
 
         def timed(fn):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -72,15 +83,20 @@ def main():
 
         solve()
         adjoint()
+        params()
         torch.cuda.synchronize(dev)
-        ts, ta = [], []
+        ts, ta, tp = [], [], []
         for _ in range(a.rounds):
             ts.append(timed(solve))
             ta.append(timed(adjoint))
-        ms, ma = float(np.median(ts)), float(np.median(ta))
+            tp.append(timed(params))
+        ms, ma, mp = float(np.median(ts)), float(np.median(ta)), float(np.median(tp))
         print(json.dumps({"shape": name, "solve_ms": round(ms, 3), "adjoint_ms": round(ma, 4),
-                          "adjoint_over_solve": round(ma / ms, 5), "solved": int((st <= 1).sum().item()),
-                          "adjoint_ok": int((vs == 0).sum().item()), "rounds": a.rounds}))
+                          "adjoint_over_solve": round(ma / ms, 5), "params_ms": round(mp, 4),
+                          "params_over_adjoint": round(mp / ma, 4), "params_over_solve": round(mp / ms, 5),
+                          "solved": int((st <= 1).sum().item()), "adjoint_ok": int((vs == 0).sum().item()),
+                          "params_ok": int((vp == 0).sum().item()), "work_mb": round(work.numel() * 8 / 2**20, 2),
+                          "rounds": a.rounds}))
 
 
 if __name__ == "__main__":
