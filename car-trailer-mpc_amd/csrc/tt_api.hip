@@ -767,10 +767,11 @@ int ttx_solve_stamped(void* handle, int B, const double* d_x0, const double* d_x
 }
 #endif
 
-int tt_obca_solve_batch_iterate_device(void* handle, int B, const double* d_x0, const double* d_xgoal,
-                                       const double* d_xref, const double* d_uref, const double* d_z_guess,
-                                       double* d_x_out, double* d_u_out, double* d_z_out, int* d_status, int* d_iters,
-                                       double* d_kkt_res, double* d_iterate_out, void* stream) {
+// both device entries of the OBCA solve: d_obs [B][M][4] / d_dmin [B] are the per-instance scenes (nullptr: the handle's)
+static int obca_solve_device(void* handle, int B, const double* d_x0, const double* d_xgoal, const double* d_xref,
+                             const double* d_uref, const double* d_z_guess, double* d_x_out, double* d_u_out,
+                             double* d_z_out, int* d_status, int* d_iters, double* d_kkt_res, double* d_iterate_out,
+                             const double* d_obs, const double* d_dmin, void* stream) {
     Handle* h = static_cast<Handle*>(handle);
     if (const int rc = prelude(h, B, kHandle | kObcaOnly | kSign | kEmpty | kRange, nullptr, 1 << 24)) return result(rc);
     const bool plan = h->cfg.variant == TT_VARIANT_OBCA_PLAN;
@@ -802,6 +803,8 @@ int tt_obca_solve_batch_iterate_device(void* handle, int B, const double* d_x0, 
     a.tfac = plan ? 100.0 : 1.0;  // trajectory_optimization.py:180 / mpc_control_obs.py:39
     fill_model(a, h);
     memcpy(a.obs, h->obs, sizeof a.obs);
+    a.obs_b = d_obs;
+    a.dmin_b = d_dmin;
     a.x0 = d_x0;
     a.xgoal = d_xgoal;
     a.xref = d_xref;
@@ -834,6 +837,24 @@ int tt_obca_solve_batch_iterate_device(void* handle, int B, const double* d_x0, 
     return 0;
 }
 
+int tt_obca_solve_batch_iterate_device(void* handle, int B, const double* d_x0, const double* d_xgoal,
+                                       const double* d_xref, const double* d_uref, const double* d_z_guess,
+                                       double* d_x_out, double* d_u_out, double* d_z_out, int* d_status, int* d_iters,
+                                       double* d_kkt_res, double* d_iterate_out, void* stream) {
+    return obca_solve_device(handle, B, d_x0, d_xgoal, d_xref, d_uref, d_z_guess, d_x_out, d_u_out, d_z_out, d_status,
+                             d_iters, d_kkt_res, d_iterate_out, nullptr, nullptr, stream);
+}
+
+int tt_obca_solve_batch_scenes_device(void* handle, int B, const double* d_x0, const double* d_xgoal,
+                                      const double* d_xref, const double* d_uref, const double* d_z_guess,
+                                      double* d_x_out, double* d_u_out, double* d_z_out, int* d_status, int* d_iters,
+                                      double* d_kkt_res, double* d_iterate_out, const tt_obca_scenes* d_scenes,
+                                      void* stream) {
+    return obca_solve_device(handle, B, d_x0, d_xgoal, d_xref, d_uref, d_z_guess, d_x_out, d_u_out, d_z_out, d_status,
+                             d_iters, d_kkt_res, d_iterate_out, d_scenes ? d_scenes->obstacles : nullptr,
+                             d_scenes ? d_scenes->d_min : nullptr, stream);
+}
+
 int tt_obca_solve_batch_device(void* handle, int B, const double* d_x0, const double* d_xgoal, const double* d_xref,
                                const double* d_uref, const double* d_z_guess, double* d_x_out, double* d_u_out,
                                double* d_z_out, int* d_status, int* d_iters, double* d_kkt_res, void* stream) {
@@ -841,11 +862,29 @@ int tt_obca_solve_batch_device(void* handle, int B, const double* d_x0, const do
                                               d_z_out, d_status, d_iters, d_kkt_res, nullptr, stream);
 }
 
-int tt_obca_solve_batch_iterate(void* handle, int B, const double* x0, const double* xgoal, const double* xref,
-                                const double* uref, const double* z_guess, double* x_out, double* u_out, double* z_out,
-                                int* status, int* iters, double* kkt_res, double* iterate_out) {
+// tt_set_scene's rule, for B scenes at once (either array may be nullptr)
+static int check_scenes(Handle* h, int B, const double* obstacles, const double* d_min) {
+    const size_t M = h->cfg.M;
+    for (size_t i = 0; obstacles && i < (size_t)B * M; ++i) {
+        const double* o = obstacles + 4 * i;
+        if (!isfinite(o[0]) || !isfinite(o[1]) || !isfinite(o[2]) || !isfinite(o[3]) || !(o[2] > 0) || !(o[3] > 0))
+            return fail(h, -EINVAL, "obstacles must be finite with w, h > 0 (instance %s)", std::to_string(i / M).c_str());
+    }
+    for (int b = 0; d_min && b < B; ++b)
+        if (!isfinite(d_min[b]) || d_min[b] < 0)
+            return fail(h, -EINVAL, "d_min must be finite and >= 0 (instance %s)", std::to_string(b).c_str());
+    return 0;
+}
+
+// both host entries of the OBCA solve (sc nullptr: the handle's scene)
+static int obca_solve_host(void* handle, int B, const double* x0, const double* xgoal, const double* xref,
+                           const double* uref, const double* z_guess, double* x_out, double* u_out, double* z_out,
+                           int* status, int* iters, double* kkt_res, double* iterate_out, const tt_obca_scenes* sc) {
     Handle* h = static_cast<Handle*>(handle);
     if (const int rc = prelude(h, B, kHandle | kObcaOnly | kSign | kEmpty)) return result(rc);
+    const double* obs = sc ? sc->obstacles : nullptr;
+    const double* dmin = sc ? sc->d_min : nullptr;
+    if (const int rc = check_scenes(h, B, obs, dmin)) return rc;  // (nothing staged, nothing launched)
     const bool plan = h->cfg.variant == TT_VARIANT_OBCA_PLAN;
     if (!x0 || !status || (plan && !xgoal) || (!plan && (!xref || !uref)))
         return fail(h, -EINVAL, "NULL host buffer%s");
@@ -854,9 +893,11 @@ int tt_obca_solve_batch_iterate(void* handle, int B, const double* x0, const dou
     const size_t N = h->cfg.N, nz = ttmpc::obca_n(h->cfg.N, h->cfg.M), b = (size_t)B;
     // the launch writes X, U, status, iters and kkt whether or not the caller wants them back
     Stager st;
-    const double *d_x0, *d_xg, *d_xr, *d_ur, *d_zg;
+    const double *d_x0, *d_xg, *d_xr, *d_ur, *d_zg, *d_obs, *d_dmin;
     double *d_xo, *d_uo, *d_zo, *d_kkt, *d_itout;
     int *d_st, *d_it;
+    st.in(obs, b * 4 * h->cfg.M, &d_obs);
+    st.in(dmin, b, &d_dmin);
     st.in(x0, b * 6, &d_x0);
     st.in(plan ? xgoal : nullptr, b * 6, &d_xg);
     st.in(plan ? nullptr : xref, b * (N + 1) * 6, &d_xr);
@@ -873,9 +914,24 @@ int tt_obca_solve_batch_iterate(void* handle, int B, const double* x0, const dou
         return fail(h, -ENOMEM, "device workspace allocation failed for B=%s", std::to_string(B).c_str());
     hipStream_t s = h->stream;
     return st.run(h, s, "OBCA solve", [&] {
-        return tt_obca_solve_batch_iterate_device(h, B, d_x0, d_xg, d_xr, d_ur, d_zg, d_xo, d_uo, d_zo, d_st, d_it, d_kkt,
-                                                  d_itout, s);
+        return obca_solve_device(h, B, d_x0, d_xg, d_xr, d_ur, d_zg, d_xo, d_uo, d_zo, d_st, d_it, d_kkt, d_itout, d_obs,
+                                 d_dmin, s);
     });
+}
+
+int tt_obca_solve_batch_iterate(void* handle, int B, const double* x0, const double* xgoal, const double* xref,
+                                const double* uref, const double* z_guess, double* x_out, double* u_out, double* z_out,
+                                int* status, int* iters, double* kkt_res, double* iterate_out) {
+    return obca_solve_host(handle, B, x0, xgoal, xref, uref, z_guess, x_out, u_out, z_out, status, iters, kkt_res,
+                           iterate_out, nullptr);
+}
+
+int tt_obca_solve_batch_scenes(void* handle, int B, const double* x0, const double* xgoal, const double* xref,
+                               const double* uref, const double* z_guess, double* x_out, double* u_out, double* z_out,
+                               int* status, int* iters, double* kkt_res, double* iterate_out,
+                               const tt_obca_scenes* scenes) {
+    return obca_solve_host(handle, B, x0, xgoal, xref, uref, z_guess, x_out, u_out, z_out, status, iters, kkt_res,
+                           iterate_out, scenes);
 }
 
 int tt_obca_solve_batch(void* handle, int B, const double* x0, const double* xgoal, const double* xref,
@@ -892,8 +948,9 @@ static int obca_vjp_horizon(Handle* h) {
                 std::to_string(ttmpc::obca_vjp_max_horizon()).c_str());
 }
 
-int tt_obca_vjp_device(void* handle, int B, const double* d_iterate, const int* d_status, const double* d_grad_x,
-                       const double* d_grad_u, const tt_obca_vjp_out* d_out, void* stream) {
+// (d_obs [B][M][4]: per-instance obstacles, nullptr: the handle's)
+static int obca_vjp_device(void* handle, int B, const double* d_iterate, const int* d_status, const double* d_grad_x,
+                           const double* d_grad_u, const tt_obca_vjp_out* d_out, const double* d_obs, void* stream) {
     Handle* h = static_cast<Handle*>(handle);
     if (const int rc = prelude(h, B, kHandle | kObcaOnly | kNotPlan | kSign)) return rc;
     if (!d_grad_x && !d_grad_u) return fail(h, -EINVAL, "grad_x and grad_u are both NULL: no loss to differentiate%s");
@@ -908,6 +965,7 @@ int tt_obca_vjp_device(void* handle, int B, const double* d_iterate, const int* 
     a.W2 = h->cfg.W2;
     a.eq_tol = 1e-5;  // trajectory_optimization.py:136-139, as the solve sets it
     memcpy(a.obs, h->obs, sizeof a.obs);
+    a.obs_b = d_obs;
     a.iterate = d_iterate;
     a.gx = d_grad_x;
     a.gu = d_grad_u;
@@ -920,21 +978,28 @@ int tt_obca_vjp_device(void* handle, int B, const double* d_iterate, const int* 
     return 0;
 }
 
-int tt_obca_vjp(void* handle, int B, const double* iterate, const int* status, const double* grad_x,
-                const double* grad_u, const tt_obca_vjp_out* out) {
+int tt_obca_vjp_device(void* handle, int B, const double* d_iterate, const int* d_status, const double* d_grad_x,
+                       const double* d_grad_u, const tt_obca_vjp_out* d_out, void* stream) {
+    return obca_vjp_device(handle, B, d_iterate, d_status, d_grad_x, d_grad_u, d_out, nullptr, stream);
+}
+
+static int obca_vjp_host(void* handle, int B, const double* iterate, const int* status, const double* grad_x,
+                         const double* grad_u, const tt_obca_vjp_out* out, const double* obs) {
     Handle* h = static_cast<Handle*>(handle);
     if (const int rc = prelude(h, B, kHandle | kObcaOnly | kNotPlan | kSign)) return rc;
     if (!grad_x && !grad_u) return fail(h, -EINVAL, "grad_x and grad_u are both NULL: no loss to differentiate%s");
     if (const int rc = obca_vjp_horizon(h)) return rc;   // (before anything is staged)
     if (const int rc = prelude(h, B, kEmpty | kRange)) return result(rc);
     if (!iterate || !status || !out) return fail(h, -EINVAL, "NULL host buffer%s");
+    if (const int rc = check_scenes(h, B, obs, nullptr)) return rc;
     DeviceGuard dg(h->device);
     if (dg.err != hipSuccess) return hip_fail(h, dg.err, "hipSetDevice");
     const size_t N = h->cfg.N, b = (size_t)B, nx = b * (N + 1) * 6, nu = b * N * 2;
     Stager st;
-    const double *d_it, *d_gx, *d_gu;
+    const double *d_it, *d_gx, *d_gu, *d_obs;
     const int* d_st;
     tt_obca_vjp_out dout;
+    st.in(obs, b * 4 * h->cfg.M, &d_obs);
     st.in(iterate, b * ttmpc::obca_iterate_len(h->cfg.N, h->cfg.M), &d_it);
     st.in(grad_x, nx, &d_gx);
     st.in(grad_u, nu, &d_gu);
@@ -946,7 +1011,12 @@ int tt_obca_vjp(void* handle, int B, const double* iterate, const int* status, c
     if (!st.carve(h->xfer)) return no_memory(h, "adjoint staging");
     hipStream_t s = h->stream;
     return st.run(h, s, "OBCA adjoint",
-                  [&] { return tt_obca_vjp_device(handle, B, d_it, d_st, d_gx, d_gu, &dout, s); });
+                  [&] { return obca_vjp_device(handle, B, d_it, d_st, d_gx, d_gu, &dout, d_obs, s); });
+}
+
+int tt_obca_vjp(void* handle, int B, const double* iterate, const int* status, const double* grad_x,
+                const double* grad_u, const tt_obca_vjp_out* out) {
+    return obca_vjp_host(handle, B, iterate, status, grad_x, grad_u, out, nullptr);
 }
 
 // tt_obca_vjp_params*: the checks both entries share, in tt_obca_vjp's order
@@ -964,9 +1034,10 @@ long long tt_obca_vjp_params_work_bytes(int N, int M) {
     return (N < 1 || M < 1) ? -EINVAL : (long long)(8 * ttmpc::obca_vjp_params_work_doubles(N, M));
 }
 
-int tt_obca_vjp_params_device(void* handle, int B, const double* d_iterate, const int* d_status, const double* d_xref,
-                              const double* d_uref, const double* d_grad_x, const double* d_grad_u,
-                              const tt_obca_vjp_params_out* d_out, void* d_work, void* stream) {
+static int obca_vjp_params_device(void* handle, int B, const double* d_iterate, const int* d_status,
+                                  const double* d_xref, const double* d_uref, const double* d_grad_x,
+                                  const double* d_grad_u, const tt_obca_vjp_params_out* d_out, void* d_work,
+                                  const double* d_obs, void* stream) {
     Handle* h = static_cast<Handle*>(handle);
     if (const int rc = obca_vjp_params_checks(h, B, d_grad_x, d_grad_u, d_xref, d_uref, d_out)) return rc;
     if (!d_work) return fail(h, -EINVAL, "NULL work buffer (tt_obca_vjp_params_work_bytes per instance)%s");
@@ -981,6 +1052,7 @@ int tt_obca_vjp_params_device(void* handle, int B, const double* d_iterate, cons
     a.W2 = h->cfg.W2;
     a.eq_tol = 1e-5;  // trajectory_optimization.py:136-139, as the solve sets it
     memcpy(a.obs, h->obs, sizeof a.obs);
+    a.obs_b = d_obs;
     a.iterate = d_iterate;
     a.gx = d_grad_x;
     a.gu = d_grad_u;
@@ -1000,18 +1072,43 @@ int tt_obca_vjp_params_device(void* handle, int B, const double* d_iterate, cons
     return 0;
 }
 
-int tt_obca_vjp_params(void* handle, int B, const double* iterate, const int* status, const double* xref,
-                       const double* uref, const double* grad_x, const double* grad_u,
-                       const tt_obca_vjp_params_out* out) {
+int tt_obca_vjp_params_device(void* handle, int B, const double* d_iterate, const int* d_status, const double* d_xref,
+                              const double* d_uref, const double* d_grad_x, const double* d_grad_u,
+                              const tt_obca_vjp_params_out* d_out, void* d_work, void* stream) {
+    return obca_vjp_params_device(handle, B, d_iterate, d_status, d_xref, d_uref, d_grad_x, d_grad_u, d_out, d_work,
+                                  nullptr, stream);
+}
+
+// tt_obca_vjp_scenes*: no parameter output wanted -> the plain instantiation (no work buffer)
+static bool plain_adjoint(const tt_obca_vjp_params_out* o) { return !o->g_obstacles && !o->g_dmin && !o->g_Q && !o->g_R; }
+
+int tt_obca_vjp_scenes_device(void* handle, int B, const double* d_iterate, const int* d_status, const double* d_xref,
+                              const double* d_uref, const double* d_grad_x, const double* d_grad_u,
+                              const tt_obca_vjp_params_out* d_out, void* d_work, const tt_obca_scenes* d_scenes,
+                              void* stream) {
+    const double* d_obs = d_scenes ? d_scenes->obstacles : nullptr;
+    if (d_out && !d_work && plain_adjoint(d_out)) {
+        const tt_obca_vjp_out o = {d_out->g_x0, d_out->g_xref, d_out->g_uref, d_out->vjp_status};
+        return obca_vjp_device(handle, B, d_iterate, d_status, d_grad_x, d_grad_u, &o, d_obs, stream);
+    }
+    return obca_vjp_params_device(handle, B, d_iterate, d_status, d_xref, d_uref, d_grad_x, d_grad_u, d_out, d_work,
+                                  d_obs, stream);
+}
+
+static int obca_vjp_params_host(void* handle, int B, const double* iterate, const int* status, const double* xref,
+                                const double* uref, const double* grad_x, const double* grad_u,
+                                const tt_obca_vjp_params_out* out, const double* obs) {
     Handle* h = static_cast<Handle*>(handle);
     if (const int rc = obca_vjp_params_checks(h, B, grad_x, grad_u, xref, uref, out)) return rc;  // (nothing staged yet)
     if (const int rc = prelude(h, B, kEmpty | kRange)) return result(rc);
     if (!iterate || !status || !out) return fail(h, -EINVAL, "NULL host buffer%s");
+    if (const int rc = check_scenes(h, B, obs, nullptr)) return rc;
     DeviceGuard dg(h->device);
     if (dg.err != hipSuccess) return hip_fail(h, dg.err, "hipSetDevice");
     const size_t N = h->cfg.N, M = h->cfg.M, b = (size_t)B, nx = b * (N + 1) * 6, nu = b * N * 2;
     Stager st;
-    const double *d_it, *d_gx, *d_gu, *d_xr, *d_ur;
+    const double *d_it, *d_gx, *d_gu, *d_xr, *d_ur, *d_obs;
+    st.in(obs, b * 4 * M, &d_obs);
     const int* d_st;
     double* d_work;
     tt_obca_vjp_params_out dout;
@@ -1033,8 +1130,29 @@ int tt_obca_vjp_params(void* handle, int B, const double* iterate, const int* st
     if (!st.carve(h->xfer)) return no_memory(h, "adjoint staging");
     hipStream_t s = h->stream;
     return st.run(h, s, "OBCA params adjoint", [&] {
-        return tt_obca_vjp_params_device(handle, B, d_it, d_st, d_xr, d_ur, d_gx, d_gu, &dout, d_work, s);
+        return obca_vjp_params_device(handle, B, d_it, d_st, d_xr, d_ur, d_gx, d_gu, &dout, d_work, d_obs, s);
     });
+}
+
+int tt_obca_vjp_params(void* handle, int B, const double* iterate, const int* status, const double* xref,
+                       const double* uref, const double* grad_x, const double* grad_u,
+                       const tt_obca_vjp_params_out* out) {
+    return obca_vjp_params_host(handle, B, iterate, status, xref, uref, grad_x, grad_u, out, nullptr);
+}
+
+int tt_obca_vjp_scenes(void* handle, int B, const double* iterate, const int* status, const double* xref,
+                       const double* uref, const double* grad_x, const double* grad_u,
+                       const tt_obca_vjp_params_out* out, const tt_obca_scenes* scenes) {
+    const double* obs = scenes ? scenes->obstacles : nullptr;
+    Handle* h = static_cast<Handle*>(handle);
+    // (the adjoint does not read d_min, but a scene the solve would have refused is refused here too)
+    if (h && is_obca(h->cfg) && scenes && scenes->d_min)
+        if (const int rc = check_scenes(h, B, nullptr, scenes->d_min)) return rc;
+    if (out && plain_adjoint(out)) {
+        const tt_obca_vjp_out o = {out->g_x0, out->g_xref, out->g_uref, out->vjp_status};
+        return obca_vjp_host(handle, B, iterate, status, grad_x, grad_u, &o, obs);
+    }
+    return obca_vjp_params_host(handle, B, iterate, status, xref, uref, grad_x, grad_u, out, obs);
 }
 
 int tt_set_scene(void* handle, const double* obstacles, const double* d_min) {

@@ -159,6 +159,10 @@ struct ObcaArgs {
     // forces the TT_HANDOFF_TIMEOUT path (tests/test_gpu_obca.py)
     unsigned long long spin_ticks;
     int fail_b;
+    // per-instance scenes (tt_obca_solve_batch_scenes*): row b replaces obs[0..4M) / dmin in the workgroup's LDS copy
+    // of this block; nullptr: the value above for every instance.  Written before the launch, never during it
+    const double* obs_b;            // [B][M][4] or nullptr
+    const double* dmin_b;           // [B] or nullptr
 };
 constexpr int kObcaBoardStride = 16;  // 128-B line per instance (+ one header line)
 // claim word of an instance's board line: epoch << 40 | chunks << 20 | next chunk (20 + 20 bits: a pass of
@@ -197,6 +201,9 @@ struct ObcaVjpArgs : DiffArgs {
     double* g_xref;             // [B][N+1][6] or nullptr
     double* g_uref;             // [B][N][2] or nullptr
     int* vjp_status;            // [B] or nullptr
+    // per-instance scenes (tt_obca_vjp_scenes*): row b replaces obs; nullptr: obs for every b.  (d_min is not an
+    // input of the adjoint: it shifts a residual and is in no coefficient of the system)
+    const double* obs_b;        // [B][M][4] or nullptr
 };
 constexpr int kObcaVjpThreads = 256;  // sixteen 16-lane groups: one OBCA block each per round
 // LDS doubles of one instance: the adjoint's stage record, the dense 4x4 pose addend and the refinement's fields (87

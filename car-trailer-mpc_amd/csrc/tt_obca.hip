@@ -3610,6 +3610,17 @@ __device__ __forceinline__ void do_chunks_helper(const Ctx& c, const LShared& sh
     else update_chunks_body<false, true>(c, p, c0, c1);
 }
 
+// per-instance scenes: overwrite the scene of this workgroup's LDS argument copy with instance b's row (lanes t < 4M
+// and lane 0; the caller's barrier publishes it).  The arrays are written before the launch and never during it, so
+// plain loads are enough: there is nothing to acquire.  Every phase reads the scene through LArgs, so the arithmetic
+// sees the words it would see on a handle created with that scene
+__device__ __forceinline__ void load_scene(LArgs& a, int b) {
+    auto* w = (__attribute__((address_space(3))) ObcaArgs*)&a;  // args_lds itself is not const
+    const int t = (int)threadIdx.x;
+    if (a.obs_b && t < 4 * a.M) w->obs[t] = a.obs_b[(size_t)b * 4 * a.M + t];
+    if (a.dmin_b && t == 0) w->dmin = a.dmin_b[b];
+}
+
 // a helper workgroup: serve open chunks of any instance until every instance has finished
 __device__ __forceinline__ void helper_main(LArgs& a, Ctx& cw, LShared& sh) {
     const int B = a.B, lane = (int)threadIdx.x;
@@ -3685,6 +3696,10 @@ __device__ __forceinline__ void helper_main(LArgs& a, Ctx& cw, LShared& sh) {
             cw.b = b;
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
+        // this workgroup's argument copy holds the scene of the instance it served last (or the launch's): take
+        // instance b's on every claim.  The barrier that ends a chunk (below) orders the previous chunk's reads of the
+        // scene before this overwrite, and the barrier that follows publishes it to the lanes of this chunk
+        load_scene(a, b);
         __syncthreads();
         ChunkPass p;
         p.mu = sh.hp_mu; p.dw = sh.hp_dw; p.tau = sh.hp_tau;
@@ -4553,6 +4568,19 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(1, 1))) void 
         helper_main(a, cs_storage, sh);
         return;
     }
+    // per-instance scenes: this instance's row over the launch's scene, before anything reads a.obs or a.dmin.  The
+    // device entry cannot validate device memory on the host, so the instance checks its own row (tt_set_scene's rule:
+    // finite entries, w, h > 0, d_min finite and >= 0); a failing instance ends below with TT_NONFINITE before its
+    // first iteration -- it opens no pass, so no helper ever serves it -- and counts itself finished like any other
+    bool badscene = false;
+    if (a.obs_b || a.dmin_b) {
+        load_scene(a, c.b);
+        __syncthreads();
+        // (every lane reads the whole row from LDS: uniform, at most 65 broadcast reads, and no reduction to pay for)
+        if (a.obs_b)
+            for (int t = 0; t < 4 * a.M; ++t) badscene |= !isfinite(a.obs[t]) || ((t & 2) && !(a.obs[t] > 0.0));
+        if (a.dmin_b) badscene |= !isfinite(a.dmin) || !(a.dmin >= 0.0);
+    }
     const int st = 8 + 16 * a.M;
     const size_t nz = obca_n(N, a.M);
     const double* zg = a.zg ? a.zg + (size_t)c.b * nz : nullptr;
@@ -4654,7 +4682,9 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(1, 1))) void 
 
     int status = 2, iter = 0;
     double E0 = INFINITY;
-    if (infeasible) {
+    if (badscene) {
+        status = 4;  // TT_NONFINITE: an invalid per-instance scene (outputs: the initial guess, 0 iterations)
+    } else if (infeasible) {
         status = 3;
     } else {
         int nxb = 0, nub = 0;

@@ -458,6 +458,10 @@ __global__ __launch_bounds__(kT) void obca_vjp_kernel(std::conditional_t<kParams
     if (tid == 0) {
 #pragma unroll
         for (int t = 0; t < 4 * kObcaMaxM; ++t) obs[t] = a.obs[t];
+        // per-instance scenes: row b over the launch's scene (the adjoint's system does not hold d_min: it only shifts
+        // the residual of row 1, so a per-instance d_min has nothing to replace here)
+        if (a.obs_b)
+            for (int t = 0; t < 4 * a.M; ++t) obs[t] = a.obs_b[(size_t)b * 4 * a.M + t];
     }
     // ---- stage-parallel pre-pass: the tracking record from the iterate's stage fields, g, a zero addend ----
     for (int k = tid; k <= N; k += kT) {

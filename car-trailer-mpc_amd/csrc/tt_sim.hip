@@ -193,16 +193,19 @@ __device__ bool pose_collides(const double* q, const double* obs, int M, double 
     return false;
 }
 
-// one wave per instance, lanes over the K poses; flag = any pose collides (check_trajectory_collision)
+// one wave per instance, lanes over the K poses; flag = any pose collides (check_trajectory_collision).  obs_stride:
+// doubles between the obstacle lists of two instances (4M: per-instance scenes, tt_collision_scenes_device; 0: one
+// list for the batch)
 __global__ void __launch_bounds__(64) collision_kernel(int B, int K, long long stride_b, int stride_k,
                                                       const double* __restrict__ poses, const double* __restrict__ obs,
-                                                      int M, double L1, double L2, double Mh, double W1, double W2,
+                                                      int obs_stride, int M, double L1, double L2, double Mh, double W1, double W2,
                                                       int* __restrict__ flag) {
     const int b = blockIdx.x, lane = threadIdx.x;
     if (b >= B) return;
     bool hit = false;
     for (int j = lane; j < K; j += 64)
-        hit = hit || pose_collides(poses + b * stride_b + (long long)j * stride_k, obs, M, L1, L2, Mh, W1, W2);
+        hit = hit || pose_collides(poses + b * stride_b + (long long)j * stride_k, obs + (size_t)b * obs_stride, M, L1, L2,
+                                   Mh, W1, W2);
     const unsigned long long any = __ballot(hit);
     if (lane == 0) flag[b] = any != 0ull ? 1 : 0;
 }
@@ -452,7 +455,16 @@ int tt_collision_device(int B, int K, const double* poses, long long stride_b, i
     if (B < 0 || K < 1 || !poses || !p || !flag || M < 0 || (M > 0 && !obstacles) || stride_k < 4) return -EINVAL;
     if (B == 0) return 0;
     hipLaunchKernelGGL(collision_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, B, K, stride_b, stride_k, poses,
-                       obstacles, M, p->L1, p->L2, p->Mh, p->W1, p->W2, flag);
+                       obstacles, 0, M, p->L1, p->L2, p->Mh, p->W1, p->W2, flag);
+    return launched("collision_kernel");
+}
+
+int tt_collision_scenes_device(int B, int K, const double* poses, long long stride_b, int stride_k,
+                               const double* obstacles, int M, const tt_plant* p, int* flag, void* stream) {
+    if (B < 0 || K < 1 || !poses || !p || !flag || M < 0 || (M > 0 && !obstacles) || stride_k < 4) return -EINVAL;
+    if (B == 0) return 0;
+    hipLaunchKernelGGL(collision_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, B, K, stride_b, stride_k, poses,
+                       obstacles, 4 * M, M, p->L1, p->L2, p->Mh, p->W1, p->W2, flag);
     return launched("collision_kernel");
 }
 

@@ -74,6 +74,11 @@ class TTObcaVjpParamsOut(C.Structure):
                                         ("g_R", C.c_void_p)]
 
 
+class TTObcaScenes(C.Structure):
+    """tt_obca_scenes (include/ttmpc.h): per-instance obstacles [B][M][4] and d_min [B]; a NULL member = the handle's."""
+    _fields_ = [("obstacles", C.c_void_p), ("d_min", C.c_void_p)]
+
+
 class TTLqrVjpOut(C.Structure):
     """tt_lqr_vjp_out (include/ttmpc.h): the outputs of tt_lqr_score_vjp_device; NULL members are skipped."""
     _fields_ = [("g_x_cur", C.c_void_p), ("g_x_goal", C.c_void_p), ("g_Q", C.c_void_p), ("g_R", C.c_void_p),
@@ -222,6 +227,18 @@ def lib():
         L.tt_set_scene.restype = C.c_int
         L.tt_get_scene.argtypes = [C.c_void_p, _dp, _dp]
         L.tt_get_scene.restype = C.c_int
+    if not os.environ.get("TTMPC_LIB") or hasattr(L, "tt_obca_solve_batch_scenes"):  # (A/B against a build without them)
+        po, ps = C.POINTER(TTObcaVjpParamsOut), C.POINTER(TTObcaScenes)
+        L.tt_obca_solve_batch_scenes.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip,
+                                                 _dp, _dp, ps]
+        L.tt_obca_solve_batch_scenes.restype = C.c_int
+        L.tt_obca_solve_batch_scenes_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 12 + [ps, C.c_void_p]
+        L.tt_obca_solve_batch_scenes_device.restype = C.c_int
+        L.tt_obca_vjp_scenes.argtypes = [C.c_void_p, C.c_int, _dp, _ip, _dp, _dp, _dp, _dp, po, ps]
+        L.tt_obca_vjp_scenes.restype = C.c_int
+        L.tt_obca_vjp_scenes_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [po, C.c_void_p, ps,
+                                                                                          C.c_void_p]
+        L.tt_obca_vjp_scenes_device.restype = C.c_int
     L.tt_obca_n.argtypes = [C.c_int, C.c_int]
     L.tt_obca_n.restype = C.c_longlong
     L.tt_obca_workspace_bytes.argtypes = [C.c_int, C.c_int]
@@ -239,6 +256,7 @@ def lib():
     vp, i, ll = C.c_void_p, C.c_int, C.c_longlong
     sim = {"tt_sim_window_device": [i, i, i, i, vp, vp, i, vp, vp, vp, vp, vp, vp],
            "tt_collision_device": [i, i, vp, ll, i, vp, i, C.POINTER(TTPlant), vp, vp],
+           "tt_collision_scenes_device": [i, i, vp, ll, i, vp, i, C.POINTER(TTPlant), vp, vp],
            "tt_plant_update_device": [i, C.POINTER(TTPlant), vp, vp, ll, vp, i, vp, vp],
            "tt_warm_start_device": [i, i, vp, vp, vp, vp, i, vp, vp],
            "tt_record_solution_device": [i, i, vp, vp, vp, vp, vp, vp],
@@ -286,7 +304,8 @@ EXPORTED_SYMBOLS = ("tt_create", "tt_solve_batch", "tt_solve_batch_device", "tt_
                     "tt_get_model", "tt_policy_plant_vjp_model_device", "tt_fuzzy_weights_rule_device",
                     "tt_fuzzy_weights_vjp_device", "tt_sim_window_vjp_fuzzy_device", "tt_obca_vjp_device",
                     "tt_obca_vjp", "tt_obca_vjp_params_work_bytes", "tt_obca_vjp_params_device", "tt_obca_vjp_params",
-                    "tt_set_scene", "tt_get_scene")
+                    "tt_set_scene", "tt_get_scene", "tt_obca_solve_batch_scenes", "tt_obca_solve_batch_scenes_device",
+                    "tt_obca_vjp_scenes", "tt_obca_vjp_scenes_device", "tt_collision_scenes_device")
 
 
 def _ptr(a):
@@ -578,13 +597,33 @@ class ObcaSolver(_Solver):
         super().__init__(N, params, params["W1"], params["W2"], Q, R, xlb, xub, ulb, uub, ob, variant, tol, acc_tol,
                          max_iter, acc_iter, dual_init, device)
 
-    def solve(self, x0, x_goal=None, xref=None, uref=None, z_guess=None, iterate=False):
+    def _scenes(self, B, obstacles, d_min):
+        """The host arrays of per-instance scenes, checked: obstacles (B,M,4)|None, d_min (B,) or a scalar|None ->
+        (obstacles, d_min, TTObcaScenes).  ValueError on a wrong shape or a wrong M, before any call into the library."""
+        ob = dm = None
+        if obstacles is not None:
+            ob = _f64(obstacles)
+            if ob.shape != (B, self.M, 4):
+                raise ValueError(f"per-instance obstacles must have shape (B, M, 4) = {(B, self.M, 4)}, got {ob.shape}")
+        if d_min is not None:
+            dm = np.full(B, float(d_min)) if np.ndim(d_min) == 0 else _f64(d_min)
+            if dm.shape != (B,):
+                raise ValueError(f"per-instance d_min must be a scalar or have shape (B,) = {(B,)}, got {dm.shape}")
+        return ob, dm, TTObcaScenes(None if ob is None else ob.ctypes.data, None if dm is None else dm.ctypes.data)
+
+    def solve(self, x0, x_goal=None, xref=None, uref=None, z_guess=None, iterate=False, obstacles=None, d_min=None):
         """Host arrays -> (X (B,N+1,6), U (B,N,2), z (B,n), status, iters, kkt); with ``iterate=True`` also the final
-        primal-dual iterate (B, tt_obca_iterate_len) of the diagnostic export (include/ttmpc.h) as a 7th element."""
+        primal-dual iterate (B, tt_obca_iterate_len) of the diagnostic export (include/ttmpc.h) as a 7th element.
+
+        obstacles (B,M,4) and d_min (B,) (or a scalar for every instance) give each instance its own scene
+        (tt_obca_solve_batch_scenes); one left None is the handle's.  Row b then solves bitwise as a B = 1 call on a
+        handle whose ``set_scene`` got row b.  TTError (-EINVAL, nothing launched) on a value ``set_scene`` refuses."""
         N, n = self.N, self.n
         x0 = _f64(x0)
         B = x0.shape[0] if x0.ndim == 2 else 1
         x0 = x0.reshape(B, 6)
+        if obstacles is not None or d_min is not None:
+            ob, dm, sc = self._scenes(B, obstacles, d_min)
         xg = None if x_goal is None else _f64(x_goal, (B, 6))
         xr = None if xref is None else _f64(xref, (B, N + 1, 6))
         ur = None if uref is None else _f64(uref, (B, N, 2))
@@ -595,6 +634,15 @@ class ObcaSolver(_Solver):
         st = np.empty(B, dtype=np.int32)
         it = np.empty(B, dtype=np.int32)
         kk = np.empty(B)
+        if obstacles is not None or d_min is not None:
+            I = np.empty((B, self.iterate_len())) if iterate else None
+            rc = self._L.tt_obca_solve_batch_scenes(self._h, B, _ptr(x0), _ptr(xg), _ptr(xr), _ptr(ur), _ptr(zg),
+                                                    _ptr(X), _ptr(U), _ptr(Z), st.ctypes.data_as(_ip),
+                                                    it.ctypes.data_as(_ip), _ptr(kk), _ptr(I), C.byref(sc))
+            if rc != 0:
+                self._err(rc, "tt_obca_solve_batch_scenes")
+            _warn_handoff(st)
+            return (X, U, Z, st, it, kk, I) if iterate else (X, U, Z, st, it, kk)
         if iterate:
             I = np.empty((B, int(self._L.tt_obca_iterate_len(N, self.M))))
             rc = self._L.tt_obca_solve_batch_iterate(self._h, B, _ptr(x0), _ptr(xg), _ptr(xr), _ptr(ur), _ptr(zg),
@@ -625,10 +673,20 @@ class ObcaSolver(_Solver):
             self._err(rc, "ttx_obca_set_handoff_debug")
 
     def solve_device(self, B, x0, x_goal, xref, uref, z_guess, x_out, u_out, z_out, status, iters=0, kkt=0, stream=0,
-                     iterate=0):
+                     iterate=0, obstacles=0, d_min=0):
         """Device pointers (ints), enqueued on ``stream``.  iterate: (B, tt_obca_iterate_len) for the final primal-dual
         iterate, the device twin of ``solve(iterate=True)`` (0 = not wanted); the other outputs are bitwise the same
-        with or without it."""
+        with or without it.  obstacles (B,M,4) / d_min (B,): per-instance scenes (tt_obca_solve_batch_scenes_device;
+        0 = the handle's); an instance whose scene ``set_scene`` would refuse ends TT_NONFINITE with 0 iterations."""
+        if obstacles or d_min:
+            sc = TTObcaScenes(obstacles or None, d_min or None)
+            rc = self._L.tt_obca_solve_batch_scenes_device(self._h, int(B), x0, x_goal or None, xref or None,
+                                                           uref or None, z_guess or None, x_out, u_out, z_out or None,
+                                                           status, iters or None, kkt or None, iterate or None,
+                                                           C.byref(sc), stream or None)
+            if rc != 0:
+                self._err(rc, "tt_obca_solve_batch_scenes_device")
+            return
         if iterate:
             rc = self._L.tt_obca_solve_batch_iterate_device(self._h, int(B), x0, x_goal or None, xref or None,
                                                             uref or None, z_guess or None, x_out, u_out, z_out or None,
@@ -670,7 +728,7 @@ class ObcaSolver(_Solver):
         return int(self._L.tt_obca_vjp_params_work_bytes(self.N, self.M))
 
     def vjp_device(self, B, iterate, status, grad_x=0, grad_u=0, g_x0=0, g_xref=0, g_uref=0, vjp_status=0, stream=0,
-                   xref=0, uref=0, g_obstacles=0, g_dmin=0, g_Q=0, g_R=0, work=0):
+                   xref=0, uref=0, g_obstacles=0, g_dmin=0, g_Q=0, g_R=0, work=0, obstacles=0, d_min=0):
         """tt_obca_vjp_device (TT_VARIANT_TRACK_OBCA): the adjoint kernel on the device iterate and status of an earlier
         ``solve_device(..., iterate=ptr)`` and the upstream gradients grad_x = dL/dX, grad_u = dL/dU (0 = zeros, not
         both).  Outputs (0 = not wanted): g_x0, g_xref, g_uref, vjp_status.  Uses no buffer of the handle: any stream
@@ -678,7 +736,20 @@ class ObcaSolver(_Solver):
 
         With ``work`` (B * vjp_params_work_bytes() bytes) or one of g_obstacles (B,M,4), g_dmin (B,), g_Q (B,6,6),
         g_R (B,2,2) the call is tt_obca_vjp_params_device: the same adjoint with the block unknowns carried, plus the
-        scene and weight gradients; xref / uref are the solve's (needed for g_Q / g_R only)."""
+        scene and weight gradients; xref / uref are the solve's (needed for g_Q / g_R only).
+
+        obstacles (B,M,4) / d_min (B,): the per-instance scenes the solve was given (tt_obca_vjp_scenes_device, which
+        picks the kernel by the same rule); g_obstacles and g_dmin are then the gradients in each instance's own scene."""
+        if obstacles or d_min:
+            pout = TTObcaVjpParamsOut(g_x0 or None, g_xref or None, g_uref or None, vjp_status or None,
+                                      g_obstacles or None, g_dmin or None, g_Q or None, g_R or None)
+            sc = TTObcaScenes(obstacles or None, d_min or None)
+            rc = self._L.tt_obca_vjp_scenes_device(self._h, int(B), iterate or None, status or None, xref or None,
+                                                   uref or None, grad_x or None, grad_u or None, C.byref(pout),
+                                                   work or None, C.byref(sc), stream or None)
+            if rc != 0:
+                self._err(rc, "tt_obca_vjp_scenes_device")
+            return
         if work or g_obstacles or g_dmin or g_Q or g_R:
             pout = TTObcaVjpParamsOut(g_x0 or None, g_xref or None, g_uref or None, vjp_status or None,
                                       g_obstacles or None, g_dmin or None, g_Q or None, g_R or None)
@@ -694,33 +765,48 @@ class ObcaSolver(_Solver):
         if rc != 0:
             self._err(rc, "tt_obca_vjp_device")
 
-    def vjp(self, iterate, status, grad_x, grad_u, xref=None, uref=None, params=False):
+    def vjp(self, iterate, status, grad_x, grad_u, xref=None, uref=None, params=False, obstacles=None, d_min=None):
         """Host arrays: the gradient of a scalar loss L(X, U) with respect to x_init, xref and uref of the MPC+OBCA
         solve that returned iterate (B, tt_obca_iterate_len) and status (B,); grad_x (B,N+1,6) = dL/dX and grad_u (B,N,2) =
         dL/dU (either may be None for zeros).  Returns a ``TrackVjpResult`` (g_wq_wr and g_model are None).
 
         ``params=True``: tt_obca_vjp_params, an ``ObcaVjpParamsResult`` with g_obstacles and g_dmin and, where the
-        solve's xref (B,N+1,6) / uref (B,N,2) are given, g_Q / g_R."""
+        solve's xref (B,N+1,6) / uref (B,N,2) are given, g_Q / g_R.
+
+        obstacles (B,M,4) / d_min (B,) or a scalar: the per-instance scenes the solve was given (tt_obca_vjp_scenes);
+        g_obstacles and g_dmin are then per instance in its own scene."""
         if params:
-            return self._vjp_params(iterate, status, grad_x, grad_u, xref, uref)
+            return self._vjp_params(iterate, status, grad_x, grad_u, xref, uref, obstacles, d_min)
         N = self.N
         I = _f64(iterate).reshape(-1, self.iterate_len())
         B = I.shape[0]
+        if obstacles is not None or d_min is not None:
+            ob, dm, sc = self._scenes(B, obstacles, d_min)
         st = np.ascontiguousarray(np.asarray(status, dtype=np.int32)).reshape(B)
         gx = None if grad_x is None else _f64(grad_x, (B, N + 1, 6))
         gu = None if grad_u is None else _f64(grad_u, (B, N, 2))
         r = TrackVjpResult(g_x0=np.empty((B, 6)), g_xref=np.empty((B, N + 1, 6)), g_uref=np.empty((B, N, 2)),
                            vjp_status=np.empty(B, dtype=np.int32))
         out = TTObcaVjpOut(r.g_x0.ctypes.data, r.g_xref.ctypes.data, r.g_uref.ctypes.data, r.vjp_status.ctypes.data)
+        if obstacles is not None or d_min is not None:
+            pout = TTObcaVjpParamsOut(r.g_x0.ctypes.data, r.g_xref.ctypes.data, r.g_uref.ctypes.data,
+                                      r.vjp_status.ctypes.data, None, None, None, None)
+            rc = self._L.tt_obca_vjp_scenes(self._h, B, _ptr(I), st.ctypes.data_as(_ip), None, None, _ptr(gx), _ptr(gu),
+                                            C.byref(pout), C.byref(sc))
+            if rc != 0:
+                self._err(rc, "tt_obca_vjp_scenes")
+            return r
         rc = self._L.tt_obca_vjp(self._h, B, _ptr(I), st.ctypes.data_as(_ip), _ptr(gx), _ptr(gu), C.byref(out))
         if rc != 0:
             self._err(rc, "tt_obca_vjp")
         return r
 
-    def _vjp_params(self, iterate, status, grad_x, grad_u, xref, uref):
+    def _vjp_params(self, iterate, status, grad_x, grad_u, xref, uref, obstacles=None, d_min=None):
         N, M = self.N, self.M
         I = _f64(iterate).reshape(-1, self.iterate_len())
         B = I.shape[0]
+        if obstacles is not None or d_min is not None:
+            ob, dm, sc = self._scenes(B, obstacles, d_min)
         st = np.ascontiguousarray(np.asarray(status, dtype=np.int32)).reshape(B)
         gx = None if grad_x is None else _f64(grad_x, (B, N + 1, 6))
         gu = None if grad_u is None else _f64(grad_u, (B, N, 2))
@@ -732,6 +818,12 @@ class ObcaSolver(_Solver):
                                 g_R=None if ur is None else np.empty((B, 2, 2)))
         out = TTObcaVjpParamsOut(*[None if a is None else a.ctypes.data for a in
                                    (r.g_x0, r.g_xref, r.g_uref, r.vjp_status, r.g_obstacles, r.g_dmin, r.g_Q, r.g_R)])
+        if obstacles is not None or d_min is not None:
+            rc = self._L.tt_obca_vjp_scenes(self._h, B, _ptr(I), st.ctypes.data_as(_ip), _ptr(xr), _ptr(ur), _ptr(gx),
+                                            _ptr(gu), C.byref(out), C.byref(sc))
+            if rc != 0:
+                self._err(rc, "tt_obca_vjp_scenes")
+            return r
         rc = self._L.tt_obca_vjp_params(self._h, B, _ptr(I), st.ctypes.data_as(_ip), _ptr(xr), _ptr(ur), _ptr(gx),
                                         _ptr(gu), C.byref(out))
         if rc != 0:

@@ -170,12 +170,26 @@ class ObcaTrackingSolveFunction(torch.autograd.Function):
     the CPU or on a device (then the forward reads them to the host once).  The forward applies them with
     ``solver.set_scene`` when they differ from the handle's, and they stay applied; the backward then runs the adjoint
     kernel's params instantiation (tt_obca_vjp_params_device) and returns the per-instance rows summed over B on each
-    tensor's device.  It raises if the handle's scene was changed between the forward and the backward."""
+    tensor's device.  It raises if the handle's scene was changed between the forward and the backward.
+
+    obstacles of shape (B,M,4) and / or d_min of shape (B,) select the per-instance path instead: every instance solves
+    against its own row (tt_obca_solve_batch_scenes_device; one left None is the handle's for every instance), the
+    handle's scene is left alone, and the backward (tt_obca_vjp_scenes_device) returns the rows as they are, (B,M,4)
+    and (B,), each instance's gradient in its own scene.  The two forms do not mix in one call."""
 
     @staticmethod
     def forward(ctx, solver, x0, xref, uref, obstacles=None, d_min=None):
         ctx.scene = None
-        if obstacles is not None or d_min is not None:
+        ctx.rows = (torch.is_tensor(obstacles) and obstacles.dim() == 3) or (torch.is_tensor(d_min) and d_min.dim() == 1)
+        if ctx.rows:
+            B, dev = x0.shape[0], x0.device
+            for name, t, shape in (("obstacles", obstacles, (B, solver.M, 4)), ("d_min", d_min, (B,))):
+                if t is not None and not (torch.is_tensor(t) and t.dtype == torch.float64 and tuple(t.shape) == shape):
+                    raise TypeError(f"per-instance {name} must be a float64 tensor of shape {shape}")
+            ctx.scene = solver.scene()  # (a member left None is the handle's)
+            ctx.like = (None if obstacles is None else obstacles.device, None if d_min is None else d_min.device)
+            scenes = tuple(None if t is None else t.detach().to(dev).contiguous() for t in (obstacles, d_min))
+        elif obstacles is not None or d_min is not None:
             ob, dm = solver.scene()
             for name, t, shape in (("obstacles", obstacles, (solver.M, 4)), ("d_min", d_min, ())):
                 if t is not None and not (torch.is_tensor(t) and t.dtype == torch.float64 and tuple(t.shape) == shape):
@@ -195,9 +209,15 @@ class ObcaTrackingSolveFunction(torch.autograd.Function):
         U = torch.empty((B, N, 2), dtype=torch.float64, device=dev)
         iterate = torch.empty((B, solver.iterate_len()), dtype=torch.float64, device=dev)
         status = torch.empty((B,), dtype=torch.int32, device=dev)
-        solver.solve_device(B, x0.data_ptr(), 0, xref.data_ptr(), uref.data_ptr(), 0, X.data_ptr(), U.data_ptr(), 0,
-                            status.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream,
-                            iterate=iterate.data_ptr())
+        if ctx.rows:
+            solver.solve_device(B, x0.data_ptr(), 0, xref.data_ptr(), uref.data_ptr(), 0, X.data_ptr(), U.data_ptr(), 0,
+                                status.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream,
+                                iterate=iterate.data_ptr(), obstacles=_ptr(scenes[0]), d_min=_ptr(scenes[1]))
+            ctx.scenes = scenes
+        else:
+            solver.solve_device(B, x0.data_ptr(), 0, xref.data_ptr(), uref.data_ptr(), 0, X.data_ptr(), U.data_ptr(), 0,
+                                status.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream,
+                                iterate=iterate.data_ptr())
         ctx.solver = solver
         ctx.save_for_backward(iterate, status)
         ctx.mark_non_differentiable(status)
@@ -224,10 +244,14 @@ class ObcaTrackingSolveFunction(torch.autograd.Function):
             g_ob = new(B, ctx.solver.M, 4) if len(need) > 4 and need[4] else None
             g_dm = new(B) if len(need) > 5 and need[5] else None
             work = torch.empty((B * ctx.solver.vjp_params_work_bytes() // 8,), dtype=torch.float64, device=dev)
+            rows = dict(obstacles=_ptr(ctx.scenes[0]), d_min=_ptr(ctx.scenes[1])) if ctx.rows else {}
             ctx.solver.vjp_device(B, iterate.data_ptr(), status.data_ptr(), grad_x=_ptr(gX), grad_u=_ptr(gU),
                                   g_x0=_ptr(g_x0), g_xref=_ptr(g_xref), g_uref=_ptr(g_uref), g_obstacles=_ptr(g_ob),
                                   g_dmin=_ptr(g_dm), work=work.data_ptr(),
-                                  stream=torch.cuda.current_stream(dev).cuda_stream)
+                                  stream=torch.cuda.current_stream(dev).cuda_stream, **rows)
+            if ctx.rows:  # each instance's gradient in its own scene: nothing to sum
+                return (None, g_x0, g_xref, g_uref, None if g_ob is None else g_ob.to(ctx.like[0]),
+                        None if g_dm is None else g_dm.to(ctx.like[1]))[:len(need)]
             return (None, g_x0, g_xref, g_uref, None if g_ob is None else _batch_sum(g_ob, ctx.like[0]),
                     None if g_dm is None else _batch_sum(g_dm, ctx.like[1]))[:len(need)]
         ctx.solver.vjp_device(B, iterate.data_ptr(), status.data_ptr(), grad_x=_ptr(gX), grad_u=_ptr(gU),
@@ -241,7 +265,9 @@ class DifferentiableObcaTracking:
     over ``ObcaTrackingSolveFunction`` for one ``ObcaSolver`` of TT_VARIANT_TRACK_OBCA.  The forward uses the handle's
     solver workspace (one stream per handle); the backward uses no buffer of the handle.  Failed instances give zeros.
     With ``obstacles`` (float64 (M,4)) and / or ``d_min`` (float64 ()), CPU or device, the handle's scene is an input
-    too: ``obstacles.grad`` and ``d_min.grad`` are the batch sums of tt_obca_vjp_params_device's rows.  Q and R are not
+    too: ``obstacles.grad`` and ``d_min.grad`` are the batch sums of tt_obca_vjp_params_device's rows.  With
+    ``obstacles`` of shape (B,M,4) and / or ``d_min`` of shape (B,) every instance has its own scene and ``.grad`` has
+    those shapes: row b is instance b's gradient in its own scene (tt_obca_vjp_scenes_device).  Q and R are not
     inputs (there is no setter for them); ``ObcaSolver.vjp(..., params=True)`` returns their gradients."""
 
     def __init__(self, solver):

@@ -48,14 +48,17 @@ class MPCTrackingControlObs(TrajectoryPlanning):
             print("Cannot find a solution!")
         return X[0], U[0]
 
-    def solve_batch(self, initial_states, reference_states, reference_inputs):
-        """(B,6), (B,6,N+1), (B,2,N) -> (B,6,N+1), (B,2,N), status (B,)."""
+    def solve_batch(self, initial_states, reference_states, reference_inputs, obstacle_lists=None):
+        """(B,6), (B,6,N+1), (B,2,N) -> (B,6,N+1), (B,2,N), status (B,).  obstacle_lists: a length-B list of obstacle
+        lists in the constructor's format, one scene per instance (each as long as the constructor's list), or None for
+        the constructor's list."""
         x0, xr, ur = self._batch_inputs(initial_states, reference_states, reference_inputs)
+        scenes = scenarios.scene_rows(obstacle_lists, x0.shape[0], len(self.obstacle_list))
         if self._obstacles is None:
             X, U, st, it, _ = self._solver.solve(x0, xr, ur)
             Z = None
         else:
-            X, U, Z, st, it, _ = self._solver.solve(x0, xref=xr, uref=ur)
+            X, U, Z, st, it, _ = self._solver.solve(x0, xref=xr, uref=ur, obstacles=scenes)
         self._last_solution = Z if Z is not None else None
         self.last_status, self.last_iters = st, it
         return X.transpose(0, 2, 1).copy(), U.transpose(0, 2, 1).copy(), st

@@ -169,6 +169,20 @@ def obstacles_array(obstacle_list):
                     dtype=np.float64).reshape(-1, 4)
 
 
+def scene_rows(obstacle_lists, B, M):
+    """A length-B list of obstacle lists (each of M obstacles, obstacles_array's format) -> (B,M,4) float64, the
+    per-instance scenes of a batched OBCA call; None -> None.  ValueError on another B or another M."""
+    if obstacle_lists is None:
+        return None
+    if len(obstacle_lists) != B:
+        raise ValueError(f"obstacle_lists must hold one obstacle list per instance: B = {B}, got {len(obstacle_lists)}")
+    for b, lst in enumerate(obstacle_lists):
+        if len(lst) != M or M == 0:
+            raise ValueError(f"obstacle_lists[{b}] has {len(lst)} obstacles: every list must have the constructor's "
+                             f"M = {M} (and M > 0); pad a shorter one with far-away obstacles")
+    return np.stack([obstacles_array(lst) for lst in obstacle_lists])
+
+
 def interpolate_waypoints(waypoints, num_output_nodes):
     """interpolate_waypoints.py:5-26: scipy CubicSpline over linspace(0,1,W) sampled at
     linspace(0,1,num_output_nodes).  Returns the array (the reference wraps it in a 1-list)."""

@@ -128,15 +128,25 @@ def window(plan_x, plan_u, k, N, state=None, noise=None, x_meas=None, xref=None,
 
 def collision_flags(poses, obstacles, params, flag=None, stream=None):
     """check_trajectory_collision (simulation.py:363-385) per instance: poses (B,K,>=4) device tensor with
-    contiguous rows; obstacles (M,4) device tensor.  -> int32 flag (B,)."""
+    contiguous rows; obstacles (M,4) device tensor, or (B,M,4) for per-instance scenes (tt_collision_scenes_device:
+    instance b against obstacles[b]).  -> int32 flag (B,)."""
     dev = poses.device
     B, K, w = poses.shape
     flag = torch.empty(B, dtype=torch.int32, device=dev) if flag is None else flag
     p = plant(params)
-    M = 0 if obstacles is None else int(obstacles.shape[0])
     if poses.stride(-1) != 1:
         raise ValueError("pose rows must be contiguous")
     sk = poses.stride(1) if K > 1 else w          # a size-1 dim may carry any stride (numpy gives 0)
+    if obstacles is not None and obstacles.dim() == 3:
+        if obstacles.shape[0] != B or obstacles.shape[2] != 4 or not obstacles.is_contiguous():
+            raise ValueError(f"per-instance obstacles must be a contiguous (B, M, 4) = ({B}, M, 4) tensor, got "
+                             f"{tuple(obstacles.shape)}")
+        M = int(obstacles.shape[1])
+        _check(lib().tt_collision_scenes_device(B, K, poses.data_ptr(), poses.stride(0), sk,
+                                                None if M == 0 else obstacles.data_ptr(), M, C.byref(p),
+                                                flag.data_ptr(), _stream(stream, dev)), "tt_collision_scenes_device")
+        return flag
+    M = 0 if obstacles is None else int(obstacles.shape[0])
     _check(lib().tt_collision_device(B, K, poses.data_ptr(), poses.stride(0), sk,
                                      None if M == 0 else obstacles.data_ptr(), M, C.byref(p), flag.data_ptr(),
                                      _stream(stream, dev)), "tt_collision_device")
@@ -390,12 +400,18 @@ class ClosedLoop:
 
     switch_adjoint=True makes a loop with a switch_solver differentiable (``run_tape`` / ``backward``): the switch step
     then exports the MPC+OBCA solve's iterate, and the backward runs tt_obca_vjp_device on the switched instances.  The
-    default keeps such a loop refusing ``run_tape``."""
+    default keeps such a loop refusing ``run_tape``.
+
+    obstacles of shape (B,M,4) give every loop its own scene: the collision check tests instance b against
+    obstacles[b], the switch solves run with the rows of the switched instances (tt_obca_solve_batch_scenes_device; M is
+    the switch solver's), and so does their adjoint in ``backward``.  d_min (a scalar or (B,)): the safety margin of the
+    switch solves, per instance; None is the switch solver's own.  ``run_graph`` does not take a switch loop either
+    way."""
 
     def __init__(self, solver, plan_x, plan_u, params, disturbance_params=None, measurement_noise=None,
                  obstacles=None, check_collision=True, switch_solver=None, warm_start=False, bug_compatible=True,
                  zero_on_fail=False, device=None, seed=0, policy=None, noise_in_plant=None, fuzzy_rule=None,
-                 switch_adjoint=False):
+                 switch_adjoint=False, d_min=None):
         self.solver = solver
         self.N = solver.N
         self.dev = torch.device("cuda", solver.device if device is None else device)
@@ -407,8 +423,19 @@ class ClosedLoop:
         self.dist = disturbance_params
         # simulation.py:509-513: noisy measurement iff disturbances are on
         self.measurement_noise = (disturbance_params is not None) if measurement_noise is None else measurement_noise
-        self.obstacles = None if obstacles is None else _dev(np.asarray(obstacles, dtype=np.float64).reshape(-1, 4),
-                                                             self.dev)
+        ob = None if obstacles is None else np.asarray(obstacles, dtype=np.float64)
+        self.per_scene = ob is not None and ob.ndim == 3   # (B,M,4): every loop has its own scene
+        if self.per_scene and ob.shape[2] != 4:
+            raise ValueError(f"per-instance obstacles must have shape (B, M, 4), got {ob.shape}")
+        self.obstacles = None if ob is None else _dev(ob if self.per_scene else ob.reshape(-1, 4), self.dev)
+        # the switch solves' safety margin: None (the switch solver's), a float for every loop, or a (B,) device tensor
+        dm = None if d_min is None else np.asarray(d_min, dtype=np.float64)
+        if dm is not None and dm.ndim > 1:
+            raise ValueError(f"d_min must be a scalar or have shape (B,), got {dm.shape}")
+        self.d_min = None if dm is None else (float(dm) if dm.ndim == 0 else _dev(dm, self.dev))
+        if switch_solver is not None and self.per_scene and ob.shape[1] != switch_solver.M:
+            raise ValueError(f"per-instance obstacles have M = {ob.shape[1]}, the switch solver has M = "
+                             f"{switch_solver.M}")
         self.check_collision = check_collision and self.obstacles is not None
         self.switch = switch_solver
         self.switch_adjoint = bool(switch_adjoint)   # run_tape / backward through the switch solve (tt_obca_vjp_device)
@@ -457,8 +484,20 @@ class ClosedLoop:
         self.rule = rule
         self.fuzzy = self._fuzzy_variant or rule is not None   # per-step weights and the unit-weight retry
 
+    def _scene_rows(self, idx):
+        """The per-instance scenes of the compacted batch idx: (obstacles (n,M,4) | None, d_min (n,) | None)."""
+        ob = self.obstacles[idx].contiguous() if self.per_scene else None
+        if self.d_min is None or torch.is_tensor(self.d_min):
+            dm = None if self.d_min is None else self.d_min[idx].contiguous()
+        else:
+            dm = torch.full((int(idx.numel()),), self.d_min, dtype=torch.float64, device=self.dev)
+        return ob, dm
+
     def _alloc(self, B):
         N, d, f = self.N, self.dev, torch.float64
+        for name, t in (("obstacles", self.obstacles if self.per_scene else None), ("d_min", self.d_min)):
+            if torch.is_tensor(t) and t.shape[0] != B:
+                raise ValueError(f"per-instance {name} are for B = {t.shape[0]} loops, the run has B = {B}")
         self.B = B
         self.state = torch.empty((B, 6), dtype=f, device=d)
         self.x_meas = torch.empty((B, 6), dtype=f, device=d)
@@ -609,16 +648,19 @@ class ClosedLoop:
         (flagged indices, compacted iterates and statuses) joins the tape."""
         idx = torch.nonzero(self.flag, as_tuple=True)[0]
         rec = self._switched
+        # per-instance scenes: the rows of the compacted batch (allocated on the loop's stream, which consumes them)
+        ob, dm = self._scene_rows(idx) if (self.per_scene or self.d_min is not None) and idx.numel() else (None, None)
+        rows = dict(obstacles=_ptr(ob) or 0, d_min=_ptr(dm) or 0) if ob is not None or dm is not None else {}
         if rec is None:
             self._resolve(idx, lambda n, x0, xr, ur, X, U, st, it, kk: self.switch.solve_device(
-                n, x0, 0, xr, ur, 0, X, U, 0, st, it, kk, stream=s.cuda_stream))
+                n, x0, 0, xr, ur, 0, X, U, 0, st, it, kk, stream=s.cuda_stream, **rows))
             return
         kept = []
 
         def solve(n, x0, xr, ur, X, U, st, it, kk, dual=0):   # (dual: the tracking solve's export, not the switch's)
             I = torch.empty((n, self.switch.iterate_len()), dtype=torch.float64, device=self.dev)
             self.switch.solve_device(n, x0, 0, xr, ur, 0, X, U, 0, st, it, kk, stream=s.cuda_stream,
-                                     iterate=I.data_ptr())
+                                     iterate=I.data_ptr(), **rows)
             kept.append(I)
         self._resolve(idx, solve)
         rec.append((idx, kept[0], self.st[idx].contiguous()) if kept else None)
@@ -820,7 +862,9 @@ class ClosedLoop:
         instance-steps from the same compacted adjoint call, which is then tt_obca_vjp_params_device (its g_x0, g_xref,
         g_uref agree with the plain call's to rounding).  The switch solver's scene must still be the run's.  The
         collision switch itself is piecewise constant in the scene and contributes nothing: the gradient holds while no
-        flag changes.  No host synchronisation is added."""
+        flag changes.  No host synchronisation is added.  With per-instance scenes (``ClosedLoop(obstacles=(B,M,4))`` and
+        / or ``d_min=``) the compacted adjoint gets the rows its solve got, and g_obstacles / g_dmin are each instance's
+        gradient in its own scene."""
         self._check_differentiable()
         if scene and (self.switch is None or not self.switch_adjoint):
             raise ValueError("scene=True needs a switch loop: ClosedLoop(..., switch_solver=..., switch_adjoint=True)")
@@ -911,19 +955,23 @@ class ClosedLoop:
                 with torch.cuda.stream(s):
                     gu_c = gU[idx].contiguous()
                     o0, oxr, our = z(n, 6), z(n, N + 1, 6), z(n, N, 2)
+                    # per-instance scenes: the adjoint gets the rows the switch solve got
+                    ob_c, dm_c = self._scene_rows(idx) if self.per_scene or self.d_min is not None else (None, None)
+                    rows = (dict(obstacles=_ptr(ob_c) or 0, d_min=_ptr(dm_c) or 0)
+                            if ob_c is not None or dm_c is not None else {})
                     if scene:  # (idx has no repeats: the indexed += is one add per row)
                         oob, odm = z(n, self.switch.M, 4), z(n)
                         work = torch.empty((n * wbytes // 8,), dtype=torch.float64, device=d)
                         self.switch.vjp_device(n, it_c.data_ptr(), st_c.data_ptr(), grad_u=gu_c.data_ptr(),
                                                g_x0=o0.data_ptr(), g_xref=oxr.data_ptr(), g_uref=our.data_ptr(),
                                                g_obstacles=oob.data_ptr(), g_dmin=odm.data_ptr(), work=work.data_ptr(),
-                                               stream=s.cuda_stream)
+                                               stream=s.cuda_stream, **rows)
                         g_ob[idx] += oob
                         g_dm[idx] += odm
                     else:
                         self.switch.vjp_device(n, it_c.data_ptr(), st_c.data_ptr(), grad_u=gu_c.data_ptr(),
                                                g_x0=o0.data_ptr(), g_xref=oxr.data_ptr(), g_uref=our.data_ptr(),
-                                               stream=s.cuda_stream)
+                                               stream=s.cuda_stream, **rows)
                     g_x0[idx], g_xr[idx], g_ur[idx] = o0, oxr, our
             _check(win_vjp(B, N, int(tape.ks[t]), int(Np), g_xr.data_ptr(), g_ur.data_ptr(), g_px.data_ptr(),
                            g_pu.data_ptr(), g_x0.data_ptr(), GS[t].data_ptr(), a.data_ptr(), g_ws.data_ptr(),

@@ -105,10 +105,13 @@ class TrajectoryOptimization(TrajectoryPlanning):
 
     optimize = plan
 
-    def plan_batch(self, initial_states, goal_states, z_guess=None):
-        """B scenarios at once: (B,6), (B,6), z_guess (B,n)|None -> (B,6,N+1), (B,2,N), z (B,n)."""
+    def plan_batch(self, initial_states, goal_states, z_guess=None, obstacle_lists=None):
+        """B scenarios at once: (B,6), (B,6), z_guess (B,n)|None -> (B,6,N+1), (B,2,N), z (B,n).  obstacle_lists: a
+        length-B list of obstacle lists in the constructor's format, one scene per scenario (each as long as the
+        constructor's list), or None for the constructor's list."""
         x0 = np.asarray(initial_states, dtype=np.float64).reshape(-1, 6)
         xg = np.asarray(goal_states, dtype=np.float64).reshape(-1, 6)
-        X, U, Z, st, it, _ = self._solver.solve(x0, x_goal=xg, z_guess=z_guess)
+        scenes = scenarios.scene_rows(obstacle_lists, x0.shape[0], len(self.obstacle_list))
+        X, U, Z, st, it, _ = self._solver.solve(x0, x_goal=xg, z_guess=z_guess, obstacles=scenes)
         self.last_status, self.last_iters = st, it
         return X.transpose(0, 2, 1).copy(), U.transpose(0, 2, 1).copy(), Z

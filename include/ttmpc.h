@@ -345,6 +345,46 @@ int tt_set_scene(void* handle, const double* obstacles, const double* d_min);
 int tt_get_scene(void* handle, double* obstacles, double* d_min);
 
 /* ---------------------------------------------------------------------------------------------
+ * Per-instance scenes: every instance of one launch solves against its own obstacle list and its own d_min.  They
+ * replace one handle per scene with B = 1 solves (Monte-Carlo over obstacle layouts, a per-instance safety margin).
+ * M stays the handle's: pad a shorter list with far-away obstacles.
+ *     obstacles [B][M][4] (cx, cy, w, h), or NULL: the handle's obstacles for every instance
+ *     d_min     [B],                      or NULL: the handle's d_min for every instance
+ * A NULL struct, or both members NULL, is exactly the call without scenes.  With every row equal to the handle's scene
+ * the results are bitwise those of the call without scenes, and row b's results are bitwise those of a B = 1 call on a
+ * handle whose tt_set_scene got row b.
+ *
+ * tt_obca_solve_batch_scenes / _device: tt_obca_solve_batch_iterate / _device (both OBCA variants; iterate_out may be
+ *   NULL) plus the scenes.  The host entry validates every scene by tt_set_scene's rule (finite, w, h > 0, d_min finite
+ *   and >= 0): -EINVAL, nothing launched, no output written.  The device entry cannot read device memory on the host:
+ *   each instance checks its own row when it starts, and one that fails ends with status TT_NONFINITE, 0 iterations and
+ *   the initial guess in its outputs; the other instances are unaffected.  A tracking handle: -EINVAL.
+ * tt_obca_vjp_scenes / _device: tt_obca_vjp_params / _device plus the scenes the solve was given (the adjoint reads the
+ *   obstacles only: d_min is in no coefficient of its system).  With g_obstacles, g_dmin, g_Q, g_R (and, on the device
+ *   entry, d_work) all NULL they run tt_obca_vjp's kernel and need no work buffer; otherwise tt_obca_vjp_params's.
+ *   g_obstacles [B][M][4] and g_dmin [B] are then the gradient in each instance's OWN scene: the caller sums nothing.
+ *   The host entry validates as above.  An instance the solve ended with TT_NONFINITE is skipped (vjp_status 2, zeros).
+ * tt_collision_scenes_device: tt_collision_device with obstacles [B][M][4], instance b against its own list. */
+typedef struct { const double* obstacles; /* [B][M][4] (cx, cy, w, h), or NULL: the handle's */
+                 const double* d_min;     /* [B], or NULL: the handle's */ } tt_obca_scenes;
+int tt_obca_solve_batch_scenes(void* handle, int B, const double* x0, const double* xgoal, const double* xref,
+                               const double* uref, const double* z_guess, double* x_out, double* u_out, double* z_out,
+                               int* status, int* iters, double* kkt_res, double* iterate_out,
+                               const tt_obca_scenes* scenes);
+int tt_obca_solve_batch_scenes_device(void* handle, int B, const double* d_x0, const double* d_xgoal,
+                                      const double* d_xref, const double* d_uref, const double* d_z_guess,
+                                      double* d_x_out, double* d_u_out, double* d_z_out, int* d_status, int* d_iters,
+                                      double* d_kkt_res, double* d_iterate_out, const tt_obca_scenes* d_scenes,
+                                      void* stream);
+int tt_obca_vjp_scenes(void* handle, int B, const double* iterate, const int* status, const double* xref,
+                       const double* uref, const double* grad_x, const double* grad_u,
+                       const tt_obca_vjp_params_out* out, const tt_obca_scenes* scenes);
+int tt_obca_vjp_scenes_device(void* handle, int B, const double* d_iterate, const int* d_status, const double* d_xref,
+                              const double* d_uref, const double* d_grad_x, const double* d_grad_u,
+                              const tt_obca_vjp_params_out* d_out, void* d_work, const tt_obca_scenes* d_scenes,
+                              void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Closed-loop simulation step, device pointers, asynchronous on `stream`.
  * The per-timestep glue of python-files/simulation.py:484-531 around the solve, batched over B
  * Monte-Carlo instances so that the whole loop stays in HBM:
@@ -383,6 +423,9 @@ int tt_sim_log_advance_device(int B, int* step, const double* state, const doubl
  * (device [M][4]: cx, cy, w, h).  flag[b] = 1 if any pose's truck or trailer touches an obstacle. */
 int tt_collision_device(int B, int K, const double* poses, long long stride_b, int stride_k, const double* obstacles,
                         int M, const tt_plant* p, int* flag, void* stream);
+/* The same with per-instance obstacle lists (device [B][M][4]): instance b is tested against obstacles + b*4M. */
+int tt_collision_scenes_device(int B, int K, const double* poses, long long stride_b, int stride_k,
+                               const double* obstacles, int M, const tt_plant* p, int* flag, void* stream);
 /* update(q, u, params[, DISTURBANCE_PARAMS]) (simulation.py:167-199) in place on state [B][6] with
  * u = u[b*u_stride + 0..1] (u_out of a solve: u_stride = 2N applies inputs[:, 0]).  zero_on_fail:
  * instances with status > TT_ACCEPTABLE apply zero control (simulation_nmpc.py:204-214).
