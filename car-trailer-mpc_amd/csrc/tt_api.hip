@@ -198,7 +198,7 @@ class Stager {
         bool used;
         void** dev;
     };
-    static constexpr int kMax = 16;
+    static constexpr int kMax = 20;  // (tt_obca_vjp_geometry registers 17)
     Item it_[kMax];
     int n_ = 0;
     size_t total_ = 0;
@@ -1034,10 +1034,11 @@ long long tt_obca_vjp_params_work_bytes(int N, int M) {
     return (N < 1 || M < 1) ? -EINVAL : (long long)(8 * ttmpc::obca_vjp_params_work_doubles(N, M));
 }
 
+// (d_geom [B][5]: also dL/d(L1, L2, Mh, W1, W2), the geometry instantiation; nullptr: the params one)
 static int obca_vjp_params_device(void* handle, int B, const double* d_iterate, const int* d_status,
                                   const double* d_xref, const double* d_uref, const double* d_grad_x,
                                   const double* d_grad_u, const tt_obca_vjp_params_out* d_out, void* d_work,
-                                  const double* d_obs, void* stream) {
+                                  const double* d_obs, void* stream, double* d_geom = nullptr) {
     Handle* h = static_cast<Handle*>(handle);
     if (const int rc = obca_vjp_params_checks(h, B, d_grad_x, d_grad_u, d_xref, d_uref, d_out)) return rc;
     if (!d_work) return fail(h, -EINVAL, "NULL work buffer (tt_obca_vjp_params_work_bytes per instance)%s");
@@ -1045,8 +1046,7 @@ static int obca_vjp_params_device(void* handle, int B, const double* d_iterate, 
     if (!d_iterate || !d_status || !d_out) return fail(h, -EINVAL, "NULL device buffer%s");
     DeviceGuard dg(h->device);
     if (dg.err != hipSuccess) return hip_fail(h, dg.err, "hipSetDevice");
-    ttmpc::ObcaVjpParamsArgs a =
-        diff_args<ttmpc::ObcaVjpParamsArgs>(h, B, nullptr, nullptr, nullptr, nullptr, d_status);
+    ttmpc::ObcaVjpGeomArgs a = diff_args<ttmpc::ObcaVjpGeomArgs>(h, B, nullptr, nullptr, nullptr, nullptr, d_status);
     a.M = h->cfg.M;
     a.W1 = h->cfg.W1;
     a.W2 = h->cfg.W2;
@@ -1067,7 +1067,9 @@ static int obca_vjp_params_device(void* handle, int B, const double* d_iterate, 
     a.g_Q = d_out->g_Q;
     a.g_R = d_out->g_R;
     a.work = static_cast<double*>(d_work);
-    const hipError_t e = ttmpc::launch_obca_vjp_params(a, static_cast<hipStream_t>(stream));
+    a.g_geom = d_geom;
+    const hipError_t e = d_geom ? ttmpc::launch_obca_vjp_geom(a, static_cast<hipStream_t>(stream))
+                                : ttmpc::launch_obca_vjp_params(a, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail(h, e, "OBCA params adjoint kernel launch");
     return 0;
 }
@@ -1097,7 +1099,7 @@ int tt_obca_vjp_scenes_device(void* handle, int B, const double* d_iterate, cons
 
 static int obca_vjp_params_host(void* handle, int B, const double* iterate, const int* status, const double* xref,
                                 const double* uref, const double* grad_x, const double* grad_u,
-                                const tt_obca_vjp_params_out* out, const double* obs) {
+                                const tt_obca_vjp_params_out* out, const double* obs, double* g_geom = nullptr) {
     Handle* h = static_cast<Handle*>(handle);
     if (const int rc = obca_vjp_params_checks(h, B, grad_x, grad_u, xref, uref, out)) return rc;  // (nothing staged yet)
     if (const int rc = prelude(h, B, kEmpty | kRange)) return result(rc);
@@ -1110,7 +1112,7 @@ static int obca_vjp_params_host(void* handle, int B, const double* iterate, cons
     const double *d_it, *d_gx, *d_gu, *d_xr, *d_ur, *d_obs;
     st.in(obs, b * 4 * M, &d_obs);
     const int* d_st;
-    double* d_work;
+    double *d_work, *d_geom;
     tt_obca_vjp_params_out dout;
     st.in(iterate, b * ttmpc::obca_iterate_len(h->cfg.N, h->cfg.M), &d_it);
     st.in(grad_x, nx, &d_gx);
@@ -1126,11 +1128,12 @@ static int obca_vjp_params_host(void* handle, int B, const double* iterate, cons
     st.out(out->g_dmin, b, &dout.g_dmin);
     st.out(out->g_Q, b * 36, &dout.g_Q);
     st.out(out->g_R, b * 4, &dout.g_R);
+    st.out(g_geom, b * 5, &d_geom);
     st.out((double*)nullptr, b * ttmpc::obca_vjp_params_work_doubles(h->cfg.N, h->cfg.M), &d_work, true);
     if (!st.carve(h->xfer)) return no_memory(h, "adjoint staging");
     hipStream_t s = h->stream;
     return st.run(h, s, "OBCA params adjoint", [&] {
-        return obca_vjp_params_device(handle, B, d_it, d_st, d_xr, d_ur, d_gx, d_gu, &dout, d_work, d_obs, s);
+        return obca_vjp_params_device(handle, B, d_it, d_st, d_xr, d_ur, d_gx, d_gu, &dout, d_work, d_obs, s, d_geom);
     });
 }
 
@@ -1153,6 +1156,68 @@ int tt_obca_vjp_scenes(void* handle, int B, const double* iterate, const int* st
         return obca_vjp_host(handle, B, iterate, status, grad_x, grad_u, &o, obs);
     }
     return obca_vjp_params_host(handle, B, iterate, status, xref, uref, grad_x, grad_u, out, obs);
+}
+
+// tt_obca_vjp_geometry*: the first eight members are tt_obca_vjp_params_out's
+static tt_obca_vjp_params_out params_members(const tt_obca_vjp_geometry_out* o) {
+    return {o->g_x0, o->g_xref, o->g_uref, o->vjp_status, o->g_obstacles, o->g_dmin, o->g_Q, o->g_R};
+}
+
+int tt_obca_vjp_geometry_device(void* handle, int B, const double* d_iterate, const int* d_status,
+                                const double* d_xref, const double* d_uref, const double* d_grad_x,
+                                const double* d_grad_u, const tt_obca_vjp_geometry_out* d_out, void* d_work,
+                                const tt_obca_scenes* d_scenes, void* stream) {
+    if (!d_out || !d_out->g_geometry) {  // no geometry wanted: tt_obca_vjp_scenes_device, its kernels and its bits
+        tt_obca_vjp_params_out o;
+        if (d_out) o = params_members(d_out);
+        return tt_obca_vjp_scenes_device(handle, B, d_iterate, d_status, d_xref, d_uref, d_grad_x, d_grad_u,
+                                         d_out ? &o : nullptr, d_work, d_scenes, stream);
+    }
+    const tt_obca_vjp_params_out o = params_members(d_out);
+    return obca_vjp_params_device(handle, B, d_iterate, d_status, d_xref, d_uref, d_grad_x, d_grad_u, &o, d_work,
+                                  d_scenes ? d_scenes->obstacles : nullptr, stream, d_out->g_geometry);
+}
+
+int tt_obca_vjp_geometry(void* handle, int B, const double* iterate, const int* status, const double* xref,
+                         const double* uref, const double* grad_x, const double* grad_u,
+                         const tt_obca_vjp_geometry_out* out, const tt_obca_scenes* scenes) {
+    if (!out || !out->g_geometry) {
+        tt_obca_vjp_params_out o;
+        if (out) o = params_members(out);
+        return tt_obca_vjp_scenes(handle, B, iterate, status, xref, uref, grad_x, grad_u, out ? &o : nullptr, scenes);
+    }
+    Handle* h = static_cast<Handle*>(handle);
+    if (h && is_obca(h->cfg) && scenes && scenes->d_min)  // (as tt_obca_vjp_scenes: a scene the solve would have refused)
+        if (const int rc = check_scenes(h, B, nullptr, scenes->d_min)) return rc;
+    const tt_obca_vjp_params_out o = params_members(out);
+    return obca_vjp_params_host(handle, B, iterate, status, xref, uref, grad_x, grad_u, &o,
+                                scenes ? scenes->obstacles : nullptr, out->g_geometry);
+}
+
+int tt_set_geometry(void* handle, double L1, double L2, double Mh, double W1, double W2) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (const int rc = prelude(h, 0, kHandle | kObcaOnly)) return rc;
+    if (!(L1 > 0) || !(L2 > 0) || !(W1 > 0) || !(W2 > 0) || !isfinite(L1) || !isfinite(L2) || !isfinite(W1) ||
+        !isfinite(W2) || !isfinite(Mh))
+        return fail(h, -EINVAL, "params L1, L2, W1, W2 must be finite and > 0 and M finite%s");
+    // every launch fills its kernel arguments from cfg: nothing on the device holds the old values
+    h->cfg.L1 = L1;
+    h->cfg.L2 = L2;
+    h->cfg.Mh = Mh;
+    h->cfg.W1 = W1;
+    h->cfg.W2 = W2;
+    return 0;
+}
+
+int tt_get_geometry(void* handle, double* L1, double* L2, double* Mh, double* W1, double* W2) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (const int rc = prelude(h, 0, kHandle | kObcaOnly)) return rc;
+    if (L1) *L1 = h->cfg.L1;
+    if (L2) *L2 = h->cfg.L2;
+    if (Mh) *Mh = h->cfg.Mh;
+    if (W1) *W1 = h->cfg.W1;
+    if (W2) *W2 = h->cfg.W2;
+    return 0;
 }
 
 int tt_set_scene(void* handle, const double* obstacles, const double* d_min) {

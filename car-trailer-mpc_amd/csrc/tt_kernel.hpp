@@ -229,5 +229,12 @@ struct ObcaVjpParamsArgs : ObcaVjpArgs {
 };
 __host__ __device__ inline size_t obca_vjp_params_work_doubles(int N, int M) { return (size_t)32 * M * (N + 1); }
 hipError_t launch_obca_vjp_params(const ObcaVjpParamsArgs& a, hipStream_t stream);
+// the params adjoint plus dL/d(L1, L2, Mh, W1, W2): the kernel's geometry instantiation (the same LDS record and the
+// same workspace).  The member sits behind ObcaVjpParamsArgs so that the plain and the params instantiations'
+// argument blocks, and with them their code, stay what they were
+struct ObcaVjpGeomArgs : ObcaVjpParamsArgs {
+    double* g_geom;       // [B][5] (L1, L2, Mh, W1, W2), never nullptr here
+};
+hipError_t launch_obca_vjp_geom(const ObcaVjpGeomArgs& a, hipStream_t stream);
 
 }  // namespace ttmpc

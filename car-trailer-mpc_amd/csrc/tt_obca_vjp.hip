@@ -44,6 +44,18 @@
 // residual against that v; one closing pass after the last step applies the last correction and reduces the blocks'
 // five terms per obstacle in block order (slots, then registers: no atomics, no LDS beyond the record above).
 // tests/obca_scene_reference.py (model_scene_vjp) is its numpy model.
+//
+// The geometry instantiation (tt_obca_vjp_geometry_device) is the params one plus dL/d(L1, L2, Mh, W1, W2), for a
+// geometry the batch shares.  Two parts of F depend on it.  Of a block only the d_min row d_0 does (build_row,
+// cls == 3, i == 0): linearly through g = (hl, hw, hl, hw) and through the body centre p, so the closing pass forms
+// the block's two (truck: L1, W1) or three (trailer: L2, W2, Mh) terms from the carried v, the stage's pose adjoint and
+// the block's iterate values (geometry_block_terms) and reduces them in flat block order as the scene terms: slot
+// entries 5 .. 7, then one register in each of five fixed threads, no atomics.  The dynamics rows and the
+// -A_k' y_{k+1} part of the x-rows (L1, L2, Mh) give tt_vjp.hip's model_gradient sum with this solve's lam: the final
+// lx (sL) and the last step's ly (sY; only ly_0 is corrected again, and the numpy model meets the cap with it), the
+// stage terms through the dead w field, summed over k by three of the five threads.  Same LDS record, same workspace;
+// the other outputs are bitwise the params instantiation's.  tests/obca_geometry_reference.py (model_geometry_vjp) is
+// its numpy model.
 #include <math.h>
 
 #include <type_traits>
@@ -387,6 +399,39 @@ __device__ __forceinline__ bool carry_block(double (&row)[20], const double (&hx
     return ok && isfinite(ur);
 }
 
+__device__ __forceinline__ void zero_geom(const ObcaVjpGeomArgs& a, int b, int tid) {
+    if (tid < 5) a.g_geom[(size_t)b * 5 + tid] = 0.0;
+}
+
+// The geometry instantiation's share of one block (lane-uniform within the group): the terms of -lam' dF/dtheta the
+// block's d_min row d_0 = g' mu - (a, c) . (p - centre) + ... contributes through g = (hl, hw, hl, hw) and the body
+// centre p.  xk: the stage's state; q: the block's iterate (mu 4, lam 4 first, y_d0 at 28); v0 .. v7, vy: the entries
+// mu 4, lam 4 and y_d0 of the block's carried unknowns; lp2, lp3: the stage's pose adjoint in theta and psi.
+// t[0]: the length (L1 truck, L2 trailer), t[1]: the width (W1, W2), t[2]: Mh (trailer; 0 for the truck).
+// tests/obca_geometry_reference.py (block_share) has the derivation.
+__device__ __forceinline__ void geometry_block_terms(const double* xk, int j, const double* q, const double (&v)[8],
+                                                     double vy, double lp2, double lp3, double (&t)[3]) {
+    const double th = xk[2], ps = xk[3];
+    const double a = q[4] - q[6], c = q[5] - q[7], yd0 = q[28];
+    const double va = v[4] - v[6], vc = v[5] - v[7], ve = v[0] + v[2], vo = v[1] + v[3];
+    const double me = q[0] + q[2], mo = q[1] + q[3];
+    double st, ct;
+    sincos(th, &st, &ct);
+    t[1] = -(yd0 * (0.5 * vo) + vy * (0.5 * mo));
+    if ((j & 1) == 0) {  // truck: dp/dL1 = (ct, st) / 2, d2p/dth dL1 = (-st, ct) / 2
+        const double dp0 = 0.5 * ct, dp1 = 0.5 * st, rot = a * (-0.5 * st) + c * (0.5 * ct);
+        t[0] = -(yd0 * (0.5 * ve - (dp0 * va + dp1 * vc) - rot * lp2) + vy * (0.5 * me - (a * dp0 + c * dp1)));
+        t[2] = 0.0;
+    } else {  // trailer: dp/dL2 = -(ca, sa) / 2, d2p/d(th, psi) dL2 = (sa, -ca) / 2; dp/dMh = -(ct, st), d2p/dth dMh = (st, -ct)
+        double sa, ca;
+        sincos(th + ps, &sa, &ca);
+        const double dp0 = -0.5 * ca, dp1 = -0.5 * sa, rot = a * (0.5 * sa) + c * (-0.5 * ca);
+        t[0] = -(yd0 * (0.5 * ve - (dp0 * va + dp1 * vc) - rot * lp2 - rot * lp3) + vy * (0.5 * me - (a * dp0 + c * dp1)));
+        const double rm = a * st + c * -ct;
+        t[2] = -(yd0 * (-(-ct * va + -st * vc) - rm * lp2) + vy * (-(a * -ct + c * -st)));
+    }
+}
+
 __device__ __forceinline__ void zero_params(const ObcaVjpParamsArgs& a, int b, int tid) {
     if (a.g_obs)
         for (int t = tid; t < 4 * a.M; t += kT) a.g_obs[(size_t)b * 4 * a.M + t] = 0.0;
@@ -431,15 +476,19 @@ __device__ __forceinline__ void forward_sweep(double* stg, const double* Ks, int
 }
 
 // kParams: the instantiation that also forms dL/d(obstacles, d_min, Q, R) (tt_obca_vjp_params*); everything it adds sits
-// behind `if constexpr`, so the plain instantiation is the kernel it was
-template <bool kParams>
-__global__ __launch_bounds__(kT) void obca_vjp_kernel(std::conditional_t<kParams, ObcaVjpParamsArgs, ObcaVjpArgs> a) {
+// behind `if constexpr`, so the plain instantiation is the kernel it was.  kGeom (with kParams): the instantiation that
+// also forms dL/d(L1, L2, Mh, W1, W2) (tt_obca_vjp_geometry*), behind `if constexpr` again
+template <bool kParams, bool kGeom = false>
+__global__ __launch_bounds__(kT) void obca_vjp_kernel(
+    std::conditional_t<kGeom, ObcaVjpGeomArgs, std::conditional_t<kParams, ObcaVjpParamsArgs, ObcaVjpArgs>> a) {
+    static_assert(kParams || !kGeom, "the geometry terms read the carried block unknowns");
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int N = a.N, S = N + 1, nbk = 2 * a.M, nblk = S * nbk;
     if (a.status[b] > 1) {  // > TT_ACCEPTABLE: no optimum to differentiate
         zero_outputs(a, b, tid);
         if constexpr (kParams) zero_params(a, b, tid);
+        if constexpr (kGeom) zero_geom(a, b, tid);
         if (a.vjp_status && tid == 0) a.vjp_status[b] = 2;
         return;
     }
@@ -542,6 +591,7 @@ __global__ __launch_bounds__(kT) void obca_vjp_kernel(std::conditional_t<kParams
     if (__syncthreads_or(bad)) {
         zero_outputs(a, b, tid);
         if constexpr (kParams) zero_params(a, b, tid);
+        if constexpr (kGeom) zero_geom(a, b, tid);
         if (a.vjp_status && tid == 0) a.vjp_status[b] = 1;
         return;
     }
@@ -697,6 +747,10 @@ __global__ __launch_bounds__(kT) void obca_vjp_kernel(std::conditional_t<kParams
     }
     // ---- the closing block pass: the last correction into v; the blocks' scene terms per obstacle in block order ----
     double acc = 0.0;  // thread 5 m + i: g_b[i] (i < 4) or the d_min sum (i = 4) of obstacle m
+    // (geometry) thread kGeomT + i: the block sum of L1, L2, Mh, W1, W2; its slot entry and its body (1: trailer)
+    constexpr int kGeomT = 5 * kObcaMaxM;
+    [[maybe_unused]] double gacc = 0.0;
+    [[maybe_unused]] const int gi = tid - kGeomT, gslot = gi < 2 ? 5 : gi == 2 ? 7 : 6, gbody = (gi == 1 || gi == 2 || gi == 4) ? 1 : 0;
     if constexpr (kParams) {
         const double* wk = a.work + (size_t)b * nblk * 16;
         const int am = tid / 5, ai = tid - 5 * am;
@@ -717,6 +771,14 @@ __global__ __launch_bounds__(kT) void obca_vjp_kernel(std::conditional_t<kParams
                 if (r16 < 4) slot[grp * 16 + r16] = -(q[28] * vl + q[4 + r16] * vy);
                 if (r16 == 4) slot[grp * 16 + 4] = -vy;
             }
+            if constexpr (kGeom) {
+                double v8[8], gt[3];
+#pragma unroll
+                for (int t = 0; t < 8; ++t) v8[t] = __shfl(vr, t, kGL);
+                geometry_block_terms(it + 30 * (size_t)k, j, q, v8, vy, stg[k * kStage + sL + 2],
+                                     stg[k * kStage + sL + 3], gt);
+                if (f0 + grp < nblk && r16 >= 5 && r16 < 8) slot[grp * 16 + r16] = r16 == 5 ? gt[0] : r16 == 6 ? gt[1] : gt[2];
+            }
             __syncthreads();
             if (tid < 5 * kObcaMaxM) {
                 const int ng = min(kGroups, nblk - f0);
@@ -726,12 +788,57 @@ __global__ __launch_bounds__(kT) void obca_vjp_kernel(std::conditional_t<kParams
                     if (++jj == nbk) jj = 0;
                 }
             }
+            if constexpr (kGeom) {
+                if (gi >= 0 && gi < 5) {
+                    const int ng = min(kGroups, nblk - f0);
+                    int jj = f0 % nbk;
+                    for (int g = 0; g < ng; ++g) {
+                        if ((jj & 1) == gbody) gacc += slot[g * 16 + gslot];
+                        if (++jj == nbk) jj = 0;
+                    }
+                }
+            }
             __syncthreads();
         }
+    }
+    // ---- (geometry) the dynamics share: dt sum_k [lx_k' (dJ_f/dtheta)' y_{k+1} + ly_{k+1}' df/dtheta], tt_vjp.hip's
+    // model_gradient expressions with the final lx and the last step's ly (sY); the stage terms go through the dead w field
+    if constexpr (kGeom) {
+        const double iL1 = 1.0 / a.L1, iL2 = 1.0 / a.L2, iL1L2 = iL1 * iL2, Mh = a.Mh;
+        for (int k = tid; k < N; k += kT) {
+            double* r = stg + k * kStage;
+            const double* xk = it + 30 * (size_t)k;
+            const double* y = it + 30 * (size_t)(k + 1) + 24;  // y_{k+1}
+            const double* ly = r + kStage + sY;                // lam_y,k+1
+            const double lx3 = r[sL + 3], lx4 = r[sL + 4], lx5 = r[sL + 5];
+            double sps, cps, sph, cph;
+            sincos(xk[3], &sps, &cps);
+            sincos(xk[4], &sph, &cph);
+            const double v = xk[5], ic = 1.0 / cph, t = sph * ic, c2 = ic * ic;
+            const double kk = 1.0 + Mh * iL2 * cps;
+            const double y2 = y[2], y3 = y[3], l2 = ly[2], l3 = ly[3];
+            const double a24 = v * c2 * iL1, a25 = t * iL1, vt = v * t * iL1;
+            const double mc = Mh * cps * iL2 * iL2, s2 = sps * iL2 * iL2;
+            r[sW + 0] = y2 * (-(a24 * iL1) * lx4 + -(a25 * iL1) * lx5)
+                      + y3 * (-(vt * Mh * sps * iL1L2) * lx3 + (a24 * kk * iL1) * lx4 + (a25 * kk * iL1) * lx5)
+                      + (l2 * -(vt * iL1) + l3 * (vt * kk * iL1));
+            r[sW + 1] = y3 * ((v * cps * iL2 * iL2 - vt * Mh * sps * iL2 * iL2) * lx3 + (a24 * mc) * lx4 + (a25 * mc + s2) * lx5)
+                      + l3 * (vt * mc + v * s2);
+            r[sW + 2] = y3 * ((vt * sps * iL2) * lx3 + -(a24 * cps * iL2) * lx4 + -(a25 * cps * iL2) * lx5)
+                      + l3 * -(vt * cps * iL2);
+        }
+        __syncthreads();
+        if (gi >= 0 && gi < 3) {
+            double s = 0.0;
+            for (int k = 0; k < N; ++k) s += stg[k * kStage + sW + gi];
+            gacc = gacc + dt * s;
+        }
+        if (gi >= 0 && gi < 5) bad |= !isfinite(gacc);
     }
     if (__syncthreads_or(bad)) {
         zero_outputs(a, b, tid);
         if constexpr (kParams) zero_params(a, b, tid);
+        if constexpr (kGeom) zero_geom(a, b, tid);
         if (a.vjp_status && tid == 0) a.vjp_status[b] = 1;
         return;
     }
@@ -755,6 +862,9 @@ __global__ __launch_bounds__(kT) void obca_vjp_kernel(std::conditional_t<kParams
                 a.g_uref[((size_t)b * N + k) * 2 + ii] = s;
             }
         }
+    }
+    if constexpr (kGeom) {
+        if (gi >= 0 && gi < 5) a.g_geom[(size_t)b * 5 + gi] = gacc;
     }
     if constexpr (kParams) {
         if (tid < 5 * kObcaMaxM) slot[tid] = acc;
@@ -808,6 +918,9 @@ __global__ __launch_bounds__(kT) void obca_vjp_kernel(std::conditional_t<kParams
     if constexpr (kParams) {
         if (late) zero_params(a, b, tid);
     }
+    if constexpr (kGeom) {
+        if (late) zero_geom(a, b, tid);
+    }
     if (a.vjp_status && tid == 0) a.vjp_status[b] = late ? 1 : 0;
 }
 
@@ -824,6 +937,13 @@ hipError_t launch_obca_vjp_params(const ObcaVjpParamsArgs& a, hipStream_t stream
     const int bytes = 8 * obca_vjp_lds_doubles(a.N);
     if (bytes > 64 * 1024 - 512 || a.M < 1 || a.M > kObcaMaxM || !a.work) return hipErrorInvalidValue;
     hipLaunchKernelGGL(obca_vjp_kernel<true>, dim3(a.B), dim3(kT), bytes, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_obca_vjp_geom(const ObcaVjpGeomArgs& a, hipStream_t stream) {
+    const int bytes = 8 * obca_vjp_lds_doubles(a.N);
+    if (bytes > 64 * 1024 - 512 || a.M < 1 || a.M > kObcaMaxM || !a.work || !a.g_geom) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((obca_vjp_kernel<true, true>), dim3(a.B), dim3(kT), bytes, stream, a);
     return hipGetLastError();
 }
 

@@ -74,6 +74,11 @@ class TTObcaVjpParamsOut(C.Structure):
                                         ("g_R", C.c_void_p)]
 
 
+class TTObcaVjpGeometryOut(C.Structure):
+    """tt_obca_vjp_geometry_out (include/ttmpc.h): tt_obca_vjp_params_out and g_geometry [B][5] behind it."""
+    _fields_ = TTObcaVjpParamsOut._fields_ + [("g_geometry", C.c_void_p)]
+
+
 class TTObcaScenes(C.Structure):
     """tt_obca_scenes (include/ttmpc.h): per-instance obstacles [B][M][4] and d_min [B]; a NULL member = the handle's."""
     _fields_ = [("obstacles", C.c_void_p), ("d_min", C.c_void_p)]
@@ -111,8 +116,9 @@ TrackVjpModelResult = TrackVjpResult
 class ObcaVjpParamsResult:
     """What ``ObcaSolver.vjp(..., params=True)`` returns: g_x0, g_xref, g_uref and vjp_status as ``TrackVjpResult``,
     and g_obstacles (B,M,4) = dL/d(cx, cy, w, h), g_dmin (B,), g_Q (B,6,6) and g_R (B,2,2) (None without xref / uref),
-    all per instance; the arrays of a failed instance are zeros."""
-    __slots__ = ("g_x0", "g_xref", "g_uref", "vjp_status", "g_obstacles", "g_dmin", "g_Q", "g_R")
+    all per instance; the arrays of a failed instance are zeros.  With ``geometry=True`` also g_geometry (B,5) =
+    dL/d(L1, L2, M, W1, W2) per instance, else None."""
+    __slots__ = ("g_x0", "g_xref", "g_uref", "vjp_status", "g_obstacles", "g_dmin", "g_Q", "g_R", "g_geometry")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -239,6 +245,17 @@ def lib():
         L.tt_obca_vjp_scenes_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [po, C.c_void_p, ps,
                                                                                           C.c_void_p]
         L.tt_obca_vjp_scenes_device.restype = C.c_int
+    if not os.environ.get("TTMPC_LIB") or hasattr(L, "tt_obca_vjp_geometry_device"):  # (A/B against a build without them)
+        pg, ps = C.POINTER(TTObcaVjpGeometryOut), C.POINTER(TTObcaScenes)
+        L.tt_obca_vjp_geometry.argtypes = [C.c_void_p, C.c_int, _dp, _ip, _dp, _dp, _dp, _dp, pg, ps]
+        L.tt_obca_vjp_geometry.restype = C.c_int
+        L.tt_obca_vjp_geometry_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [pg, C.c_void_p, ps,
+                                                                                            C.c_void_p]
+        L.tt_obca_vjp_geometry_device.restype = C.c_int
+        L.tt_set_geometry.argtypes = [C.c_void_p] + [C.c_double] * 5
+        L.tt_set_geometry.restype = C.c_int
+        L.tt_get_geometry.argtypes = [C.c_void_p] + [_dp] * 5
+        L.tt_get_geometry.restype = C.c_int
     L.tt_obca_n.argtypes = [C.c_int, C.c_int]
     L.tt_obca_n.restype = C.c_longlong
     L.tt_obca_workspace_bytes.argtypes = [C.c_int, C.c_int]
@@ -305,7 +322,8 @@ EXPORTED_SYMBOLS = ("tt_create", "tt_solve_batch", "tt_solve_batch_device", "tt_
                     "tt_fuzzy_weights_vjp_device", "tt_sim_window_vjp_fuzzy_device", "tt_obca_vjp_device",
                     "tt_obca_vjp", "tt_obca_vjp_params_work_bytes", "tt_obca_vjp_params_device", "tt_obca_vjp_params",
                     "tt_set_scene", "tt_get_scene", "tt_obca_solve_batch_scenes", "tt_obca_solve_batch_scenes_device",
-                    "tt_obca_vjp_scenes", "tt_obca_vjp_scenes_device", "tt_collision_scenes_device")
+                    "tt_obca_vjp_scenes", "tt_obca_vjp_scenes_device", "tt_collision_scenes_device",
+                    "tt_obca_vjp_geometry", "tt_obca_vjp_geometry_device", "tt_set_geometry", "tt_get_geometry")
 
 
 def _ptr(a):
@@ -723,12 +741,31 @@ class ObcaSolver(_Solver):
             self._err(rc, "tt_get_scene")
         return ob, float(dm[0])
 
+    def set_geometry(self, L1=None, L2=None, M=None, W1=None, W2=None):
+        """tt_set_geometry: change the handle's lengths L1, L2, hitch offset M and widths W1, W2 (a value left None keeps
+        its current one).  Host-side state only: every later call of this solver runs with the new values, and a solve
+        is bitwise that of a fresh solver created with them.  Work already enqueued keeps the old values.  Raises
+        TTError for a length or width <= 0 or a non-finite value (nothing is changed then)."""
+        cur = self.geometry()
+        v = [float(c if x is None else x) for x, c in zip((L1, L2, M, W1, W2), cur)]
+        rc = self._L.tt_set_geometry(self._h, *v)
+        if rc != 0:
+            self._err(rc, "tt_set_geometry")
+
+    def geometry(self):
+        """tt_get_geometry: the handle's current (L1, L2, M, W1, W2)."""
+        v = [C.c_double() for _ in range(5)]
+        rc = self._L.tt_get_geometry(self._h, *[C.byref(c) for c in v])
+        if rc != 0:
+            self._err(rc, "tt_get_geometry")
+        return tuple(c.value for c in v)
+
     def vjp_params_work_bytes(self):
         """tt_obca_vjp_params_work_bytes of this handle's (N, M): bytes of ``work`` per instance."""
         return int(self._L.tt_obca_vjp_params_work_bytes(self.N, self.M))
 
     def vjp_device(self, B, iterate, status, grad_x=0, grad_u=0, g_x0=0, g_xref=0, g_uref=0, vjp_status=0, stream=0,
-                   xref=0, uref=0, g_obstacles=0, g_dmin=0, g_Q=0, g_R=0, work=0, obstacles=0, d_min=0):
+                   xref=0, uref=0, g_obstacles=0, g_dmin=0, g_Q=0, g_R=0, work=0, obstacles=0, d_min=0, g_geometry=0):
         """tt_obca_vjp_device (TT_VARIANT_TRACK_OBCA): the adjoint kernel on the device iterate and status of an earlier
         ``solve_device(..., iterate=ptr)`` and the upstream gradients grad_x = dL/dX, grad_u = dL/dU (0 = zeros, not
         both).  Outputs (0 = not wanted): g_x0, g_xref, g_uref, vjp_status.  Uses no buffer of the handle: any stream
@@ -739,7 +776,20 @@ class ObcaSolver(_Solver):
         scene and weight gradients; xref / uref are the solve's (needed for g_Q / g_R only).
 
         obstacles (B,M,4) / d_min (B,): the per-instance scenes the solve was given (tt_obca_vjp_scenes_device, which
-        picks the kernel by the same rule); g_obstacles and g_dmin are then the gradients in each instance's own scene."""
+        picks the kernel by the same rule); g_obstacles and g_dmin are then the gradients in each instance's own scene.
+
+        g_geometry (B,5): also dL/d(L1, L2, M, W1, W2) per instance at the handle's geometry
+        (tt_obca_vjp_geometry_device; needs ``work``); the other outputs are bitwise those of the call without it."""
+        if g_geometry:
+            gout = TTObcaVjpGeometryOut(g_x0 or None, g_xref or None, g_uref or None, vjp_status or None,
+                                        g_obstacles or None, g_dmin or None, g_Q or None, g_R or None, g_geometry)
+            sc = TTObcaScenes(obstacles or None, d_min or None)
+            rc = self._L.tt_obca_vjp_geometry_device(self._h, int(B), iterate or None, status or None, xref or None,
+                                                     uref or None, grad_x or None, grad_u or None, C.byref(gout),
+                                                     work or None, C.byref(sc), stream or None)
+            if rc != 0:
+                self._err(rc, "tt_obca_vjp_geometry_device")
+            return
         if obstacles or d_min:
             pout = TTObcaVjpParamsOut(g_x0 or None, g_xref or None, g_uref or None, vjp_status or None,
                                       g_obstacles or None, g_dmin or None, g_Q or None, g_R or None)
@@ -765,7 +815,8 @@ class ObcaSolver(_Solver):
         if rc != 0:
             self._err(rc, "tt_obca_vjp_device")
 
-    def vjp(self, iterate, status, grad_x, grad_u, xref=None, uref=None, params=False, obstacles=None, d_min=None):
+    def vjp(self, iterate, status, grad_x, grad_u, xref=None, uref=None, params=False, obstacles=None, d_min=None,
+            geometry=False):
         """Host arrays: the gradient of a scalar loss L(X, U) with respect to x_init, xref and uref of the MPC+OBCA
         solve that returned iterate (B, tt_obca_iterate_len) and status (B,); grad_x (B,N+1,6) = dL/dX and grad_u (B,N,2) =
         dL/dU (either may be None for zeros).  Returns a ``TrackVjpResult`` (g_wq_wr and g_model are None).
@@ -774,9 +825,12 @@ class ObcaSolver(_Solver):
         solve's xref (B,N+1,6) / uref (B,N,2) are given, g_Q / g_R.
 
         obstacles (B,M,4) / d_min (B,) or a scalar: the per-instance scenes the solve was given (tt_obca_vjp_scenes);
-        g_obstacles and g_dmin are then per instance in its own scene."""
-        if params:
-            return self._vjp_params(iterate, status, grad_x, grad_u, xref, uref, obstacles, d_min)
+        g_obstacles and g_dmin are then per instance in its own scene.
+
+        ``geometry=True`` implies ``params=True`` and adds g_geometry (B,5) = dL/d(L1, L2, M, W1, W2) per instance
+        (tt_obca_vjp_geometry); the other arrays are bitwise those of the params call."""
+        if params or geometry:
+            return self._vjp_params(iterate, status, grad_x, grad_u, xref, uref, obstacles, d_min, geometry)
         N = self.N
         I = _f64(iterate).reshape(-1, self.iterate_len())
         B = I.shape[0]
@@ -801,11 +855,11 @@ class ObcaSolver(_Solver):
             self._err(rc, "tt_obca_vjp")
         return r
 
-    def _vjp_params(self, iterate, status, grad_x, grad_u, xref, uref, obstacles=None, d_min=None):
+    def _vjp_params(self, iterate, status, grad_x, grad_u, xref, uref, obstacles=None, d_min=None, geometry=False):
         N, M = self.N, self.M
         I = _f64(iterate).reshape(-1, self.iterate_len())
         B = I.shape[0]
-        if obstacles is not None or d_min is not None:
+        if obstacles is not None or d_min is not None or geometry:
             ob, dm, sc = self._scenes(B, obstacles, d_min)
         st = np.ascontiguousarray(np.asarray(status, dtype=np.int32)).reshape(B)
         gx = None if grad_x is None else _f64(grad_x, (B, N + 1, 6))
@@ -815,7 +869,17 @@ class ObcaSolver(_Solver):
         r = ObcaVjpParamsResult(g_x0=np.empty((B, 6)), g_xref=np.empty((B, N + 1, 6)), g_uref=np.empty((B, N, 2)),
                                 vjp_status=np.empty(B, dtype=np.int32), g_obstacles=np.empty((B, M, 4)),
                                 g_dmin=np.empty(B), g_Q=None if xr is None else np.empty((B, 6, 6)),
-                                g_R=None if ur is None else np.empty((B, 2, 2)))
+                                g_R=None if ur is None else np.empty((B, 2, 2)),
+                                g_geometry=np.empty((B, 5)) if geometry else None)
+        if geometry:
+            gout = TTObcaVjpGeometryOut(*[None if a is None else a.ctypes.data for a in
+                                          (r.g_x0, r.g_xref, r.g_uref, r.vjp_status, r.g_obstacles, r.g_dmin, r.g_Q,
+                                           r.g_R, r.g_geometry)])
+            rc = self._L.tt_obca_vjp_geometry(self._h, B, _ptr(I), st.ctypes.data_as(_ip), _ptr(xr), _ptr(ur), _ptr(gx),
+                                              _ptr(gu), C.byref(gout), C.byref(sc))
+            if rc != 0:
+                self._err(rc, "tt_obca_vjp_geometry")
+            return r
         out = TTObcaVjpParamsOut(*[None if a is None else a.ctypes.data for a in
                                    (r.g_x0, r.g_xref, r.g_uref, r.vjp_status, r.g_obstacles, r.g_dmin, r.g_Q, r.g_R)])
         if obstacles is not None or d_min is not None:

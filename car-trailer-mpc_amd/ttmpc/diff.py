@@ -53,12 +53,13 @@ def _check(name, t, shape):
 
 
 _GEOMETRY = "(L1, L2, M)"
+_OBCA_GEOMETRY = "(L1, L2, M, W1, W2)"
 _THETA = "(psi_full, gain_hitch, gain_steer, gain_rate, rev_hitch, rev_steer, rev_rate)"
 
 
 def _host_vector(name, t, what):
-    """A geometry (_GEOMETRY) or rule-parameter (_THETA) tensor as host floats: float64, shape (3,) or (7,), on the CPU
-    or on a device (one host read)."""
+    """A geometry (_GEOMETRY, _OBCA_GEOMETRY) or rule-parameter (_THETA) tensor as host floats: float64, shape (3,),
+    (5,) or (7,), on the CPU or on a device (one host read)."""
     n = what.count(",") + 1
     if not (torch.is_tensor(t) and t.dtype == torch.float64 and tuple(t.shape) == (n,)):
         raise TypeError(f"{name} must be a float64 tensor of shape ({n},) = {what}")
@@ -175,11 +176,24 @@ class ObcaTrackingSolveFunction(torch.autograd.Function):
     obstacles of shape (B,M,4) and / or d_min of shape (B,) select the per-instance path instead: every instance solves
     against its own row (tt_obca_solve_batch_scenes_device; one left None is the handle's for every instance), the
     handle's scene is left alone, and the backward (tt_obca_vjp_scenes_device) returns the rows as they are, (B,M,4)
-    and (B,), each instance's gradient in its own scene.  The two forms do not mix in one call."""
+    and (B,), each instance's gradient in its own scene.  The two forms do not mix in one call.
+
+    geometry (float64 (5,) = (L1, L2, M, W1, W2), CPU or device), if given, makes the handle's geometry an input, the
+    pattern of ``TrackingSolveFunction``'s ``model``: the forward applies it with ``solver.set_geometry`` when it
+    differs from the handle's, and it stays applied; the backward runs the adjoint kernel's geometry instantiation
+    (tt_obca_vjp_geometry_device) and returns the per-instance rows summed over B on the tensor's device.  It raises if
+    the handle's geometry was changed between the forward and the backward."""
 
     @staticmethod
-    def forward(ctx, solver, x0, xref, uref, obstacles=None, d_min=None):
+    def forward(ctx, solver, x0, xref, uref, obstacles=None, d_min=None, geometry=None):
+        ctx.geom = None
+        if geometry is not None:
+            vals = _host_vector("geometry", geometry, _OBCA_GEOMETRY)
+            if vals != solver.geometry():
+                solver.set_geometry(*vals)
+            ctx.geom, ctx.geom_like = solver.geometry(), geometry.device
         ctx.scene = None
+        ctx.like = (None, None)
         ctx.rows = (torch.is_tensor(obstacles) and obstacles.dim() == 3) or (torch.is_tensor(d_min) and d_min.dim() == 1)
         if ctx.rows:
             B, dev = x0.shape[0], x0.device
@@ -225,7 +239,9 @@ class ObcaTrackingSolveFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_X, grad_U, _grad_status):
-        need = ctx.needs_input_grad  # (solver, x0, xref, uref[, obstacles, d_min])
+        need = ctx.needs_input_grad  # (solver, x0, xref, uref[, obstacles, d_min[, geometry]])
+        if ctx.geom is not None and ctx.solver.geometry() != ctx.geom:
+            raise RuntimeError("the solver's geometry changed since the forward")
         if ctx.scene is not None:
             ob, dm = ctx.solver.scene()
             if not (ob == ctx.scene[0]).all() or dm != ctx.scene[1]:
@@ -240,35 +256,39 @@ class ObcaTrackingSolveFunction(torch.autograd.Function):
         g_x0 = new(B, 6) if need[1] else None
         g_xref = new(B, N + 1, 6) if need[2] else None
         g_uref = new(B, N, 2) if need[3] else None
-        if ctx.scene is not None:
+        if ctx.scene is not None or ctx.geom is not None:
             g_ob = new(B, ctx.solver.M, 4) if len(need) > 4 and need[4] else None
             g_dm = new(B) if len(need) > 5 and need[5] else None
+            g_ge = new(B, 5) if len(need) > 6 and need[6] else None
             work = torch.empty((B * ctx.solver.vjp_params_work_bytes() // 8,), dtype=torch.float64, device=dev)
             rows = dict(obstacles=_ptr(ctx.scenes[0]), d_min=_ptr(ctx.scenes[1])) if ctx.rows else {}
             ctx.solver.vjp_device(B, iterate.data_ptr(), status.data_ptr(), grad_x=_ptr(gX), grad_u=_ptr(gU),
                                   g_x0=_ptr(g_x0), g_xref=_ptr(g_xref), g_uref=_ptr(g_uref), g_obstacles=_ptr(g_ob),
-                                  g_dmin=_ptr(g_dm), work=work.data_ptr(),
+                                  g_dmin=_ptr(g_dm), work=work.data_ptr(), g_geometry=_ptr(g_ge),
                                   stream=torch.cuda.current_stream(dev).cuda_stream, **rows)
+            g_ge = None if g_ge is None else _batch_sum(g_ge, ctx.geom_like)  # (one geometry for the batch)
             if ctx.rows:  # each instance's gradient in its own scene: nothing to sum
                 return (None, g_x0, g_xref, g_uref, None if g_ob is None else g_ob.to(ctx.like[0]),
-                        None if g_dm is None else g_dm.to(ctx.like[1]))[:len(need)]
+                        None if g_dm is None else g_dm.to(ctx.like[1]), g_ge)[:len(need)]
             return (None, g_x0, g_xref, g_uref, None if g_ob is None else _batch_sum(g_ob, ctx.like[0]),
-                    None if g_dm is None else _batch_sum(g_dm, ctx.like[1]))[:len(need)]
+                    None if g_dm is None else _batch_sum(g_dm, ctx.like[1]), g_ge)[:len(need)]
         ctx.solver.vjp_device(B, iterate.data_ptr(), status.data_ptr(), grad_x=_ptr(gX), grad_u=_ptr(gU),
                               g_x0=_ptr(g_x0), g_xref=_ptr(g_xref), g_uref=_ptr(g_uref),
                               stream=torch.cuda.current_stream(dev).cuda_stream)
-        return (None, g_x0, g_xref, g_uref, None, None)[:len(need)]
+        return (None, g_x0, g_xref, g_uref, None, None, None)[:len(need)]
 
 
 class DifferentiableObcaTracking:
-    """``X, U, status = layer(x0, xref, uref, obstacles=None, d_min=None)`` with float64 CUDA tensors: a thin callable
+    """``X, U, status = layer(x0, xref, uref, obstacles=None, d_min=None, geometry=None)`` with float64 CUDA tensors: a thin callable
     over ``ObcaTrackingSolveFunction`` for one ``ObcaSolver`` of TT_VARIANT_TRACK_OBCA.  The forward uses the handle's
     solver workspace (one stream per handle); the backward uses no buffer of the handle.  Failed instances give zeros.
     With ``obstacles`` (float64 (M,4)) and / or ``d_min`` (float64 ()), CPU or device, the handle's scene is an input
     too: ``obstacles.grad`` and ``d_min.grad`` are the batch sums of tt_obca_vjp_params_device's rows.  With
     ``obstacles`` of shape (B,M,4) and / or ``d_min`` of shape (B,) every instance has its own scene and ``.grad`` has
     those shapes: row b is instance b's gradient in its own scene (tt_obca_vjp_scenes_device).  Q and R are not
-    inputs (there is no setter for them); ``ObcaSolver.vjp(..., params=True)`` returns their gradients."""
+    inputs (there is no setter for them); ``ObcaSolver.vjp(..., params=True)`` returns their gradients.  With
+    ``geometry`` (float64 (5,) = (L1, L2, M, W1, W2), CPU or device) the handle's geometry is an input:
+    ``geometry.grad`` is the batch sum of tt_obca_vjp_geometry_device's rows."""
 
     def __init__(self, solver):
         from ._lib import TT_VARIANT_TRACK_OBCA
@@ -276,8 +296,8 @@ class DifferentiableObcaTracking:
             raise TypeError("DifferentiableObcaTracking needs an ObcaSolver of TT_VARIANT_TRACK_OBCA")
         self.solver = solver
 
-    def __call__(self, x0, xref, uref, obstacles=None, d_min=None):
-        return ObcaTrackingSolveFunction.apply(self.solver, x0, xref, uref, obstacles, d_min)
+    def __call__(self, x0, xref, uref, obstacles=None, d_min=None, geometry=None):
+        return ObcaTrackingSolveFunction.apply(self.solver, x0, xref, uref, obstacles, d_min, geometry)
 
 
 class ClosedLoopFunction(torch.autograd.Function):

@@ -313,9 +313,11 @@ class LoopTape:
     ``FuzzyRule`` also keeps rule (that rule), W (K,B,8), the weights each step's accepted solve used (ones where the
     unit-weight retry was taken), and retried (K,B) int32, where it was: 68 bytes per instance and step.  The taped run
     of a switch loop (``switch_adjoint=True``) keeps switched: per step None, or (idx (n,) int64, the flagged instances;
-    iterate (n, tt_obca_iterate_len), the MPC+OBCA solve's exported iterates of those instances; status (n,) int32)."""
+    iterate (n, tt_obca_iterate_len), the MPC+OBCA solve's exported iterates of those instances; status (n,) int32),
+    and geometry_switch, the (L1, L2, M, W1, W2) of the switch solver's handle during the run."""
     __slots__ = ("ks", "S", "Ua", "status", "iters", "collide", "active", "consec", "X", "U", "dual", "noise", "wq_wr",
-                 "plan_x", "plan_u", "model_solver", "model_plant", "W", "retried", "rule", "switched")
+                 "plan_x", "plan_u", "model_solver", "model_plant", "W", "retried", "rule", "switched",
+                 "geometry_switch")
     # (log field, the loop's buffer a step leaves it in), in the order record() copies them; the solve writes dual
     STEP = (("S", "state"), ("Ua", "u_applied"), ("status", "st"), ("iters", "it"), ("collide", "flag"),
             ("active", "active"), ("consec", "consec"), ("X", "X"), ("U", "U"), ("W", "wq"), ("retried", "retried"))
@@ -337,6 +339,8 @@ class LoopTape:
             log.consec = new(K, B, dtype=torch.int32)
             log.X, log.U, log.dual = new(K, B, N + 1, 6), new(K, B, N, 2), new(K, B, N + 1, 22)
             log.model_solver, log.model_plant = loop.solver.model(), loop.plant_model()   # (run_tape: a BatchSolver)
+            if loop.switch is not None and loop.switch_adjoint:
+                log.geometry_switch = loop.switch.geometry()
             if loop.rule is not None:
                 log.W, log.retried, log.rule = new(K, B, 8), new(K, B, dtype=torch.int32), loop.rule
         return log
@@ -833,7 +837,7 @@ class ClosedLoop:
         torch.cuda.synchronize(self.dev)
         return dict(self._policy_logs(), **tape.result(), tape=tape)
 
-    def backward(self, tape, GS, GU, model=False, rule=False, scene=False):
+    def backward(self, tape, GS, GU, model=False, rule=False, scene=False, geometry=False):
         """The adjoint of a taped run for a scalar loss L(S, Ua): GS = dL/dS (K+1,B,6), GU = dL/dUa (K,B,2), float64
         device tensors.  Per step, backwards: tt_policy_plant_vjp_device, the step's window again,
         tt_track_vjp_device on the taped solve, tt_sim_window_vjp_device (include/ttmpc.h, "Reverse mode of the closed
@@ -855,8 +859,8 @@ class ClosedLoop:
         in which the switched instances carry TT_MAX_ITER, so it writes zeros for them (and nothing into g_wq_wr);
         tt_obca_vjp_device then runs on the taped iterates of the compacted set with the gathered dL/dU, and its g_x0,
         g_xref, g_uref take those rows before the window adjoint.  The compaction sizes are the tape's: no host
-        synchronisation.  model=True and rule=True raise on such a loop (the OBCA adjoint has no geometry or rule
-        gradient).
+        synchronisation.  model=True and rule=True raise on such a loop (it has three geometries: geometry=True below
+        returns them; the rule's adjoint is not carried through the switch solve).
         scene=True (a switch loop with ``switch_adjoint=True`` only, else it raises) adds g_obstacles (B,M,4) and g_dmin
         (B,): dL/d(cx, cy, w, h) and dL/dd_min of the switch solver's scene per instance, accumulated over the switched
         instance-steps from the same compacted adjoint call, which is then tt_obca_vjp_params_device (its g_x0, g_xref,
@@ -864,10 +868,20 @@ class ClosedLoop:
         collision switch itself is piecewise constant in the scene and contributes nothing: the gradient holds while no
         flag changes.  No host synchronisation is added.  With per-instance scenes (``ClosedLoop(obstacles=(B,M,4))`` and
         / or ``d_min=``) the compacted adjoint gets the rows its solve got, and g_obstacles / g_dmin are each instance's
-        gradient in its own scene."""
+        gradient in its own scene.
+        geometry=True (a switch loop with ``switch_adjoint=True`` only, else it raises) adds g_geometry_switch (B,5):
+        dL/d(L1, L2, M, W1, W2) of the switch solver's geometry per instance, accumulated over the switched
+        instance-steps from the same compacted adjoint call (then tt_obca_vjp_geometry_device), and g_model_solver and
+        g_model_plant (B,3) of the tracking solver's and the plant's (L1, L2, M) as model=True forms them on a loop
+        without a switch; the switched instances, masked in the tracking adjoint, add nothing to g_model_solver.  The
+        three geometries are separate inputs: a loop that shares one sums them.  The switch solver's geometry must still
+        be the run's.  The collision switch is piecewise constant in the geometry too.  No host synchronisation is
+        added."""
         self._check_differentiable()
         if scene and (self.switch is None or not self.switch_adjoint):
             raise ValueError("scene=True needs a switch loop: ClosedLoop(..., switch_solver=..., switch_adjoint=True)")
+        if geometry and (self.switch is None or not self.switch_adjoint):
+            raise ValueError("geometry=True needs a switch loop: ClosedLoop(..., switch_solver=..., switch_adjoint=True)")
         if self.switch is not None and (model or rule):
             raise ValueError("a switch (OBCA) loop has no model=True or rule=True gradient: the OBCA adjoint "
                              "(switch_adjoint) gives dL/d(x_init, xref, uref) only")
@@ -881,6 +895,11 @@ class ClosedLoop:
             raise ValueError(f"the geometry changed since the tape was made: solver {tape.model_solver} -> "
                              f"{self.solver.model()}, plant {tape.model_plant} -> {self.plant_model()}; run the tape "
                              "again, or set the geometry back before the backward")
+        if tape.geometry_switch is not None and tape.geometry_switch != self.switch.geometry():
+            raise ValueError(f"the switch solver's geometry changed since the tape was made: {tape.geometry_switch} -> "
+                             f"{self.switch.geometry()}; run the tape again, or set the geometry back before the "
+                             "backward")
+        mdl = model or geometry   # (the model instantiations of the plant and tracking adjoints)
         s, d, N = self.stream, self.dev, self.N
         K, B = tape.status.shape
         Np = tape.plan_u.shape[-2]
@@ -892,12 +911,13 @@ class ClosedLoop:
         g_w, g_px, g_pu, g_n = z(B, 8), z(B, Np + 1, 6), z(B, Np, 2), z(K, B, 6)
         xref, uref = z(B, N + 1, 6), z(B, N, 2)
         g_x0, g_xr, g_ur, g_ws = z(B, 6), z(B, N + 1, 6), z(B, N, 2), z(B, 8)
-        g_ms, g_mp = (z(B, 3), z(B, 3)) if model else (None, None)
+        g_ms, g_mp = (z(B, 3), z(B, 3)) if mdl else (None, None)
         fz = tape.rule is not None
         g_th = z(B, 7) if rule else None
         x_meas = z(B, 6) if fz else None
         g_ob, g_dm = (z(B, self.switch.M, 4), z(B)) if scene else (None, None)
-        wbytes = self.switch.vjp_params_work_bytes() if scene else 0
+        g_ge = z(B, 5) if geometry else None
+        wbytes = self.switch.vjp_params_work_bytes() if scene or geometry else 0
         rs = _rule_ref(tape.rule)
         in_plant = self.noise_in_plant and tape.noise is not None
         meas = self.measurement_noise and tape.noise is not None
@@ -910,9 +930,9 @@ class ClosedLoop:
         # calls the form it needs (marshalling the wider argument lists costs about 1.5 us per step, which the plain
         # loop must not pay).  at(t): what a rule loop adds per step, ((state, noise) of the window launch that rebuilds
         # x_meas, the weights the solve used, the tail of the window adjoint).
-        plant_vjp, plant_tail = ((L.tt_policy_plant_vjp_model_device, (g_mp.data_ptr(), sp)) if model else
+        plant_vjp, plant_tail = ((L.tt_policy_plant_vjp_model_device, (g_mp.data_ptr(), sp)) if mdl else
                                  (L.tt_policy_plant_vjp_device, (sp,)))
-        g_model = g_ms.data_ptr() if model else 0
+        g_model = g_ms.data_ptr() if mdl else 0
         if fz:
             # the rule's four extra per-step addresses by offset: a tape slice made on the host costs it more than the
             # launch it feeds, and the host only just keeps ahead of a backward step
@@ -959,15 +979,19 @@ class ClosedLoop:
                     ob_c, dm_c = self._scene_rows(idx) if self.per_scene or self.d_min is not None else (None, None)
                     rows = (dict(obstacles=_ptr(ob_c) or 0, d_min=_ptr(dm_c) or 0)
                             if ob_c is not None or dm_c is not None else {})
-                    if scene:  # (idx has no repeats: the indexed += is one add per row)
-                        oob, odm = z(n, self.switch.M, 4), z(n)
+                    if scene or geometry:  # (idx has no repeats: the indexed += is one add per row)
+                        oob, odm = (z(n, self.switch.M, 4), z(n)) if scene else (None, None)
+                        oge = z(n, 5) if geometry else None
                         work = torch.empty((n * wbytes // 8,), dtype=torch.float64, device=d)
                         self.switch.vjp_device(n, it_c.data_ptr(), st_c.data_ptr(), grad_u=gu_c.data_ptr(),
                                                g_x0=o0.data_ptr(), g_xref=oxr.data_ptr(), g_uref=our.data_ptr(),
-                                               g_obstacles=oob.data_ptr(), g_dmin=odm.data_ptr(), work=work.data_ptr(),
-                                               stream=s.cuda_stream, **rows)
-                        g_ob[idx] += oob
-                        g_dm[idx] += odm
+                                               g_obstacles=_ptr(oob) or 0, g_dmin=_ptr(odm) or 0, work=work.data_ptr(),
+                                               g_geometry=_ptr(oge) or 0, stream=s.cuda_stream, **rows)
+                        if scene:
+                            g_ob[idx] += oob
+                            g_dm[idx] += odm
+                        if geometry:
+                            g_ge[idx] += oge
                     else:
                         self.switch.vjp_device(n, it_c.data_ptr(), st_c.data_ptr(), grad_u=gu_c.data_ptr(),
                                                g_x0=o0.data_ptr(), g_xref=oxr.data_ptr(), g_uref=our.data_ptr(),
@@ -981,8 +1005,10 @@ class ClosedLoop:
                 g_px, g_pu = g_px.sum(dim=0, keepdim=True), g_pu.sum(dim=0, keepdim=True)
         torch.cuda.current_stream(d).wait_stream(s)
         out = {"g_x_init": a, "g_wq_wr": g_w, "g_plan_x": g_px, "g_plan_u": g_pu, "g_noise": g_n}
-        if model:
+        if mdl:
             out.update(g_model_solver=g_ms, g_model_plant=g_mp)
+        if geometry:
+            out["g_geometry_switch"] = g_ge
         if rule:
             out["g_fuzzy_rule"] = g_th
         if scene:

@@ -295,7 +295,7 @@ int tt_obca_solve_batch_iterate_device(void* handle, int B, const double* d_x0, 
  *   and a variable sitting on a bound carries (numerically) zero lam.
  *   Only TT_VARIANT_TRACK_OBCA: a plan handle and a tracking handle return -EINVAL.  Gradients with respect to the
  *   obstacles, d_min, Q and R come from tt_obca_vjp_params* below; those with respect to the geometry (L1, L2, M, W1,
- *   W2) are not formed.  The horizon must keep the instance's record in 64 KB of LDS
+ *   W2) from tt_obca_vjp_geometry*.  The horizon must keep the instance's record in 64 KB of LDS
  *   (N <= 76), else -EINVAL.
  *
  * tt_obca_vjp_device: device pointers (inside the host-side struct too), asynchronous on `stream`.  It uses no buffer
@@ -383,6 +383,43 @@ int tt_obca_vjp_scenes_device(void* handle, int B, const double* d_iterate, cons
                               const double* d_uref, const double* d_grad_x, const double* d_grad_u,
                               const tt_obca_vjp_params_out* d_out, void* d_work, const tt_obca_scenes* d_scenes,
                               void* stream);
+
+/* The same adjoint plus the gradient with respect to the geometry the batch shares (tt_obca_vjp_geometry_out: the
+ * eight members of tt_obca_vjp_params_out, then g_geometry):
+ *     g_geometry [B][5]  dL/d(L1, L2, Mh, W1, W2) per instance, at the handle's current geometry; the sum over B is
+ *                        the caller's
+ *   dL/dtheta = -lam' dF/dtheta at the exported iterate.  Two parts of F depend on theta.  The dynamics rows and the
+ *   -A_k' y_{k+1} part of the x-stationarity rows (L1, L2, Mh): tt_track_vjp_model's sum
+ *   dt sum_{k<N} [lam_x,k' (dJ_f/dtheta)' y_{k+1} + lam_y,k+1' df/dtheta] with this solve's lam.  And of every block
+ *   (stage k >= 1, obstacle m, body) the d_min row d_0, through g = (L/2, W/2, L/2, W/2) and through the body centre
+ *   p (truck: rear axle + L1/2 along the heading; trailer: rear axle - Mh along the heading - L2/2 along the trailer);
+ *   with l_b = y_d0 d_0 and v the block's 16 entries of lam its share is
+ *   -[(lam_pose, v_w)' d/dtheta grad_(pose, w) l_b + v_yd0 dd_0/dtheta]; truck blocks feed L1 and W1, trailer blocks
+ *   L2, Mh and W2.  The block terms are read from the carried v (d_work, as tt_obca_vjp_params).
+ *   With g_geometry NULL the calls are tt_obca_vjp_scenes / _device: the same kernel, the same bits.  With it set the
+ *   other eight outputs are bitwise what tt_obca_vjp_scenes* writes with a work buffer, and d_work is needed (NULL:
+ *   -EINVAL).  Failed or skipped instances get zeros.  Only TT_VARIANT_TRACK_OBCA, N <= 76.
+ * tt_obca_vjp_geometry_device uses no buffer of the handle; tt_obca_vjp_geometry stages through the handle (its work
+ * buffer included), synchronous. */
+typedef struct { double* g_x0; double* g_xref; double* g_uref; int* vjp_status;
+                 double* g_obstacles; double* g_dmin; double* g_Q; double* g_R;
+                 double* g_geometry; /* [B][5] dL/d(L1, L2, Mh, W1, W2) per instance */ } tt_obca_vjp_geometry_out;
+int tt_obca_vjp_geometry_device(void* handle, int B, const double* d_iterate, const int* d_status,
+                                const double* d_xref, const double* d_uref, const double* d_grad_x,
+                                const double* d_grad_u, const tt_obca_vjp_geometry_out* d_out, void* d_work,
+                                const tt_obca_scenes* d_scenes /* NULL: the handle's */, void* stream);
+int tt_obca_vjp_geometry(void* handle, int B, const double* iterate, const int* status, const double* xref,
+                         const double* uref, const double* grad_x, const double* grad_u,
+                         const tt_obca_vjp_geometry_out* out, const tt_obca_scenes* scenes);
+
+/* The geometry of an OBCA handle (both variants) without rebuilding it: the lengths L1, L2, the hitch offset Mh and
+ * the widths W1, W2, which are the dynamics' parameters and the H-representations of the two bodies.  tt_create's
+ * validation: L1, L2, W1, W2 finite and > 0, Mh finite, else -EINVAL and nothing is changed.  Host-side state only:
+ * every later solve and adjoint of the handle is bitwise that of a fresh handle created with these values; work already
+ * enqueued keeps the old ones.  A tracking handle: -EINVAL (it has tt_set_model, which keeps refusing OBCA handles).
+ * tt_get_geometry: any pointer may be NULL. */
+int tt_set_geometry(void* handle, double L1, double L2, double Mh, double W1, double W2);
+int tt_get_geometry(void* handle, double* L1, double* L2, double* Mh, double* W1, double* W2);
 
 /* ---------------------------------------------------------------------------------------------
  * Closed-loop simulation step, device pointers, asynchronous on `stream`.

@@ -7,7 +7,11 @@ tests/obca_vjp_reference.py (N = 6, M = 1).  Solve, adjoint and params adjoint a
 tools/time_vjp.py does; the line per shape gives the median of each and the ratios adjoint / solve, params / adjoint
 and params / solve.
 
-    python tools/time_obca_vjp.py [--rounds 5]
+    python tools/time_obca_vjp.py [--rounds 5] [--geometry]
+
+--geometry also times the geometry entry (tt_obca_vjp_geometry_device: the params outputs plus dL/d(L1, L2, Mh, W1, W2))
+in the same alternation and adds geometry_ms and geometry_over_params to the line.  A library without the entry
+(TTMPC_LIB pointing at an older build) is timed without it, so the same command measures both sides of a comparison.
 """
 import argparse
 import json
@@ -40,6 +44,7 @@ def main():
     from ttmpc import scenarios as sc
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--geometry", action="store_true", help="also time tt_obca_vjp_geometry_device")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     for name, N, p, bnd, obs, x0, xr, ur in shapes():
@@ -57,6 +62,8 @@ def main():
         vp = torch.empty(B, dtype=torch.int32, device=dev)
         gob, gdm, gQ, gR = new(B, s.M, 4), new(B), new(B, 6, 6), new(B, 2, 2)
         work = new(B * s.vjp_params_work_bytes() // 8)
+        geo = a.geometry and hasattr(s._L, "tt_obca_vjp_geometry_device")
+        gge, vg = new(B, 5), torch.empty(B, dtype=torch.int32, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
 
         def solve():
@@ -73,6 +80,12 @@ def main():
                          xref=dxr.data_ptr(), uref=dur.data_ptr(), g_obstacles=gob.data_ptr(), g_dmin=gdm.data_ptr(),
                          g_Q=gQ.data_ptr(), g_R=gR.data_ptr(), work=work.data_ptr())
 
+        def geometry():
+            s.vjp_device(B, I.data_ptr(), st.data_ptr(), grad_x=gX.data_ptr(), grad_u=gU.data_ptr(), g_x0=g0.data_ptr(),
+                         g_xref=gr.data_ptr(), g_uref=gu.data_ptr(), vjp_status=vg.data_ptr(), stream=stream,
+                         xref=dxr.data_ptr(), uref=dur.data_ptr(), g_obstacles=gob.data_ptr(), g_dmin=gdm.data_ptr(),
+                         g_Q=gQ.data_ptr(), g_R=gR.data_ptr(), work=work.data_ptr(), g_geometry=gge.data_ptr())
+
         def timed(fn):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -84,19 +97,28 @@ def main():
         solve()
         adjoint()
         params()
+        if geo:
+            geometry()
         torch.cuda.synchronize(dev)
-        ts, ta, tp = [], [], []
+        ts, ta, tp, tg = [], [], [], []
         for _ in range(a.rounds):
             ts.append(timed(solve))
             ta.append(timed(adjoint))
             tp.append(timed(params))
+            if geo:
+                tg.append(timed(geometry))
         ms, ma, mp = float(np.median(ts)), float(np.median(ta)), float(np.median(tp))
+        extra = {}
+        if geo:
+            mg = float(np.median(tg))
+            extra = {"geometry_ms": round(mg, 4), "geometry_over_params": round(mg / mp, 4),
+                     "geometry_ok": int((vg == 0).sum().item())}
         print(json.dumps({"shape": name, "solve_ms": round(ms, 3), "adjoint_ms": round(ma, 4),
                           "adjoint_over_solve": round(ma / ms, 5), "params_ms": round(mp, 4),
                           "params_over_adjoint": round(mp / ma, 4), "params_over_solve": round(mp / ms, 5),
                           "solved": int((st <= 1).sum().item()), "adjoint_ok": int((vs == 0).sum().item()),
                           "params_ok": int((vp == 0).sum().item()), "work_mb": round(work.numel() * 8 / 2**20, 2),
-                          "rounds": a.rounds}))
+                          "rounds": a.rounds, **extra}))
 
 
 if __name__ == "__main__":
