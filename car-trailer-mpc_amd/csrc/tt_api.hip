@@ -226,6 +226,13 @@ const tt_track_vjp_model_out* widen(const tt_track_vjp_out* out, tt_track_vjp_mo
     return &o;
 }
 
+// tt_track_vjp_model_out as the bounds entries take it, in o: no g_bounds.  NULL stays NULL (theirs to refuse).
+const tt_track_vjp_bounds_out* widen(const tt_track_vjp_model_out* out, tt_track_vjp_bounds_out& o) {
+    if (!out) return nullptr;
+    o = {out->g_x0, out->g_xref, out->g_uref, out->g_wq_wr, out->g_model, nullptr, out->vjp_status};
+    return &o;
+}
+
 // ---------------- the zero-copy mirror of tracking host calls ----------------
 void free_stage(Handle* h) {
     if (h->d_sin) (void)hipFree(h->d_sin);
@@ -631,10 +638,10 @@ int tt_track_sens_device(void* handle, int B, const double* d_x, const double* d
     return sens_launch(h, B, d_x, d_u, d_dual, d_wq_wr, d_status, x, stream);
 }
 
-int tt_track_vjp_model_device(void* handle, int B, const double* d_x, const double* d_u, const double* d_dual,
-                              const double* d_xref, const double* d_uref, const double* d_wq_wr, const int* d_status,
-                              const double* d_grad_x, const double* d_grad_u, const tt_track_vjp_model_out* d_out,
-                              int accumulate, void* stream) {
+int tt_track_vjp_bounds_device(void* handle, int B, const double* d_x, const double* d_u, const double* d_dual,
+                               const double* d_xref, const double* d_uref, const double* d_wq_wr, const int* d_status,
+                               const double* d_grad_x, const double* d_grad_u, const tt_track_vjp_bounds_out* d_out,
+                               int accumulate, void* stream) {
     Handle* h = static_cast<Handle*>(handle);
     if (const int rc = prelude(h, B, kHandle | kTrackOnly | kSign)) return rc;
     if (!d_grad_x && !d_grad_u) return fail(h, -EINVAL, "grad_x and grad_u are both NULL: no loss to differentiate%s");
@@ -645,7 +652,7 @@ int tt_track_vjp_model_device(void* handle, int B, const double* d_x, const doub
     if (const int rc = prelude(h, B, kFuzzy, d_wq_wr)) return rc;
     DeviceGuard dg(h->device);
     if (dg.err != hipSuccess) return hip_fail(h, dg.err, "hipSetDevice");
-    ttmpc::VjpModelArgs a = diff_args<ttmpc::VjpModelArgs>(h, B, d_x, d_u, d_dual, d_wq_wr, d_status);
+    ttmpc::VjpBoundsArgs a = diff_args<ttmpc::VjpBoundsArgs>(h, B, d_x, d_u, d_dual, d_wq_wr, d_status);
     a.xref = d_xref;
     a.uref = d_uref;
     a.gx = d_grad_x;
@@ -657,11 +664,23 @@ int tt_track_vjp_model_device(void* handle, int B, const double* d_x, const doub
     a.vjp_status = d_out->vjp_status;
     a.g_model = d_out->g_model;
     a.accumulate = accumulate != 0;
-    // without g_model the plain instantiation, on the VjpArgs head of the same block
-    const hipError_t e = a.g_model ? ttmpc::launch_track_vjp_model(a, static_cast<hipStream_t>(stream))
-                                   : ttmpc::launch_track_vjp(a, static_cast<hipStream_t>(stream));
+    a.g_bounds = d_out->g_bounds;
+    // without g_bounds the model instantiation, without g_model either the plain one: on the VjpModelArgs / VjpArgs
+    // head of the same block
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const hipError_t e = a.g_bounds ? ttmpc::launch_track_vjp_bounds(a, s)
+                         : a.g_model ? ttmpc::launch_track_vjp_model(a, s) : ttmpc::launch_track_vjp(a, s);
     if (e != hipSuccess) return hip_fail(h, e, "adjoint kernel launch");
     return 0;
+}
+
+int tt_track_vjp_model_device(void* handle, int B, const double* d_x, const double* d_u, const double* d_dual,
+                              const double* d_xref, const double* d_uref, const double* d_wq_wr, const int* d_status,
+                              const double* d_grad_x, const double* d_grad_u, const tt_track_vjp_model_out* d_out,
+                              int accumulate, void* stream) {
+    tt_track_vjp_bounds_out o;
+    return tt_track_vjp_bounds_device(handle, B, d_x, d_u, d_dual, d_xref, d_uref, d_wq_wr, d_status, d_grad_x,
+                                      d_grad_u, widen(d_out, o), accumulate, stream);
 }
 
 int tt_track_vjp_device(void* handle, int B, const double* d_x, const double* d_u, const double* d_dual,
@@ -672,9 +691,9 @@ int tt_track_vjp_device(void* handle, int B, const double* d_x, const double* d_
                                      d_grad_u, widen(d_out, o), 0, stream);
 }
 
-int tt_track_vjp_model(void* handle, int B, const double* x, const double* u, const double* dual, const double* xref,
-                       const double* uref, const double* wq_wr, const int* status, const double* grad_x,
-                       const double* grad_u, const tt_track_vjp_model_out* out, int accumulate) {
+int tt_track_vjp_bounds(void* handle, int B, const double* x, const double* u, const double* dual, const double* xref,
+                        const double* uref, const double* wq_wr, const int* status, const double* grad_x,
+                        const double* grad_u, const tt_track_vjp_bounds_out* out, int accumulate) {
     Handle* h = static_cast<Handle*>(handle);
     if (const int rc = prelude(h, B, kHandle | kTrackOnly | kSign)) return rc;
     if (!grad_x && !grad_u) return fail(h, -EINVAL, "grad_x and grad_u are both NULL: no loss to differentiate%s");
@@ -686,7 +705,7 @@ int tt_track_vjp_model(void* handle, int B, const double* x, const double* u, co
     Stager st;
     const double *d_x, *d_u, *d_dual, *d_xref, *d_uref, *d_w, *d_gx, *d_gu;
     const int* d_st;
-    tt_track_vjp_model_out dout;
+    tt_track_vjp_bounds_out dout;
     st.in(x, nx, &d_x);
     st.in(u, nu, &d_u);
     st.in(dual, b * (N + 1) * ttmpc::kDualPerStage, &d_dual);
@@ -701,16 +720,27 @@ int tt_track_vjp_model(void* handle, int B, const double* x, const double* u, co
     st.out(out->g_uref, nu, &dout.g_uref);
     st.out(out->g_wq_wr, b * 8, &dout.g_wq_wr);
     st.out(out->vjp_status, b, &dout.vjp_status);
-    if (accumulate)
+    if (accumulate) {
         st.inout(out->g_model, b * 3, &dout.g_model);
-    else
+        st.inout(out->g_bounds, b * 16, &dout.g_bounds);
+    } else {
         st.out(out->g_model, b * 3, &dout.g_model);
+        st.out(out->g_bounds, b * 16, &dout.g_bounds);
+    }
     if (!st.carve(h->xfer)) return no_memory(h, "adjoint staging");
     hipStream_t s = h->stream;
     return st.run(h, s, "adjoint", [&] {
-        return tt_track_vjp_model_device(handle, B, d_x, d_u, d_dual, d_xref, d_uref, d_w, d_st, d_gx, d_gu, &dout,
-                                         accumulate, s);
+        return tt_track_vjp_bounds_device(handle, B, d_x, d_u, d_dual, d_xref, d_uref, d_w, d_st, d_gx, d_gu, &dout,
+                                          accumulate, s);
     });
+}
+
+int tt_track_vjp_model(void* handle, int B, const double* x, const double* u, const double* dual, const double* xref,
+                       const double* uref, const double* wq_wr, const int* status, const double* grad_x,
+                       const double* grad_u, const tt_track_vjp_model_out* out, int accumulate) {
+    tt_track_vjp_bounds_out o;
+    return tt_track_vjp_bounds(handle, B, x, u, dual, xref, uref, wq_wr, status, grad_x, grad_u, widen(out, o),
+                               accumulate);
 }
 
 int tt_track_vjp(void* handle, int B, const double* x, const double* u, const double* dual, const double* xref,
@@ -740,6 +770,37 @@ int tt_get_model(void* handle, double* L1, double* L2, double* Mh) {
     if (L1) *L1 = h->cfg.L1;
     if (L2) *L2 = h->cfg.L2;
     if (Mh) *Mh = h->cfg.Mh;
+    return 0;
+}
+
+int tt_set_bounds(void* handle, const double* xlb, const double* xub, const double* ulb, const double* uub) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (!h) return fail(nullptr, -EINVAL, "NULL handle%s");
+    if (is_obca(h->cfg))
+        return fail(h, -EINVAL, "tt_set_bounds changes the box of a tracking handle; an OBCA handle keeps the box it was "
+                                "created with%s");
+    if (!xlb || !xub || !ulb || !uub) return fail(h, -EINVAL, "NULL argument%s");
+    for (int i = 0; i < 6; ++i)  // (a NaN fails the comparison, as in tt_create)
+        if (!(xlb[i] <= xub[i])) return fail(h, -EINVAL, "state bound lb > ub%s");
+    for (int i = 0; i < 2; ++i)
+        if (!(ulb[i] <= uub[i])) return fail(h, -EINVAL, "input bound lb > ub%s");
+    // every launch path copies the box into its kernel arguments (fill_model) and launch_track picks its build from
+    // the bound pattern of those arguments: nothing on the device, and no choice made at tt_create, holds the old box
+    memcpy(h->xlb, xlb, sizeof h->xlb);
+    memcpy(h->xub, xub, sizeof h->xub);
+    memcpy(h->ulb, ulb, sizeof h->ulb);
+    memcpy(h->uub, uub, sizeof h->uub);
+    return 0;
+}
+
+int tt_get_bounds(void* handle, double* xlb, double* xub, double* ulb, double* uub) {
+    Handle* h = static_cast<Handle*>(handle);
+    if (!h) return fail(nullptr, -EINVAL, "NULL handle%s");
+    if (is_obca(h->cfg)) return fail(h, -EINVAL, "tt_get_bounds reads the box of a tracking handle%s");
+    if (xlb) memcpy(xlb, h->xlb, sizeof h->xlb);
+    if (xub) memcpy(xub, h->xub, sizeof h->xub);
+    if (ulb) memcpy(ulb, h->ulb, sizeof h->ulb);
+    if (uub) memcpy(uub, h->uub, sizeof h->uub);
     return 0;
 }
 

@@ -113,6 +113,14 @@ struct VjpModelArgs : VjpArgs {
     int accumulate;       // != 0: g_model[b] += (a failed instance adds nothing); 0: g_model[b] = (zeros if failed)
 };
 hipError_t launch_track_vjp_model(const VjpModelArgs& a, hipStream_t stream);
+// the same adjoint plus dL/d(xlb, xub, ulb, uub): the kernel's bounds instantiations (the same LDS record; with
+// g_model also set, the model and the bounds gradient of one launch).  The member sits behind VjpModelArgs so that the
+// plain and the model instantiations' argument blocks, and with them their code, stay what they were
+struct VjpBoundsArgs : VjpModelArgs {
+    double* g_bounds;     // [B][16]: lower bounds of (x 6, u 2), then upper bounds; never nullptr here.  g_model may
+                          //  be nullptr (then the bounds gradient alone); `accumulate` concerns both
+};
+hipError_t launch_track_vjp_bounds(const VjpBoundsArgs& a, hipStream_t stream);
 
 }  // namespace ttmpc
 

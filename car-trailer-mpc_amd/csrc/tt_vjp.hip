@@ -25,7 +25,16 @@
 // and lam_y comes from the x-rows of K, one more six-lane sweep (model_gradient below): ly_N = gX_N - H_N lx_N,
 // ly_k = gX_k - H_k lx_k + A_k' ly_{k+1}, H_k = W_k + Sigma_x,k.  ly overlays gX, so the LDS record is the same; the
 // plain instantiation's code is what it was.  tests/model_vjp_reference.py is the numpy model.
+//
+// The bounds instantiations (tt_track_vjp_bounds_device, kBounds, with or without kModel) add the gradient in the box
+// (xlb, xub, ulb, uub).  The bounds enter F only through z_L = mu / (v - l_rel) and z_U = mu / (u_rel - v), so
+//   dL/dl_v = rho_l sum_k Sigma_L,k,v lam_k,v,   dL/du_v = rho_u sum_k Sigma_U,k,v lam_k,v,
+// Sigma_L = z_L / (v - l_rel) and Sigma_U = z_U / (u_rel - v) the two halves of linearise_stage's Sigma, lam the
+// lam_x | lam_u of the forward sweep, rho the derivative of the bound relaxation (bounds_gradient below).  One more
+// stage-parallel pass and sixteen butterflies; nothing new in LDS.  tests/bounds_vjp_reference.py is the numpy model.
 #include <math.h>
+
+#include <type_traits>
 
 #include "tt_kernel.hpp"
 #include "tt_sens_stage.hpp"
@@ -158,24 +167,68 @@ __device__ __forceinline__ void model_gradient(const DiffArgs& a, double* stg, c
     }
 }
 
-template <bool kModel>
+// g_bounds of an instance that gives no gradient: zeros, or with `accumulate` the accumulator as it is
+__device__ __forceinline__ void zero_bounds(const VjpBoundsArgs& a, int b, int lane) {
+    if (!a.accumulate && lane < 16) a.g_bounds[(size_t)b * 16 + lane] = 0.0;
+}
+
+// The bounds instantiations' phase, behind the forward sweep (the record holds lam_x | lam_u in the Sigma slots), stage-
+// parallel: lane k forms Sigma_L,k,v lam_k,v rho_l and Sigma_U,k,v lam_k,v rho_u of its stages, Sigma_L and Sigma_U
+// again with linearise_stage's own expressions, rho = d(relaxed bound)/d(bound).  A bound the kernel takes as infinite
+// adds nothing (exactly 0).  The states of stage 0 are skipped: x_0 is pinned to x_init and may sit on or beyond a
+// relaxed bound (lam_x,0 = 0, but Sigma is inf or negative there); the last stage has no inputs.  Sixteen butterflies;
+// lane t < 16 leaves with entry t (lower bounds of x 6, u 2, then the upper bounds) in the return value.
+__device__ __forceinline__ double bounds_gradient(const DiffArgs& a, const double* stg, const double* x, const double* u,
+                                                  const double* dl, int lane, bool& bad) {
+    const int N = a.N;
+    double acc[16] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int k = lane; k <= N; k += W) {
+        const double* r = stg + k * kStage;
+        const double* dk = dl + k * kDualPerStage;
+#pragma unroll
+        for (int v = 0; v < 8; ++v) {
+            if (v < 6 ? k == 0 : k == N) continue;
+            const double lam = r[sSG + v];
+            const double val = v < 6 ? x[k * 6 + v] : u[k * 2 + (v - 6)];
+            const double l = v < 6 ? a.xlb[v] : a.ulb[v - 6], ub = v < 6 ? a.xub[v] : a.uub[v - 6];
+            if (isfinite(l) && l > -1e19) {
+                const double sg = dk[6 + v] / (val - (l - 1e-8 * fmax(1.0, fabs(l))));
+                const double rho = fabs(l) > 1.0 ? 1.0 - (l > 0.0 ? 1e-8 : -1e-8) : 1.0;
+                acc[v] += sg * lam * rho;
+            }
+            if (isfinite(ub) && ub < 1e19) {
+                const double sg = dk[14 + v] / ((ub + 1e-8 * fmax(1.0, fabs(ub))) - val);
+                const double rho = fabs(ub) > 1.0 ? 1.0 + (ub > 0.0 ? 1e-8 : -1e-8) : 1.0;
+                acc[8 + v] += sg * lam * rho;
+            }
+        }
+    }
+    double mine = 0.0;
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+        const double s = wave_sum(acc[t]);
+        bad |= !isfinite(s);
+        if (lane == t) mine = s;
+    }
+    return mine;
+}
+
+template <bool kModel, bool kBounds>
 struct KernelArgs {
-    using type = VjpArgs;
-};
-template <>
-struct KernelArgs<true> {
-    using type = VjpModelArgs;
+    using type = std::conditional_t<kBounds, VjpBoundsArgs, std::conditional_t<kModel, VjpModelArgs, VjpArgs>>;
 };
 
-// kModel: also dL/d(L1, L2, Mh) into a.g_model (VjpModelArgs); the plain instantiation is the kernel as it was
-template <bool kModel>
-__global__ __launch_bounds__(W) void track_vjp_kernel(typename KernelArgs<kModel>::type a) {
+// kModel: also dL/d(L1, L2, Mh) into a.g_model (VjpModelArgs); kBounds: also dL/d(bounds) into a.g_bounds
+// (VjpBoundsArgs).  The plain instantiation is the kernel as it was
+template <bool kModel, bool kBounds = false>
+__global__ __launch_bounds__(W) void track_vjp_kernel(typename KernelArgs<kModel, kBounds>::type a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int b = blockIdx.x, lane = threadIdx.x;
     const int N = a.N, S = N + 1;
     if (a.status[b] > 1) {  // > TT_ACCEPTABLE: no optimum to differentiate
         zero_outputs(a, b, lane);
         if constexpr (kModel) zero_model(a, b, lane);
+        if constexpr (kBounds) zero_bounds(a, b, lane);
         if (a.vjp_status && lane == 0) a.vjp_status[b] = 2;
         return;
     }
@@ -239,12 +292,16 @@ __global__ __launch_bounds__(W) void track_vjp_kernel(typename KernelArgs<kModel
     if (__ballot(bad) != 0ull) {
         zero_outputs(a, b, lane);
         if constexpr (kModel) zero_model(a, b, lane);
+        if constexpr (kBounds) zero_bounds(a, b, lane);
         if (a.vjp_status && lane == 0) a.vjp_status[b] = 1;
         return;
     }
     // ---- model geometry: lam_y over gX, then the stage sums (p_0 stays in T, lam_x | lam_u in the records) ----
     double gm[3] = {0.0, 0.0, 0.0};
     if constexpr (kModel) model_gradient(a, stg, T, x, dl, lane, bad, gm);
+    // ---- bounds: the stage sums of Sigma_L lam and Sigma_U lam (entry `lane` of the sixteen in lanes 0 .. 15) ----
+    double gb = 0.0;
+    if constexpr (kBounds) gb = bounds_gradient(a, stg, x, u, dl, lane, bad);
     // ---- outputs ----
     if (a.g_x0 && ro.pl) a.g_x0[(size_t)b * 6 + ro.pi] = T[pc + ro.pi];
     const double* xr = a.xref ? a.xref + (size_t)b * S * 6 : nullptr;
@@ -331,6 +388,14 @@ __global__ __launch_bounds__(W) void track_vjp_kernel(typename KernelArgs<kModel
             *g = a.accumulate ? *g + v : v;
         }
     }
+    if constexpr (kBounds) {  // one writer per instance: lanes 0 .. 15 of its only wavefront
+        if (late) {
+            zero_bounds(a, b, lane);
+        } else if (lane < 16) {
+            double* g = a.g_bounds + (size_t)b * 16 + lane;
+            *g = a.accumulate ? *g + gb : gb;
+        }
+    }
     if (a.vjp_status && lane == 0) a.vjp_status[b] = late ? 1 : 0;
 }
 
@@ -347,6 +412,16 @@ hipError_t launch_track_vjp_model(const VjpModelArgs& a, hipStream_t stream) {
     const int bytes = 8 * vjp_lds_doubles(a.N);  // the same record: lam_y overlays gX
     if (bytes > 64 * 1024 || !a.g_model) return hipErrorInvalidValue;
     hipLaunchKernelGGL(track_vjp_kernel<true>, dim3(a.B), dim3(W), bytes, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_track_vjp_bounds(const VjpBoundsArgs& a, hipStream_t stream) {
+    const int bytes = 8 * vjp_lds_doubles(a.N);  // the same record: nothing of the bounds gradient lives in LDS
+    if (bytes > 64 * 1024 || !a.g_bounds) return hipErrorInvalidValue;
+    if (a.g_model)
+        hipLaunchKernelGGL((track_vjp_kernel<true, true>), dim3(a.B), dim3(W), bytes, stream, a);
+    else
+        hipLaunchKernelGGL((track_vjp_kernel<false, true>), dim3(a.B), dim3(W), bytes, stream, a);
     return hipGetLastError();
 }
 

@@ -63,6 +63,12 @@ class TTTrackVjpModelOut(C.Structure):
                 ("g_model", C.c_void_p), ("vjp_status", C.c_void_p)]
 
 
+class TTTrackVjpBoundsOut(C.Structure):
+    """tt_track_vjp_bounds_out (include/ttmpc.h): tt_track_vjp_model_out with g_bounds [B][16] before vjp_status."""
+    _fields_ = [("g_x0", C.c_void_p), ("g_xref", C.c_void_p), ("g_uref", C.c_void_p), ("g_wq_wr", C.c_void_p),
+                ("g_model", C.c_void_p), ("g_bounds", C.c_void_p), ("vjp_status", C.c_void_p)]
+
+
 class TTObcaVjpOut(C.Structure):
     """tt_obca_vjp_out (include/ttmpc.h): the outputs of tt_obca_vjp*; NULL members are skipped."""
     _fields_ = [("g_x0", C.c_void_p), ("g_xref", C.c_void_p), ("g_uref", C.c_void_p), ("vjp_status", C.c_void_p)]
@@ -94,20 +100,36 @@ class TTError(RuntimeError):
     pass
 
 
-class TrackVjpResult:
+class _BoundsGradient:
+    """g_bounds of a ``TrackVjpResult`` and its four views.  A slot of its own: ``TrackVjpResult.__slots__`` stays the
+    list of what every ``vjp`` call fills."""
+    __slots__ = ("g_bounds",)
+
+    def _part(self, lo, hi):
+        return None if self.g_bounds is None else self.g_bounds[:, lo:hi]
+
+    g_xlb = property(lambda self: self._part(0, 6))
+    g_ulb = property(lambda self: self._part(6, 8))
+    g_xub = property(lambda self: self._part(8, 14))
+    g_uub = property(lambda self: self._part(14, 16))
+
+
+class TrackVjpResult(_BoundsGradient):
     """What ``BatchSolver.vjp`` returns: g_x0 (B,6) = dL/dx0, g_xref (B,N+1,6), g_uref (B,N,2), g_wq_wr (B,8) and
     vjp_status (B,) (0 ok, 1 undefined, 2 solve not successful; the gradients of a failed instance are zeros); with
     ``model=True`` also g_model (B,3) = dL/d(L1, L2, M) per instance, else None.  ``r["model"]``, ``r["x0"]``,
-    ``r["xref"]``, ``r["uref"]``, ``r["w"]`` read the gradients by the names of the inputs."""
+    ``r["xref"]``, ``r["uref"]``, ``r["w"]`` read the gradients by the names of the inputs.  With ``bounds=True`` also
+    g_bounds (B,16) = dL/d(xlb 6, ulb 2, xub 6, uub 2) per instance (``r["bounds"]``), else None; g_xlb (B,6), g_ulb
+    (B,2), g_xub (B,6) and g_uub (B,2) are views of it."""
     __slots__ = ("g_x0", "g_xref", "g_uref", "g_wq_wr", "g_model", "vjp_status")
 
     def __init__(self, **kw):
-        for k in self.__slots__:
+        for k in self.__slots__ + _BoundsGradient.__slots__:
             setattr(self, k, kw.get(k))
 
     def __getitem__(self, key):
         return getattr(self, {"model": "g_model", "x0": "g_x0", "xref": "g_xref", "uref": "g_uref", "w": "g_wq_wr",
-                              "vjp_status": "vjp_status"}[key])
+                              "bounds": "g_bounds", "vjp_status": "vjp_status"}[key])
 
 
 TrackVjpModelResult = TrackVjpResult
@@ -202,6 +224,17 @@ def lib():
         L.tt_set_model.restype = C.c_int
         L.tt_get_model.argtypes = [C.c_void_p, _dp, _dp, _dp]
         L.tt_get_model.restype = C.c_int
+    if not os.environ.get("TTMPC_LIB") or hasattr(L, "tt_track_vjp_bounds_device"):  # (A/B against a build without them)
+        L.tt_track_vjp_bounds_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 9 + [
+            C.POINTER(TTTrackVjpBoundsOut), C.c_int, C.c_void_p]
+        L.tt_track_vjp_bounds_device.restype = C.c_int
+        L.tt_track_vjp_bounds.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp,
+                                          C.POINTER(TTTrackVjpBoundsOut), C.c_int]
+        L.tt_track_vjp_bounds.restype = C.c_int
+        L.tt_set_bounds.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp]
+        L.tt_set_bounds.restype = C.c_int
+        L.tt_get_bounds.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp]
+        L.tt_get_bounds.restype = C.c_int
     L.tt_plan_batch.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _ip]
     L.tt_plan_batch.restype = C.c_int
     L.tt_obca_solve_batch.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp]
@@ -323,7 +356,8 @@ EXPORTED_SYMBOLS = ("tt_create", "tt_solve_batch", "tt_solve_batch_device", "tt_
                     "tt_obca_vjp", "tt_obca_vjp_params_work_bytes", "tt_obca_vjp_params_device", "tt_obca_vjp_params",
                     "tt_set_scene", "tt_get_scene", "tt_obca_solve_batch_scenes", "tt_obca_solve_batch_scenes_device",
                     "tt_obca_vjp_scenes", "tt_obca_vjp_scenes_device", "tt_collision_scenes_device",
-                    "tt_obca_vjp_geometry", "tt_obca_vjp_geometry_device", "tt_set_geometry", "tt_get_geometry")
+                    "tt_obca_vjp_geometry", "tt_obca_vjp_geometry_device", "tt_set_geometry", "tt_get_geometry",
+                    "tt_track_vjp_bounds_device", "tt_track_vjp_bounds", "tt_set_bounds", "tt_get_bounds")
 
 
 def _ptr(a):
@@ -542,14 +576,48 @@ class BatchSolver(_Solver):
             self._err(rc, "tt_get_model")
         return tuple(c.value for c in v)
 
+    def set_bounds(self, xlb=None, xub=None, ulb=None, uub=None):
+        """tt_set_bounds: change the handle's box (a vector left None keeps its current values; +-inf or beyond +-1e19 is
+        a free bound).  Host-side state only: every later call of this solver, host or device, runs with the new box,
+        and a solve is bitwise that of a fresh solver created with it, whichever build of the tracking kernel the new
+        bound pattern selects.  Work already enqueued, and a captured graph, keep the old box.  Raises TTError for a
+        NaN or lb > ub (nothing is changed then).  ``self.bounds`` follows."""
+        new = tuple(c if v is None else _bounds(v, n) for v, c, n in zip((xlb, xub, ulb, uub), self.get_bounds(),
+                                                                          (6, 6, 2, 2)))
+        rc = self._L.tt_set_bounds(self._h, *[_ptr(b) for b in new])
+        if rc != 0:
+            self._err(rc, "tt_set_bounds")
+        self.bounds = tuple(b.copy() for b in new)
+
+    def get_bounds(self):
+        """tt_get_bounds: the handle's current (xlb (6,), xub (6,), ulb (2,), uub (2,))."""
+        if os.environ.get("TTMPC_LIB") and not hasattr(self._L, "tt_get_bounds"):  # (A/B against a build without it)
+            return None
+        out = (np.empty(6), np.empty(6), np.empty(2), np.empty(2))
+        rc = self._L.tt_get_bounds(self._h, *[_ptr(b) for b in out])
+        if rc != 0:
+            self._err(rc, "tt_get_bounds")
+        return out
+
     def vjp_device(self, B, x, u, dual, xref, uref, status, grad_x=0, grad_u=0, g_x0=0, g_xref=0, g_uref=0, g_wq_wr=0,
-                   vjp_status=0, wq_wr=0, stream=0, g_model=0, accumulate=False):
+                   vjp_status=0, wq_wr=0, stream=0, g_model=0, accumulate=False, g_bounds=0):
         """tt_track_vjp_device: the adjoint kernel on device arrays of an earlier ``solve_ex_device`` (its x, u, dual,
         status, and its inputs xref, uref, wq_wr) and the upstream gradients grad_x = dL/dX, grad_u = dL/dU (0 = zeros,
         not both).  Outputs (0 = not wanted): g_x0, g_xref, g_uref, g_wq_wr, vjp_status.  Uses no buffer of the handle:
         any stream will do, behind the solve whose outputs it reads.  g_model (B,3): also dL/d(L1, L2, M) per instance,
         added to the buffer instead of written with ``accumulate``.  One call of tt_track_vjp_model_device either way:
-        without g_model it launches the plain kernel instantiation, as tt_track_vjp_device does."""
+        without g_model it launches the plain kernel instantiation, as tt_track_vjp_device does.  g_bounds (B,16): also
+        dL/d(xlb 6, ulb 2, xub 6, uub 2) per instance, written or added as g_model is, from the same launch
+        (tt_track_vjp_bounds_device; without it the call and its bits are the ones above)."""
+        if g_bounds:
+            out = TTTrackVjpBoundsOut(g_x0 or None, g_xref or None, g_uref or None, g_wq_wr or None, g_model or None,
+                                      g_bounds, vjp_status or None)
+            rc = self._L.tt_track_vjp_bounds_device(self._h, int(B), x, u, dual, xref or None, uref or None,
+                                                    wq_wr or None, status, grad_x or None, grad_u or None,
+                                                    C.byref(out), int(bool(accumulate)), stream or None)
+            if rc != 0:
+                self._err(rc, "tt_track_vjp_bounds_device")
+            return
         out = TTTrackVjpModelOut(g_x0 or None, g_xref or None, g_uref or None, g_wq_wr or None, g_model or None,
                                  vjp_status or None)
         rc = self._L.tt_track_vjp_model_device(self._h, int(B), x, u, dual, xref or None, uref or None, wq_wr or None,
@@ -558,12 +626,14 @@ class BatchSolver(_Solver):
         if rc != 0:
             self._err(rc, "tt_track_vjp_model_device" if g_model else "tt_track_vjp_device")
 
-    def vjp(self, x, u, dual, xref, uref, status, grad_x, grad_u, wq_wr=None, model=False):
+    def vjp(self, x, u, dual, xref, uref, status, grad_x, grad_u, wq_wr=None, model=False, bounds=False):
         """Host arrays: the gradient of a scalar loss L(X, U) with respect to the inputs of the solve that returned
         x (B,N+1,6), u (B,N,2), dual (B,N+1,22) and status (B,) for xref, uref and wq_wr; grad_x (B,N+1,6) = dL/dX and
         grad_u (B,N,2) = dL/dU (either may be None for zeros).  Returns a ``TrackVjpResult``; with ``model=True`` it
         also has g_model (B,3) = dL/d(L1, L2, M) per instance (``r["model"]``).  One call of tt_track_vjp_model either
-        way."""
+        way.  With ``bounds=True`` it also has g_bounds (B,16) = dL/d(xlb 6, ulb 2, xub 6, uub 2) per instance
+        (``r["bounds"]``, and the views g_xlb, g_ulb, g_xub, g_uub): the call is then tt_track_vjp_bounds, the other
+        outputs bitwise the same."""
         N = self.N
         x = _f64(x)
         B = x.shape[0] if x.ndim == 3 else 1
@@ -578,7 +648,15 @@ class BatchSolver(_Solver):
         w = None if wq_wr is None else _f64(wq_wr, (B, 8))
         r = TrackVjpResult(g_x0=np.empty((B, 6)), g_xref=np.empty((B, N + 1, 6)), g_uref=np.empty((B, N, 2)),
                            g_wq_wr=np.empty((B, 8)), g_model=np.empty((B, 3)) if model else None,
-                           vjp_status=np.empty(B, dtype=np.int32))
+                           g_bounds=np.empty((B, 16)) if bounds else None, vjp_status=np.empty(B, dtype=np.int32))
+        if bounds:
+            out = TTTrackVjpBoundsOut(*[None if a is None else a.ctypes.data for a in (
+                r.g_x0, r.g_xref, r.g_uref, r.g_wq_wr, r.g_model, r.g_bounds, r.vjp_status)])
+            rc = self._L.tt_track_vjp_bounds(self._h, B, _ptr(x), _ptr(u), _ptr(dual), _ptr(xref), _ptr(uref), _ptr(w),
+                                             st.ctypes.data_as(_ip), _ptr(gx), _ptr(gu), C.byref(out), 0)
+            if rc != 0:
+                self._err(rc, "tt_track_vjp_bounds")
+            return r
         out = TTTrackVjpModelOut(*[None if a is None else a.ctypes.data for a in (r.g_x0, r.g_xref, r.g_uref, r.g_wq_wr,
                                                                                    r.g_model, r.vjp_status)])
         rc = self._L.tt_track_vjp_model(self._h, B, _ptr(x), _ptr(u), _ptr(dual), _ptr(xref), _ptr(uref), _ptr(w),

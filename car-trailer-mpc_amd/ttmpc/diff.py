@@ -20,6 +20,10 @@ handle with ``set_model``) and, for the closed loop, ``plant_model`` = the plant
 instantiations of the adjoint kernels (include/ttmpc.h, tt_track_vjp_model_device, tt_policy_plant_vjp_model_device),
 summed over the batch.
 
+Both layers also take the solver's box as a tensor: ``bounds`` = (xlb 6, ulb 2, xub 6, uub 2), applied to the handle with
+``set_bounds``; its gradient comes from the bounds instantiations of the adjoint kernel (tt_track_vjp_bounds_device),
+summed over the batch.  It is where the loss on a saturated variable goes.
+
 A closed loop built with a ``ttmpc.simulation.FuzzyRule`` takes the rule's seven parameters as a tensor too
 (``fuzzy_rule=``), and ``fuzzy_weights(x, xref, theta)`` is the rule alone as an autograd
 node (tt_fuzzy_weights_rule_device / tt_fuzzy_weights_vjp_device) whose output feeds ``DifferentiableTracking``'s wq_wr.
@@ -66,13 +70,26 @@ def _host_vector(name, t, what):
     return tuple(float(v) for v in t.detach().cpu().tolist())
 
 
+def _host_bounds(t):
+    """A bounds tensor, float64 (16,) = (xlb 6, ulb 2, xub 6, uub 2) on the CPU or on a device (one host read; +-inf
+    allowed), as the (xlb, xub, ulb, uub) of ``BatchSolver.set_bounds``."""
+    if not (torch.is_tensor(t) and t.dtype == torch.float64 and tuple(t.shape) == (16,)):
+        raise TypeError("bounds must be a float64 tensor of shape (16,) = (xlb 6, ulb 2, xub 6, uub 2)")
+    v = t.detach().cpu().numpy()
+    return v[0:6].copy(), v[8:14].copy(), v[6:8].copy(), v[14:16].copy()
+
+
+def _same_bounds(a, b):
+    return all(np.array_equal(x, y) for x, y in zip(a, b))
+
+
 def _batch_sum(g, device):
     """The per-instance gradients (B,n) summed over the batch, on the input tensor's device."""
     return g.sum(dim=0).to(device)
 
 
 class TrackingSolveFunction(torch.autograd.Function):
-    """``X, U, status = TrackingSolveFunction.apply(solver, x0, xref, uref, wq_wr, z_guess[, model])``.
+    """``X, U, status = TrackingSolveFunction.apply(solver, x0, xref, uref, wq_wr, z_guess[, model[, bounds]])``.
 
     x0 (B,6), xref (B,N+1,6), uref (B,N,2), wq_wr (B,8) or None, z_guess (B,8N+6) or None: float64 CUDA tensors on the
     solver's device.  X (B,N+1,6) and U (B,N,2) are differentiable with respect to x0, xref, uref and wq_wr; status
@@ -83,10 +100,21 @@ class TrackingSolveFunction(torch.autograd.Function):
     the forward reads it to the host once).  The forward applies it with ``solver.set_model`` when it differs from the
     handle's values, and it stays applied; the backward runs the adjoint kernel's model instantiation and returns the
     per-instance gradients summed over B on the tensor's device.  It raises if the handle's geometry was changed
-    between the forward and the backward.  Left out or None: the geometry as it is, no gradient for it."""
+    between the forward and the backward.  Left out or None: the geometry as it is, no gradient for it.
+
+    bounds, if given, makes the solver's box an input in the same way: float64 (16,) = (xlb 6, ulb 2, xub 6, uub 2), the
+    order of g_bounds, on the CPU or on a device; +-inf is a free bound.  The forward applies it with
+    ``solver.set_bounds`` when it differs from the handle's box, and it stays applied; the backward runs the adjoint
+    kernel's bounds instantiation and returns the per-instance gradients summed over B on the tensor's device.  It
+    raises if the handle's box was changed between the forward and the backward."""
 
     @staticmethod
-    def forward(ctx, solver, x0, xref, uref, wq_wr, z_guess, model=None):
+    def forward(ctx, solver, x0, xref, uref, wq_wr, z_guess, model=None, bounds=None):
+        ctx.box = None
+        if bounds is not None:
+            ctx.box, ctx.box_like = _host_bounds(bounds), bounds.device
+            if not _same_bounds(ctx.box, solver.get_bounds()):
+                solver.set_bounds(*ctx.box)
         ctx.geometry = None
         if model is not None:
             ctx.geometry, ctx.like = _host_vector("model", model, _GEOMETRY), model.device
@@ -114,10 +142,13 @@ class TrackingSolveFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_X, grad_U, _grad_status):
-        need = ctx.needs_input_grad  # (solver, x0, xref, uref, wq_wr, z_guess[, model]): one gradient per input given
+        # (solver, x0, xref, uref, wq_wr, z_guess[, model[, bounds]]): one gradient per input given
+        need = ctx.needs_input_grad
         if ctx.geometry is not None and ctx.geometry != ctx.solver.model():
             raise RuntimeError(f"the solver's geometry changed since the forward: {ctx.geometry} -> "
                                f"{ctx.solver.model()}")
+        if ctx.box is not None and not _same_bounds(ctx.box, ctx.solver.get_bounds()):
+            raise RuntimeError("the solver's bounds changed since the forward")
         if grad_X is None and grad_U is None:
             return (None,) * len(need)
         X, U, dual, status, xref, uref = ctx.saved_tensors[:6]
@@ -131,19 +162,22 @@ class TrackingSolveFunction(torch.autograd.Function):
         g_uref = new(B, N, 2) if need[3] else None
         g_w = new(B, 8) if need[4] else None
         g_m = new(B, 3) if len(need) > 6 and need[6] else None
+        g_b = new(B, 16) if len(need) > 7 and need[7] else None
         ctx.solver.vjp_device(B, X.data_ptr(), U.data_ptr(), dual.data_ptr(), xref.data_ptr(), uref.data_ptr(),
                               status.data_ptr(), grad_x=_ptr(gX), grad_u=_ptr(gU), g_x0=_ptr(g_x0), g_xref=_ptr(g_xref),
                               g_uref=_ptr(g_uref), g_wq_wr=_ptr(g_w), wq_wr=_ptr(wq_wr),
-                              stream=torch.cuda.current_stream(dev).cuda_stream, g_model=_ptr(g_m))
-        return (None, g_x0, g_xref, g_uref, g_w, None,
-                None if g_m is None else _batch_sum(g_m, ctx.like))[:len(need)]
+                              stream=torch.cuda.current_stream(dev).cuda_stream, g_model=_ptr(g_m),
+                              g_bounds=_ptr(g_b))
+        return (None, g_x0, g_xref, g_uref, g_w, None, None if g_m is None else _batch_sum(g_m, ctx.like),
+                None if g_b is None else _batch_sum(g_b, ctx.box_like))[:len(need)]
 
 
 TrackingSolveModelFunction = TrackingSolveFunction
 
 
 class DifferentiableTracking:
-    """``X, U, status = layer(x0, xref, uref, wq_wr=None, z_guess=None, model=None)`` with float64 CUDA tensors.
+    """``X, U, status = layer(x0, xref, uref, wq_wr=None, z_guess=None, model=None, bounds=None)`` with float64 CUDA
+    tensors.
 
     A thin callable over ``TrackingSolveFunction`` for one ``BatchSolver`` (TT_VARIANT_TRACK, _NMPC or _FUZZY; the
     fuzzy variant needs wq_wr).  One handle serialises its solves on one stream: the forward uses workspaces of the
@@ -151,14 +185,19 @@ class DifferentiableTracking:
     solver).  The backward uses no buffer of the handle and may run on any stream that is ordered behind the forward,
     as autograd's stream bookkeeping arranges.  Look at ``status`` (and at ``solver.vjp_device(..., vjp_status=...)``
     when in doubt) to see which instances gave a gradient: failed ones give zeros.  With ``model`` (a float64 (3,)
-    tensor (L1, L2, M), CPU or device) the solver's geometry is an input too."""
+    tensor (L1, L2, M), CPU or device) the solver's geometry is an input too, and with ``bounds`` (a float64 (16,)
+    tensor (xlb 6, ulb 2, xub 6, uub 2), CPU or device) its box: a loss on a saturated variable, which has no gradient
+    in the other inputs, arrives at the bound it sits on."""
 
     def __init__(self, solver):
         self.solver = solver
 
-    def __call__(self, x0, xref, uref, wq_wr=None, z_guess=None, model=None):
-        """model: float64 (3,) tensor (L1, L2, M) or None (the solver's geometry as it is, no gradient for it)."""
-        return TrackingSolveFunction.apply(self.solver, x0, xref, uref, wq_wr, z_guess, model)
+    def __call__(self, x0, xref, uref, wq_wr=None, z_guess=None, model=None, bounds=None):
+        """model: float64 (3,) tensor (L1, L2, M) or None (the solver's geometry as it is, no gradient for it).
+        bounds: float64 (16,) tensor (xlb 6, ulb 2, xub 6, uub 2) or None (the solver's box as it is, no gradient)."""
+        if bounds is None:   # (the call form of before)
+            return TrackingSolveFunction.apply(self.solver, x0, xref, uref, wq_wr, z_guess, model)
+        return TrackingSolveFunction.apply(self.solver, x0, xref, uref, wq_wr, z_guess, model, bounds)
 
 
 class ObcaTrackingSolveFunction(torch.autograd.Function):
@@ -302,7 +341,7 @@ class DifferentiableObcaTracking:
 
 class ClosedLoopFunction(torch.autograd.Function):
     """``S, Ua, status = ClosedLoopFunction.apply(loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise[, model,
-    plant_model[, fuzzy_rule]])``.
+    plant_model[, fuzzy_rule[, bounds]]])``.
 
     x_init (B,6), wq_wr (B,8) or None, plan_x (P,Np+1,6) and plan_u (P,Np,2) with P = 1 (shared) or B, or None for the
     loop's own plan, noise (K,B,6) or None: float64 CUDA tensors on the loop's device.  S (K+1,B,6) and Ua (K,B,2) are
@@ -318,12 +357,22 @@ class ClosedLoopFunction(torch.autograd.Function):
     the CPU or on a device (one host read), or None.  The forward applies it with ``loop.set_fuzzy_rule`` (the rule's
     settings w_min, w_max, v_rev stay the loop's) when it differs from the current values, and it stays applied; the
     backward returns dL/dtheta summed over B on the tensor's device.  wq_wr must then be None: the weights come from
-    the rule."""
+    the rule.
 
-    EXTRA = ("g_model_solver", "g_model_plant", "g_fuzzy_rule")   # ClosedLoop.backward's keys of inputs 7, 8, 9
+    bounds: the solver's box as an input, a float64 (16,) tensor (xlb 6, ulb 2, xub 6, uub 2) on the CPU or on a device
+    (one host read; +-inf is a free bound), or None.  The forward applies it with ``loop.set_bounds`` when it differs
+    from the handle's box, and it stays applied; the backward returns dL/dbounds summed over B on the tensor's device
+    (the bounds enter the loop only through the solves: the plant does not clip)."""
+
+    EXTRA = ("g_model_solver", "g_model_plant", "g_fuzzy_rule", "g_bounds")   # ClosedLoop.backward's keys of inputs 7 .. 10
 
     @staticmethod
-    def forward(ctx, loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise, model=None, plant_model=None, fuzzy_rule=None):
+    def forward(ctx, loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise, model=None, plant_model=None, fuzzy_rule=None,
+                bounds=None):
+        if bounds is not None:
+            box = _host_bounds(bounds)
+            if not _same_bounds(box, loop.solver.get_bounds()):
+                loop.set_bounds(*box)
         if fuzzy_rule is not None:
             if loop.rule is None:
                 raise ValueError("fuzzy_rule= needs a loop built with ClosedLoop(..., fuzzy_rule=FuzzyRule(...))")
@@ -334,7 +383,7 @@ class ClosedLoopFunction(torch.autograd.Function):
         vp = None if plant_model is None else _host_vector("plant_model", plant_model, _GEOMETRY)
         loop.set_model(solver=None if vs is None or vs == loop.solver.model() else vs,
                        plant=None if vp is None or vp == loop.plant_model() else vp)
-        ctx.like = tuple(None if t is None else t.device for t in (model, plant_model, fuzzy_rule))
+        ctx.like = tuple(None if t is None else t.device for t in (model, plant_model, fuzzy_rule, bounds))
         if (plan_x is None) != (plan_u is None):
             raise ValueError("give plan_x and plan_u together")
         B = x_init.shape[0]
@@ -354,16 +403,16 @@ class ClosedLoopFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_S, grad_Ua, _grad_status):
-        # (loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise[, model, plant_model[, fuzzy_rule]]): one gradient per
-        # input given
-        need = ctx.needs_input_grad + (False,) * (10 - len(ctx.needs_input_grad))
+        # (loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise[, model, plant_model[, fuzzy_rule[, bounds]]]): one
+        # gradient per input given
+        need = ctx.needs_input_grad + (False,) * (11 - len(ctx.needs_input_grad))
         tape = ctx.tape
         if grad_S is None and grad_Ua is None:
             return (None,) * len(ctx.needs_input_grad)
         GS = torch.zeros_like(tape.S) if grad_S is None else grad_S.to(torch.float64).contiguous()
         GU = torch.zeros_like(tape.Ua) if grad_Ua is None else grad_Ua.to(torch.float64).contiguous()
         g = ctx.loop.backward(tape, GS, GU, **(dict(model=True) if need[7] or need[8] else {}),
-                              **(dict(rule=True) if need[9] else {}))
+                              **(dict(rule=True) if need[9] else {}), **(dict(bounds=True) if need[10] else {}))
         pick = lambda i, k: g[k] if need[i] else None  # noqa: E731
         extra = [_batch_sum(g[k], ctx.like[i]) if need[7 + i] else None for i, k in enumerate(ClosedLoopFunction.EXTRA)]
         return (None, None, pick(2, "g_x_init"), pick(3, "g_wq_wr"), pick(4, "g_plan_x"), pick(5, "g_plan_u"),
@@ -409,7 +458,7 @@ def fuzzy_weights(x, xref, theta, rule=None):
 
 class DifferentiableClosedLoop:
     """``S, Ua, status = layer(x_init, T_sim, wq_wr=None, plan_x=None, plan_u=None, noise=None, model=None,
-    plant_model=None, fuzzy_rule=None)``.
+    plant_model=None, fuzzy_rule=None, bounds=None)``.
 
     A thin callable over ``ClosedLoopFunction`` for one ``ClosedLoop`` whose solver is TT_VARIANT_TRACK or
     TT_VARIANT_NMPC (any of the three failure policies, warm start on or off, measurement or in-plant noise, shared or
@@ -421,18 +470,24 @@ class DifferentiableClosedLoop:
     from: failed solves (whatever the policy then applies), stopped instances, variables sitting on a bound, and the
     warm start (z_guess does not move a converged solution).  With ``model`` and / or ``plant_model`` (float64 (3,)
     tensors (L1, L2, M), CPU or device) the controller's and the plant's geometry are inputs too.  With ``fuzzy_rule``
-    (a float64 (7,) tensor theta, CPU or device) the parameters of the loop's fuzzy rule are an input as well."""
+    (a float64 (7,) tensor theta, CPU or device) the parameters of the loop's fuzzy rule are an input as well.  With
+    ``bounds`` (a float64 (16,) tensor (xlb 6, ulb 2, xub 6, uub 2), CPU or device; not on a switch loop) the solver's box
+    is an input: the loss on the saturated inputs of every step arrives at the bounds they sit on."""
 
     def __init__(self, loop):
         loop._check_differentiable()
         self.loop = loop
 
     def __call__(self, x_init, T_sim, wq_wr=None, plan_x=None, plan_u=None, noise=None, model=None, plant_model=None,
-                 fuzzy_rule=None):
+                 fuzzy_rule=None, bounds=None):
         """model, plant_model: float64 (3,) tensors (L1, L2, M) of the controller's and of the plant's geometry, or
-        None (as they are, no gradient).  fuzzy_rule: float64 (7,) tensor theta of the loop's ``FuzzyRule``, or None."""
+        None (as they are, no gradient).  fuzzy_rule: float64 (7,) tensor theta of the loop's ``FuzzyRule``, or None.
+        bounds: float64 (16,) tensor (xlb 6, ulb 2, xub 6, uub 2) of the solver's box, or None."""
+        if bounds is None:   # (the call form of before)
+            return ClosedLoopFunction.apply(self.loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise, model, plant_model,
+                                            fuzzy_rule)
         return ClosedLoopFunction.apply(self.loop, T_sim, x_init, wq_wr, plan_x, plan_u, noise, model, plant_model,
-                                        fuzzy_rule)
+                                        fuzzy_rule, bounds)
 
 
 def _host(name, m, n):

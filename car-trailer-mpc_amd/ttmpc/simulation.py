@@ -309,7 +309,8 @@ class LoopTape:
     what ``ClosedLoop.backward`` needs, None in a plain ``run``: consec (K,B), the consecutive-failure count after each
     step, each step's solve X (K,B,N+1,6), U (K,B,N,2), dual (K,B,N+1,22) and the noise it used (K,B,6) or None.
     wq_wr (B,8) or None are the run's weights, plan_x / plan_u the plan it saw, model_solver / model_plant the
-    (L1, L2, M) of the solver's handle and of the plant during a taped run.  The taped run of a loop with a
+    (L1, L2, M) of the solver's handle and of the plant during a taped run, bounds the handle's box (xlb, xub, ulb, uub)
+    during it.  The taped run of a loop with a
     ``FuzzyRule`` also keeps rule (that rule), W (K,B,8), the weights each step's accepted solve used (ones where the
     unit-weight retry was taken), and retried (K,B) int32, where it was: 68 bytes per instance and step.  The taped run
     of a switch loop (``switch_adjoint=True``) keeps switched: per step None, or (idx (n,) int64, the flagged instances;
@@ -317,7 +318,7 @@ class LoopTape:
     and geometry_switch, the (L1, L2, M, W1, W2) of the switch solver's handle during the run."""
     __slots__ = ("ks", "S", "Ua", "status", "iters", "collide", "active", "consec", "X", "U", "dual", "noise", "wq_wr",
                  "plan_x", "plan_u", "model_solver", "model_plant", "W", "retried", "rule", "switched",
-                 "geometry_switch")
+                 "geometry_switch", "bounds")
     # (log field, the loop's buffer a step leaves it in), in the order record() copies them; the solve writes dual
     STEP = (("S", "state"), ("Ua", "u_applied"), ("status", "st"), ("iters", "it"), ("collide", "flag"),
             ("active", "active"), ("consec", "consec"), ("X", "X"), ("U", "U"), ("W", "wq"), ("retried", "retried"))
@@ -339,6 +340,7 @@ class LoopTape:
             log.consec = new(K, B, dtype=torch.int32)
             log.X, log.U, log.dual = new(K, B, N + 1, 6), new(K, B, N, 2), new(K, B, N + 1, 22)
             log.model_solver, log.model_plant = loop.solver.model(), loop.plant_model()   # (run_tape: a BatchSolver)
+            log.bounds = loop.solver.get_bounds()
             if loop.switch is not None and loop.switch_adjoint:
                 log.geometry_switch = loop.switch.geometry()
             if loop.rule is not None:
@@ -478,6 +480,13 @@ class ClosedLoop:
             if not (L1 > 0 and L2 > 0 and math.isfinite(L1) and math.isfinite(L2) and math.isfinite(M)):
                 raise ValueError("plant geometry: L1, L2 must be > 0 and M finite")
             self.params.update(L1=L1, L2=L2, M=M)
+
+    def set_bounds(self, xlb=None, xub=None, ulb=None, uub=None):
+        """Change the box of the tracking solver (``BatchSolver.set_bounds``, tt_set_bounds; a vector left None keeps its
+        values).  Host-side state only: later steps and runs solve in the new box; the plant does not clip, so the box
+        enters the loop through the solves alone.  ``run_graph`` captures its step anew on every call.  A tape keeps the
+        box of its run; ``backward`` on a tape made before a change raises."""
+        self.solver.set_bounds(xlb, xub, ulb, uub)
 
     def set_fuzzy_rule(self, rule):
         """The ``FuzzyRule`` of the steps and runs from now on (None: the built-in rule for a TT_VARIANT_FUZZY solver,
@@ -837,7 +846,7 @@ class ClosedLoop:
         torch.cuda.synchronize(self.dev)
         return dict(self._policy_logs(), **tape.result(), tape=tape)
 
-    def backward(self, tape, GS, GU, model=False, rule=False, scene=False, geometry=False):
+    def backward(self, tape, GS, GU, model=False, rule=False, scene=False, geometry=False, bounds=False):
         """The adjoint of a taped run for a scalar loss L(S, Ua): GS = dL/dS (K+1,B,6), GU = dL/dUa (K,B,2), float64
         device tensors.  Per step, backwards: tt_policy_plant_vjp_device, the step's window again,
         tt_track_vjp_device on the taped solve, tt_sim_window_vjp_device (include/ttmpc.h, "Reverse mode of the closed
@@ -876,7 +885,16 @@ class ClosedLoop:
         without a switch; the switched instances, masked in the tracking adjoint, add nothing to g_model_solver.  The
         three geometries are separate inputs: a loop that shares one sums them.  The switch solver's geometry must still
         be the run's.  The collision switch is piecewise constant in the geometry too.  No host synchronisation is
-        added."""
+        added.
+        bounds=True adds g_bounds (B,16): dL/d(xlb 6, ulb 2, xub 6, uub 2) per instance of the tracking solver's box,
+        accumulated over the steps by the step's one solve adjoint (then tt_track_vjp_bounds_device, beside g_model
+        with model=True): the step stays four launches.  The box enters the loop only through the solves (the plant
+        does not clip).  The same loops as model=True: all three policies and a loop with a ``FuzzyRule``; a switch
+        loop raises (the MPC+OBCA solver's box is not differentiated).  Raises if the solver's box is no longer the
+        tape's, with or without bounds=True."""
+        if self.switch is not None and bounds:
+            raise ValueError("a switch (OBCA) loop has no bounds=True gradient: the box of the MPC+OBCA solver is not "
+                             "differentiated")
         self._check_differentiable()
         if scene and (self.switch is None or not self.switch_adjoint):
             raise ValueError("scene=True needs a switch loop: ClosedLoop(..., switch_solver=..., switch_adjoint=True)")
@@ -885,6 +903,10 @@ class ClosedLoop:
         if self.switch is not None and (model or rule):
             raise ValueError("a switch (OBCA) loop has no model=True or rule=True gradient: the OBCA adjoint "
                              "(switch_adjoint) gives dL/d(x_init, xref, uref) only")
+        if tape.bounds is not None and not all(np.array_equal(a, b) for a, b in zip(tape.bounds,
+                                                                                     self.solver.get_bounds())):
+            raise ValueError("the solver's bounds changed since the tape was made; run the tape again, or set the "
+                             "bounds back before the backward")
         if tape.rule != self.rule:
             raise ValueError(f"the fuzzy rule changed since the tape was made: {tape.rule} -> {self.rule}; run the tape "
                              "again, or set the rule back before the backward")
@@ -912,6 +934,7 @@ class ClosedLoop:
         xref, uref = z(B, N + 1, 6), z(B, N, 2)
         g_x0, g_xr, g_ur, g_ws = z(B, 6), z(B, N + 1, 6), z(B, N, 2), z(B, 8)
         g_ms, g_mp = (z(B, 3), z(B, 3)) if mdl else (None, None)
+        g_bd = z(B, 16) if bounds else None
         fz = tape.rule is not None
         g_th = z(B, 7) if rule else None
         x_meas = z(B, 6) if fz else None
@@ -933,6 +956,7 @@ class ClosedLoop:
         plant_vjp, plant_tail = ((L.tt_policy_plant_vjp_model_device, (g_mp.data_ptr(), sp)) if mdl else
                                  (L.tt_policy_plant_vjp_device, (sp,)))
         g_model = g_ms.data_ptr() if mdl else 0
+        g_bounds = g_bd.data_ptr() if bounds else 0
         if fz:
             # the rule's four extra per-step addresses by offset: a tape slice made on the host costs it more than the
             # launch it feeds, and the host only just keeps ahead of a backward step
@@ -968,7 +992,7 @@ class ClosedLoop:
                                    xref.data_ptr(), uref.data_ptr(), status[t].data_ptr(), grad_u=gU.data_ptr(),
                                    g_x0=g_x0.data_ptr(), g_xref=g_xr.data_ptr(), g_uref=g_ur.data_ptr(),
                                    g_wq_wr=g_ws.data_ptr(), wq_wr=w_t, stream=s.cuda_stream, g_model=g_model,
-                                   accumulate=True)
+                                   accumulate=True, g_bounds=g_bounds)
             if sw[t] is not None:
                 idx, it_c, st_c = sw[t]
                 n = int(idx.shape[0])
@@ -1009,6 +1033,8 @@ class ClosedLoop:
             out.update(g_model_solver=g_ms, g_model_plant=g_mp)
         if geometry:
             out["g_geometry_switch"] = g_ge
+        if bounds:
+            out["g_bounds"] = g_bd
         if rule:
             out["g_fuzzy_rule"] = g_th
         if scene:

@@ -171,7 +171,8 @@ int tt_track_sens_device(void* handle, int B, const double* d_x, const double* d
  *   Signs: the arrays are gradients of L (descent moves a parameter against them); a positive g_x0 entry means
  *   L grows with that x_init entry.
  *   First order only, as above: the active set is taken as fixed, and a variable sitting on a bound carries
- *   (numerically) zero lam, so a loss on it has no gradient.
+ *   (numerically) zero lam, so a loss on it has no gradient in these inputs: it goes to the bound itself
+ *   (tt_track_vjp_bounds below).
  *
  * tt_track_vjp_device: device pointers (inside the host-side struct too), asynchronous on `stream`.  It uses
  * no buffer of the handle, so it may run on any stream, also beside a solve of the same handle on another
@@ -220,6 +221,50 @@ int tt_track_vjp_model(void* handle, int B, const double* x, const double* u, co
  * after a change.  tt_get_model reads the current values (NULL pointers are skipped). */
 int tt_set_model(void* handle, double L1, double L2, double Mh);
 int tt_get_model(void* handle, double* L1, double* L2, double* Mh);
+
+/* The same adjoint with the gradient in the box (xlb, xub, ulb, uub) of the handle (tt_create, or the last
+ * tt_set_bounds).  The bounds enter F only through z_L = mu / (v - l_rel) and z_U = mu / (u_rel - v) (l_rel, u_rel:
+ * the relaxed bounds l - 1e-8 max(1, |l|), u + 1e-8 max(1, |u|)), so with lam of the same solve K (lam_z, lam_y) = (g, 0)
+ *     dL/dl_v = rho_l sum_k Sigma_L,k,v lam_k,v,      dL/du_v = rho_u sum_k Sigma_U,k,v lam_k,v,
+ * Sigma_L = z_L / (v - l_rel) and Sigma_U = z_U / (u_rel - v) the two halves of Sigma, rho the derivative of the
+ * relaxation (1 -+ 1e-8 sign(bound) beyond |bound| > 1, else 1); the sums run over the stages k >= 1 for a state
+ * bound (x_0 is pinned to x_init) and k < N for an input bound.  This is where the loss on a saturated variable goes:
+ * on a hard-active bound Sigma is huge, lam = g / Sigma, and the product is the upstream gradient g itself.  An inactive
+ * bound's entry is mu / slack^2 lam, numerically zero; a weakly active bound's entry depends on the final mu.  First
+ * order, as above: a bound that becomes active or inactive inside a step of the bound is a kink.
+ *     g_bounds [B][16]      dL/dxlb (6), dL/dulb (2), dL/dxub (6), dL/duub (2) per instance: the order of z_L | z_U in
+ *                           the multiplier export; the sum over B for the box the batch shares is the caller's.  The
+ *                           entry of a bound the solver treats as infinite (not finite, or beyond +-1e19) is exactly 0.
+ *   accumulate: as for tt_track_vjp_model, and it concerns g_model and g_bounds only (zeros or an untouched
+ *   accumulator for vjp_status 1 and 2).
+ *   g_bounds == NULL: the call is tt_track_vjp_model[_device] (the same kernel instantiation, the same bits); with it
+ *   the other arrays (g_model included, which may be NULL) and vjp_status are bitwise what that call writes.  One
+ *   launch either way (track_vjp_kernel's bounds instantiations, tt_vjp.hip): no second factorisation, the same LDS
+ *   record.
+ * tt_track_vjp_bounds: host pointers, synchronous, as tt_track_vjp_model. */
+typedef struct { double* g_x0; double* g_xref; double* g_uref; double* g_wq_wr; double* g_model;
+                 double* g_bounds;  /* [B][16]  dL/d(xlb 6, ulb 2, xub 6, uub 2) per instance */
+                 int* vjp_status; } tt_track_vjp_bounds_out;
+int tt_track_vjp_bounds_device(void* handle, int B, const double* d_x, const double* d_u, const double* d_dual,
+                               const double* d_xref, const double* d_uref, const double* d_wq_wr, const int* d_status,
+                               const double* d_grad_x, const double* d_grad_u, const tt_track_vjp_bounds_out* d_out,
+                               int accumulate, void* stream);
+int tt_track_vjp_bounds(void* handle, int B, const double* x, const double* u, const double* dual, const double* xref,
+                        const double* uref, const double* wq_wr, const int* status, const double* grad_x,
+                        const double* grad_u, const tt_track_vjp_bounds_out* out, int accumulate);
+
+/* The box of a tracking handle (TT_VARIANT_TRACK, _NMPC, _FUZZY) without rebuilding it: xlb, xub [6], ulb, uub [2], raw
+ * bounds as tt_create takes them (not finite, or beyond +-1e19: free).  tt_set_bounds applies tt_create's validation (no
+ * NaN, lb <= ub; else -EINVAL and the handle keeps its values); an OBCA handle returns -EINVAL.  It changes host-side
+ * state only: the box is a launch argument of every kernel of the handle, and the tracking kernel's build (the MPC
+ * pattern, the OBCA pattern, or the one that reads its bound pattern at run time) is chosen from it at every launch.
+ * So every later call, host or device, zero-copy or not, runs with the new box, and a solve is bitwise that of a fresh
+ * handle created with it, also when the change moves the handle from one build to another.  Calls on one handle stay
+ * serialised as before: work already enqueued keeps the box it was launched with, and so does a captured graph
+ * (hipGraph, ClosedLoop.run_graph): capture again after a change.  tt_get_bounds reads the current values (NULL
+ * pointers are skipped). */
+int tt_set_bounds(void* handle, const double* xlb, const double* xub, const double* ulb, const double* uub);
+int tt_get_bounds(void* handle, double* xlb, double* xub, double* ulb, double* uub);
 
 /* Replaces TrajectoryOptimization.plan (trajectory_optimization.py:311-331) for B scenarios of a
  * TT_VARIANT_OBCA_PLAN handle.  x0, xgoal [B][6] (ca.vertcat(initial_state, goal_state), 316-323);
