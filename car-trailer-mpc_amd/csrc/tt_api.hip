@@ -1009,80 +1009,37 @@ static int obca_vjp_horizon(Handle* h) {
                 std::to_string(ttmpc::obca_vjp_max_horizon()).c_str());
 }
 
-// (d_obs [B][M][4]: per-instance obstacles, nullptr: the handle's)
-static int obca_vjp_device(void* handle, int B, const double* d_iterate, const int* d_status, const double* d_grad_x,
-                           const double* d_grad_u, const tt_obca_vjp_out* d_out, const double* d_obs, void* stream) {
-    Handle* h = static_cast<Handle*>(handle);
-    if (const int rc = prelude(h, B, kHandle | kObcaOnly | kNotPlan | kSign)) return rc;
-    if (!d_grad_x && !d_grad_u) return fail(h, -EINVAL, "grad_x and grad_u are both NULL: no loss to differentiate%s");
-    if (const int rc = obca_vjp_horizon(h)) return rc;
-    if (const int rc = prelude(h, B, kEmpty | kRange)) return result(rc);
-    if (!d_iterate || !d_status || !d_out) return fail(h, -EINVAL, "NULL device buffer%s");
-    DeviceGuard dg(h->device);
-    if (dg.err != hipSuccess) return hip_fail(h, dg.err, "hipSetDevice");
-    ttmpc::ObcaVjpArgs a = diff_args<ttmpc::ObcaVjpArgs>(h, B, nullptr, nullptr, nullptr, nullptr, d_status);
-    a.M = h->cfg.M;
-    a.W1 = h->cfg.W1;
-    a.W2 = h->cfg.W2;
-    a.eq_tol = 1e-5;  // trajectory_optimization.py:136-139, as the solve sets it
-    memcpy(a.obs, h->obs, sizeof a.obs);
-    a.obs_b = d_obs;
-    a.iterate = d_iterate;
-    a.gx = d_grad_x;
-    a.gu = d_grad_u;
-    a.g_x0 = d_out->g_x0;
-    a.g_xref = d_out->g_xref;
-    a.g_uref = d_out->g_uref;
-    a.vjp_status = d_out->vjp_status;
-    const hipError_t e = ttmpc::launch_obca_vjp(a, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(h, e, "OBCA adjoint kernel launch");
-    return 0;
+long long tt_obca_vjp_params_work_bytes(int N, int M) {
+    return (N < 1 || M < 1) ? -EINVAL : (long long)(8 * ttmpc::obca_vjp_params_work_doubles(N, M));
 }
 
-int tt_obca_vjp_device(void* handle, int B, const double* d_iterate, const int* d_status, const double* d_grad_x,
-                       const double* d_grad_u, const tt_obca_vjp_out* d_out, void* stream) {
-    return obca_vjp_device(handle, B, d_iterate, d_status, d_grad_x, d_grad_u, d_out, nullptr, stream);
+// The eight entries below run one device body and one host stager over the widest call, the geometry entries': each
+// widens its out-struct to tt_obca_vjp_geometry_out and names the kernel instantiation (ttmpc::ObcaVjpKind) its own
+// rule picks.  NULL stays NULL (the bodies' to refuse).
+static const tt_obca_vjp_geometry_out* widen(const tt_obca_vjp_params_out* out, tt_obca_vjp_geometry_out& o) {
+    if (!out) return nullptr;
+    o = {out->g_x0, out->g_xref, out->g_uref, out->vjp_status, out->g_obstacles, out->g_dmin, out->g_Q, out->g_R,
+         nullptr};
+    return &o;
 }
 
-static int obca_vjp_host(void* handle, int B, const double* iterate, const int* status, const double* grad_x,
-                         const double* grad_u, const tt_obca_vjp_out* out, const double* obs) {
-    Handle* h = static_cast<Handle*>(handle);
-    if (const int rc = prelude(h, B, kHandle | kObcaOnly | kNotPlan | kSign)) return rc;
-    if (!grad_x && !grad_u) return fail(h, -EINVAL, "grad_x and grad_u are both NULL: no loss to differentiate%s");
-    if (const int rc = obca_vjp_horizon(h)) return rc;   // (before anything is staged)
-    if (const int rc = prelude(h, B, kEmpty | kRange)) return result(rc);
-    if (!iterate || !status || !out) return fail(h, -EINVAL, "NULL host buffer%s");
-    if (const int rc = check_scenes(h, B, obs, nullptr)) return rc;
-    DeviceGuard dg(h->device);
-    if (dg.err != hipSuccess) return hip_fail(h, dg.err, "hipSetDevice");
-    const size_t N = h->cfg.N, b = (size_t)B, nx = b * (N + 1) * 6, nu = b * N * 2;
-    Stager st;
-    const double *d_it, *d_gx, *d_gu, *d_obs;
-    const int* d_st;
-    tt_obca_vjp_out dout;
-    st.in(obs, b * 4 * h->cfg.M, &d_obs);
-    st.in(iterate, b * ttmpc::obca_iterate_len(h->cfg.N, h->cfg.M), &d_it);
-    st.in(grad_x, nx, &d_gx);
-    st.in(grad_u, nu, &d_gu);
-    st.in(status, b, &d_st);
-    st.out(out->g_x0, b * 6, &dout.g_x0);
-    st.out(out->g_xref, nx, &dout.g_xref);
-    st.out(out->g_uref, nu, &dout.g_uref);
-    st.out(out->vjp_status, b, &dout.vjp_status);
-    if (!st.carve(h->xfer)) return no_memory(h, "adjoint staging");
-    hipStream_t s = h->stream;
-    return st.run(h, s, "OBCA adjoint",
-                  [&] { return obca_vjp_device(handle, B, d_it, d_st, d_gx, d_gu, &dout, d_obs, s); });
+static const tt_obca_vjp_geometry_out* widen(const tt_obca_vjp_out* out, tt_obca_vjp_geometry_out& o) {
+    if (!out) return nullptr;
+    o = {out->g_x0, out->g_xref, out->g_uref, out->vjp_status, nullptr, nullptr, nullptr, nullptr, nullptr};
+    return &o;
 }
 
-int tt_obca_vjp(void* handle, int B, const double* iterate, const int* status, const double* grad_x,
-                const double* grad_u, const tt_obca_vjp_out* out) {
-    return obca_vjp_host(handle, B, iterate, status, grad_x, grad_u, out, nullptr);
+// tt_obca_vjp_scenes* / _geometry*: the geometry instantiation iff g_geometry is wanted; else the plain one (no work
+// buffer) iff no parameter output is wanted and, in a device entry, no work buffer is given; else the params one
+static ttmpc::ObcaVjpKind obca_vjp_kind(const tt_obca_vjp_geometry_out* o, const void* work) {
+    if (o && o->g_geometry) return ttmpc::kObcaVjpGeom;
+    const bool plain = o && !work && !o->g_obstacles && !o->g_dmin && !o->g_Q && !o->g_R;
+    return plain ? ttmpc::kObcaVjpPlain : ttmpc::kObcaVjpParams;
 }
 
-// tt_obca_vjp_params*: the checks both entries share, in tt_obca_vjp's order
-static int obca_vjp_params_checks(Handle* h, int B, const void* grad_x, const void* grad_u, const void* xref,
-                                  const void* uref, const tt_obca_vjp_params_out* out) {
+// the checks the device body and the host stager share, in this order (nothing staged yet)
+static int obca_vjp_checks(Handle* h, int B, const void* grad_x, const void* grad_u, const void* xref, const void* uref,
+                           const tt_obca_vjp_geometry_out* out) {
     if (const int rc = prelude(h, B, kHandle | kObcaOnly | kNotPlan | kSign)) return rc;
     if (!grad_x && !grad_u) return fail(h, -EINVAL, "grad_x and grad_u are both NULL: no loss to differentiate%s");
     if (const int rc = obca_vjp_horizon(h)) return rc;
@@ -1091,18 +1048,15 @@ static int obca_vjp_params_checks(Handle* h, int B, const void* grad_x, const vo
     return 0;
 }
 
-long long tt_obca_vjp_params_work_bytes(int N, int M) {
-    return (N < 1 || M < 1) ? -EINVAL : (long long)(8 * ttmpc::obca_vjp_params_work_doubles(N, M));
-}
-
-// (d_geom [B][5]: also dL/d(L1, L2, Mh, W1, W2), the geometry instantiation; nullptr: the params one)
-static int obca_vjp_params_device(void* handle, int B, const double* d_iterate, const int* d_status,
-                                  const double* d_xref, const double* d_uref, const double* d_grad_x,
-                                  const double* d_grad_u, const tt_obca_vjp_params_out* d_out, void* d_work,
-                                  const double* d_obs, void* stream, double* d_geom = nullptr) {
+// (d_obs [B][M][4]: per-instance obstacles, nullptr: the handle's; d_work: not read by the plain kind)
+static int obca_vjp_device(void* handle, int B, const double* d_iterate, const int* d_status, const double* d_xref,
+                           const double* d_uref, const double* d_grad_x, const double* d_grad_u,
+                           const tt_obca_vjp_geometry_out* d_out, void* d_work, const double* d_obs,
+                           ttmpc::ObcaVjpKind kind, void* stream) {
     Handle* h = static_cast<Handle*>(handle);
-    if (const int rc = obca_vjp_params_checks(h, B, d_grad_x, d_grad_u, d_xref, d_uref, d_out)) return rc;
-    if (!d_work) return fail(h, -EINVAL, "NULL work buffer (tt_obca_vjp_params_work_bytes per instance)%s");
+    const bool plain = kind == ttmpc::kObcaVjpPlain;
+    if (const int rc = obca_vjp_checks(h, B, d_grad_x, d_grad_u, d_xref, d_uref, d_out)) return rc;
+    if (!plain && !d_work) return fail(h, -EINVAL, "NULL work buffer (tt_obca_vjp_params_work_bytes per instance)%s");
     if (const int rc = prelude(h, B, kEmpty | kRange)) return result(rc);
     if (!d_iterate || !d_status || !d_out) return fail(h, -EINVAL, "NULL device buffer%s");
     DeviceGuard dg(h->device);
@@ -1128,41 +1082,23 @@ static int obca_vjp_params_device(void* handle, int B, const double* d_iterate, 
     a.g_Q = d_out->g_Q;
     a.g_R = d_out->g_R;
     a.work = static_cast<double*>(d_work);
-    a.g_geom = d_geom;
-    const hipError_t e = d_geom ? ttmpc::launch_obca_vjp_geom(a, static_cast<hipStream_t>(stream))
-                                : ttmpc::launch_obca_vjp_params(a, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(h, e, "OBCA params adjoint kernel launch");
+    a.g_geom = d_out->g_geometry;
+    const hipError_t e = ttmpc::launch_obca_vjp(a, kind, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(h, e, plain ? "OBCA adjoint kernel launch" : "OBCA params adjoint kernel launch");
     return 0;
 }
 
-int tt_obca_vjp_params_device(void* handle, int B, const double* d_iterate, const int* d_status, const double* d_xref,
-                              const double* d_uref, const double* d_grad_x, const double* d_grad_u,
-                              const tt_obca_vjp_params_out* d_out, void* d_work, void* stream) {
-    return obca_vjp_params_device(handle, B, d_iterate, d_status, d_xref, d_uref, d_grad_x, d_grad_u, d_out, d_work,
-                                  nullptr, stream);
-}
-
-// tt_obca_vjp_scenes*: no parameter output wanted -> the plain instantiation (no work buffer)
-static bool plain_adjoint(const tt_obca_vjp_params_out* o) { return !o->g_obstacles && !o->g_dmin && !o->g_Q && !o->g_R; }
-
-int tt_obca_vjp_scenes_device(void* handle, int B, const double* d_iterate, const int* d_status, const double* d_xref,
-                              const double* d_uref, const double* d_grad_x, const double* d_grad_u,
-                              const tt_obca_vjp_params_out* d_out, void* d_work, const tt_obca_scenes* d_scenes,
-                              void* stream) {
-    const double* d_obs = d_scenes ? d_scenes->obstacles : nullptr;
-    if (d_out && !d_work && plain_adjoint(d_out)) {
-        const tt_obca_vjp_out o = {d_out->g_x0, d_out->g_xref, d_out->g_uref, d_out->vjp_status};
-        return obca_vjp_device(handle, B, d_iterate, d_status, d_grad_x, d_grad_u, &o, d_obs, stream);
-    }
-    return obca_vjp_params_device(handle, B, d_iterate, d_status, d_xref, d_uref, d_grad_x, d_grad_u, d_out, d_work,
-                                  d_obs, stream);
-}
-
-static int obca_vjp_params_host(void* handle, int B, const double* iterate, const int* status, const double* xref,
-                                const double* uref, const double* grad_x, const double* grad_u,
-                                const tt_obca_vjp_params_out* out, const double* obs, double* g_geom = nullptr) {
+// (scenes nullptr: the handle's scene)
+static int obca_vjp_host(void* handle, int B, const double* iterate, const int* status, const double* xref,
+                         const double* uref, const double* grad_x, const double* grad_u,
+                         const tt_obca_vjp_geometry_out* out, const tt_obca_scenes* scenes, ttmpc::ObcaVjpKind kind) {
     Handle* h = static_cast<Handle*>(handle);
-    if (const int rc = obca_vjp_params_checks(h, B, grad_x, grad_u, xref, uref, out)) return rc;  // (nothing staged yet)
+    const double* obs = scenes ? scenes->obstacles : nullptr;
+    const bool plain = kind == ttmpc::kObcaVjpPlain;
+    // (the adjoint does not read d_min, but a scene the solve would have refused is refused here too)
+    if (h && is_obca(h->cfg) && scenes && scenes->d_min)
+        if (const int rc = check_scenes(h, B, nullptr, scenes->d_min)) return rc;
+    if (const int rc = obca_vjp_checks(h, B, grad_x, grad_u, xref, uref, out)) return rc;
     if (const int rc = prelude(h, B, kEmpty | kRange)) return result(rc);
     if (!iterate || !status || !out) return fail(h, -EINVAL, "NULL host buffer%s");
     if (const int rc = check_scenes(h, B, obs, nullptr)) return rc;
@@ -1171,10 +1107,10 @@ static int obca_vjp_params_host(void* handle, int B, const double* iterate, cons
     const size_t N = h->cfg.N, M = h->cfg.M, b = (size_t)B, nx = b * (N + 1) * 6, nu = b * N * 2;
     Stager st;
     const double *d_it, *d_gx, *d_gu, *d_xr, *d_ur, *d_obs;
-    st.in(obs, b * 4 * M, &d_obs);
     const int* d_st;
-    double *d_work, *d_geom;
-    tt_obca_vjp_params_out dout;
+    double* d_work = nullptr;
+    tt_obca_vjp_geometry_out dout;
+    st.in(obs, b * 4 * M, &d_obs);
     st.in(iterate, b * ttmpc::obca_iterate_len(h->cfg.N, h->cfg.M), &d_it);
     st.in(grad_x, nx, &d_gx);
     st.in(grad_u, nu, &d_gu);
@@ -1189,70 +1125,74 @@ static int obca_vjp_params_host(void* handle, int B, const double* iterate, cons
     st.out(out->g_dmin, b, &dout.g_dmin);
     st.out(out->g_Q, b * 36, &dout.g_Q);
     st.out(out->g_R, b * 4, &dout.g_R);
-    st.out(g_geom, b * 5, &d_geom);
-    st.out((double*)nullptr, b * ttmpc::obca_vjp_params_work_doubles(h->cfg.N, h->cfg.M), &d_work, true);
+    st.out(out->g_geometry, b * 5, &dout.g_geometry);
+    if (!plain) st.out((double*)nullptr, b * ttmpc::obca_vjp_params_work_doubles(h->cfg.N, h->cfg.M), &d_work, true);
     if (!st.carve(h->xfer)) return no_memory(h, "adjoint staging");
     hipStream_t s = h->stream;
-    return st.run(h, s, "OBCA params adjoint", [&] {
-        return obca_vjp_params_device(handle, B, d_it, d_st, d_xr, d_ur, d_gx, d_gu, &dout, d_work, d_obs, s, d_geom);
+    return st.run(h, s, plain ? "OBCA adjoint" : "OBCA params adjoint", [&] {
+        return obca_vjp_device(handle, B, d_it, d_st, d_xr, d_ur, d_gx, d_gu, &dout, d_work, d_obs, kind, s);
     });
+}
+
+int tt_obca_vjp_device(void* handle, int B, const double* d_iterate, const int* d_status, const double* d_grad_x,
+                       const double* d_grad_u, const tt_obca_vjp_out* d_out, void* stream) {
+    tt_obca_vjp_geometry_out o;
+    return obca_vjp_device(handle, B, d_iterate, d_status, nullptr, nullptr, d_grad_x, d_grad_u, widen(d_out, o),
+                           nullptr, nullptr, ttmpc::kObcaVjpPlain, stream);
+}
+
+int tt_obca_vjp(void* handle, int B, const double* iterate, const int* status, const double* grad_x,
+                const double* grad_u, const tt_obca_vjp_out* out) {
+    tt_obca_vjp_geometry_out o;
+    return obca_vjp_host(handle, B, iterate, status, nullptr, nullptr, grad_x, grad_u, widen(out, o), nullptr,
+                         ttmpc::kObcaVjpPlain);
+}
+
+int tt_obca_vjp_params_device(void* handle, int B, const double* d_iterate, const int* d_status, const double* d_xref,
+                              const double* d_uref, const double* d_grad_x, const double* d_grad_u,
+                              const tt_obca_vjp_params_out* d_out, void* d_work, void* stream) {
+    tt_obca_vjp_geometry_out o;
+    return obca_vjp_device(handle, B, d_iterate, d_status, d_xref, d_uref, d_grad_x, d_grad_u, widen(d_out, o), d_work,
+                           nullptr, ttmpc::kObcaVjpParams, stream);
 }
 
 int tt_obca_vjp_params(void* handle, int B, const double* iterate, const int* status, const double* xref,
                        const double* uref, const double* grad_x, const double* grad_u,
                        const tt_obca_vjp_params_out* out) {
-    return obca_vjp_params_host(handle, B, iterate, status, xref, uref, grad_x, grad_u, out, nullptr);
+    tt_obca_vjp_geometry_out o;
+    return obca_vjp_host(handle, B, iterate, status, xref, uref, grad_x, grad_u, widen(out, o), nullptr,
+                         ttmpc::kObcaVjpParams);
+}
+
+int tt_obca_vjp_scenes_device(void* handle, int B, const double* d_iterate, const int* d_status, const double* d_xref,
+                              const double* d_uref, const double* d_grad_x, const double* d_grad_u,
+                              const tt_obca_vjp_params_out* d_out, void* d_work, const tt_obca_scenes* d_scenes,
+                              void* stream) {
+    tt_obca_vjp_geometry_out o;
+    return tt_obca_vjp_geometry_device(handle, B, d_iterate, d_status, d_xref, d_uref, d_grad_x, d_grad_u,
+                                       widen(d_out, o), d_work, d_scenes, stream);
 }
 
 int tt_obca_vjp_scenes(void* handle, int B, const double* iterate, const int* status, const double* xref,
                        const double* uref, const double* grad_x, const double* grad_u,
                        const tt_obca_vjp_params_out* out, const tt_obca_scenes* scenes) {
-    const double* obs = scenes ? scenes->obstacles : nullptr;
-    Handle* h = static_cast<Handle*>(handle);
-    // (the adjoint does not read d_min, but a scene the solve would have refused is refused here too)
-    if (h && is_obca(h->cfg) && scenes && scenes->d_min)
-        if (const int rc = check_scenes(h, B, nullptr, scenes->d_min)) return rc;
-    if (out && plain_adjoint(out)) {
-        const tt_obca_vjp_out o = {out->g_x0, out->g_xref, out->g_uref, out->vjp_status};
-        return obca_vjp_host(handle, B, iterate, status, grad_x, grad_u, &o, obs);
-    }
-    return obca_vjp_params_host(handle, B, iterate, status, xref, uref, grad_x, grad_u, out, obs);
-}
-
-// tt_obca_vjp_geometry*: the first eight members are tt_obca_vjp_params_out's
-static tt_obca_vjp_params_out params_members(const tt_obca_vjp_geometry_out* o) {
-    return {o->g_x0, o->g_xref, o->g_uref, o->vjp_status, o->g_obstacles, o->g_dmin, o->g_Q, o->g_R};
+    tt_obca_vjp_geometry_out o;
+    return tt_obca_vjp_geometry(handle, B, iterate, status, xref, uref, grad_x, grad_u, widen(out, o), scenes);
 }
 
 int tt_obca_vjp_geometry_device(void* handle, int B, const double* d_iterate, const int* d_status,
                                 const double* d_xref, const double* d_uref, const double* d_grad_x,
                                 const double* d_grad_u, const tt_obca_vjp_geometry_out* d_out, void* d_work,
                                 const tt_obca_scenes* d_scenes, void* stream) {
-    if (!d_out || !d_out->g_geometry) {  // no geometry wanted: tt_obca_vjp_scenes_device, its kernels and its bits
-        tt_obca_vjp_params_out o;
-        if (d_out) o = params_members(d_out);
-        return tt_obca_vjp_scenes_device(handle, B, d_iterate, d_status, d_xref, d_uref, d_grad_x, d_grad_u,
-                                         d_out ? &o : nullptr, d_work, d_scenes, stream);
-    }
-    const tt_obca_vjp_params_out o = params_members(d_out);
-    return obca_vjp_params_device(handle, B, d_iterate, d_status, d_xref, d_uref, d_grad_x, d_grad_u, &o, d_work,
-                                  d_scenes ? d_scenes->obstacles : nullptr, stream, d_out->g_geometry);
+    return obca_vjp_device(handle, B, d_iterate, d_status, d_xref, d_uref, d_grad_x, d_grad_u, d_out, d_work,
+                           d_scenes ? d_scenes->obstacles : nullptr, obca_vjp_kind(d_out, d_work), stream);
 }
 
 int tt_obca_vjp_geometry(void* handle, int B, const double* iterate, const int* status, const double* xref,
                          const double* uref, const double* grad_x, const double* grad_u,
                          const tt_obca_vjp_geometry_out* out, const tt_obca_scenes* scenes) {
-    if (!out || !out->g_geometry) {
-        tt_obca_vjp_params_out o;
-        if (out) o = params_members(out);
-        return tt_obca_vjp_scenes(handle, B, iterate, status, xref, uref, grad_x, grad_u, out ? &o : nullptr, scenes);
-    }
-    Handle* h = static_cast<Handle*>(handle);
-    if (h && is_obca(h->cfg) && scenes && scenes->d_min)  // (as tt_obca_vjp_scenes: a scene the solve would have refused)
-        if (const int rc = check_scenes(h, B, nullptr, scenes->d_min)) return rc;
-    const tt_obca_vjp_params_out o = params_members(out);
-    return obca_vjp_params_host(handle, B, iterate, status, xref, uref, grad_x, grad_u, &o,
-                                scenes ? scenes->obstacles : nullptr, out->g_geometry);
+    return obca_vjp_host(handle, B, iterate, status, xref, uref, grad_x, grad_u, out, scenes,
+                         obca_vjp_kind(out, nullptr));
 }
 
 int tt_set_geometry(void* handle, double L1, double L2, double Mh, double W1, double W2) {

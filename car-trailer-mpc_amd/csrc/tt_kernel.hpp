@@ -222,7 +222,6 @@ inline int obca_vjp_lds_doubles(int N) { return kObcaVjpStage * (N + 1) + 12 * N
 inline int obca_vjp_max_horizon() {  // (512 bytes stay free for the compiler's own LDS)
     return ((64 * 1024 - 512) / 8 - kObcaVjpFixed - kObcaVjpStage) / (kObcaVjpStage + 12);
 }
-hipError_t launch_obca_vjp(const ObcaVjpArgs& a, hipStream_t stream);
 // the same adjoint plus dL/d(obstacles, d_min, Q, R): the kernel's params instantiation (the same LDS record).  The
 // members sit behind ObcaVjpArgs so that the plain instantiation's argument block, and with it its code, stays what it
 // was.  The block unknowns (16 per block) are carried across the refinement steps in `work`
@@ -236,13 +235,15 @@ struct ObcaVjpParamsArgs : ObcaVjpArgs {
     double* work;         // [B][2M(N+1)][16]: one 128-byte record per block, never nullptr here
 };
 __host__ __device__ inline size_t obca_vjp_params_work_doubles(int N, int M) { return (size_t)32 * M * (N + 1); }
-hipError_t launch_obca_vjp_params(const ObcaVjpParamsArgs& a, hipStream_t stream);
 // the params adjoint plus dL/d(L1, L2, Mh, W1, W2): the kernel's geometry instantiation (the same LDS record and the
 // same workspace).  The member sits behind ObcaVjpParamsArgs so that the plain and the params instantiations'
 // argument blocks, and with them their code, stay what they were
 struct ObcaVjpGeomArgs : ObcaVjpParamsArgs {
     double* g_geom;       // [B][5] (L1, L2, Mh, W1, W2), never nullptr here
 };
-hipError_t launch_obca_vjp_geom(const ObcaVjpGeomArgs& a, hipStream_t stream);
+// one launch for the three instantiations: the widest block, of which each kernel takes its own base (work is needed
+// by the params and geometry kinds, g_geom by the geometry kind)
+enum ObcaVjpKind { kObcaVjpPlain, kObcaVjpParams, kObcaVjpGeom };
+hipError_t launch_obca_vjp(const ObcaVjpGeomArgs& a, ObcaVjpKind kind, hipStream_t stream);
 
 }  // namespace ttmpc

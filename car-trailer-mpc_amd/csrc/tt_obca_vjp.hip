@@ -926,24 +926,19 @@ __global__ __launch_bounds__(kT) void obca_vjp_kernel(
 
 }  // namespace
 
-hipError_t launch_obca_vjp(const ObcaVjpArgs& a, hipStream_t stream) {
+hipError_t launch_obca_vjp(const ObcaVjpGeomArgs& a, ObcaVjpKind kind, hipStream_t stream) {
     const int bytes = 8 * obca_vjp_lds_doubles(a.N);
     if (bytes > 64 * 1024 - 512 || a.M < 1 || a.M > kObcaMaxM) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(obca_vjp_kernel<false>, dim3(a.B), dim3(kT), bytes, stream, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_obca_vjp_params(const ObcaVjpParamsArgs& a, hipStream_t stream) {
-    const int bytes = 8 * obca_vjp_lds_doubles(a.N);
-    if (bytes > 64 * 1024 - 512 || a.M < 1 || a.M > kObcaMaxM || !a.work) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(obca_vjp_kernel<true>, dim3(a.B), dim3(kT), bytes, stream, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_obca_vjp_geom(const ObcaVjpGeomArgs& a, hipStream_t stream) {
-    const int bytes = 8 * obca_vjp_lds_doubles(a.N);
-    if (bytes > 64 * 1024 - 512 || a.M < 1 || a.M > kObcaMaxM || !a.work || !a.g_geom) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((obca_vjp_kernel<true, true>), dim3(a.B), dim3(kT), bytes, stream, a);
+    if ((kind != kObcaVjpPlain && !a.work) || (kind == kObcaVjpGeom && !a.g_geom)) return hipErrorInvalidValue;
+    // each instantiation takes its own base of the block: the narrower ones' arguments are what they were
+    if (kind == kObcaVjpPlain)
+        hipLaunchKernelGGL(obca_vjp_kernel<false>, dim3(a.B), dim3(kT), bytes, stream,
+                           static_cast<const ObcaVjpArgs&>(a));
+    else if (kind == kObcaVjpParams)
+        hipLaunchKernelGGL(obca_vjp_kernel<true>, dim3(a.B), dim3(kT), bytes, stream,
+                           static_cast<const ObcaVjpParamsArgs&>(a));
+    else
+        hipLaunchKernelGGL((obca_vjp_kernel<true, true>), dim3(a.B), dim3(kT), bytes, stream, a);
     return hipGetLastError();
 }
 

@@ -189,175 +189,100 @@ def lib():
         raise TTError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`"
                       " (ttmpc is GPU-only; there is no CPU fallback)")
     L = C.CDLL(str(LIB_PATH))
-    L.tt_create.argtypes = [C.POINTER(TTConfig), _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int, C.POINTER(C.c_void_p)]
-    L.tt_create.restype = C.c_int
-    L.tt_solve_batch.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp]
-    L.tt_solve_batch.restype = C.c_int
-    L.tt_solve_batch_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 10 + [C.c_void_p]
-    L.tt_solve_batch_device.restype = C.c_int
-    if not os.environ.get("TTMPC_LIB") or hasattr(L, "tt_track_dual_len"):  # (A/B against a build without them)
-        L.tt_solve_batch_ex.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp,
-                                        C.POINTER(TTTrackExtra)]
-        L.tt_solve_batch_ex.restype = C.c_int
-        L.tt_solve_batch_ex_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 10 + [C.POINTER(TTTrackExtra),
-                                                                                          C.c_void_p]
-        L.tt_solve_batch_ex_device.restype = C.c_int
-        L.tt_track_sens_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 10
-        L.tt_track_sens_device.restype = C.c_int
-        L.tt_track_dual_len.argtypes = [C.c_int]
-        L.tt_track_dual_len.restype = C.c_longlong
-    if not os.environ.get("TTMPC_LIB") or hasattr(L, "tt_track_vjp_device"):  # (A/B against a build without them)
-        L.tt_track_vjp_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 9 + [C.POINTER(TTTrackVjpOut),
-                                                                                    C.c_void_p]
-        L.tt_track_vjp_device.restype = C.c_int
-        L.tt_track_vjp.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp,
-                                   C.POINTER(TTTrackVjpOut)]
-        L.tt_track_vjp.restype = C.c_int
-    if not os.environ.get("TTMPC_LIB") or hasattr(L, "tt_track_vjp_model_device"):  # (A/B against a build without them)
-        L.tt_track_vjp_model_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 9 + [
-            C.POINTER(TTTrackVjpModelOut), C.c_int, C.c_void_p]
-        L.tt_track_vjp_model_device.restype = C.c_int
-        L.tt_track_vjp_model.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp,
-                                         C.POINTER(TTTrackVjpModelOut), C.c_int]
-        L.tt_track_vjp_model.restype = C.c_int
-        L.tt_set_model.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double]
-        L.tt_set_model.restype = C.c_int
-        L.tt_get_model.argtypes = [C.c_void_p, _dp, _dp, _dp]
-        L.tt_get_model.restype = C.c_int
-    if not os.environ.get("TTMPC_LIB") or hasattr(L, "tt_track_vjp_bounds_device"):  # (A/B against a build without them)
-        L.tt_track_vjp_bounds_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 9 + [
-            C.POINTER(TTTrackVjpBoundsOut), C.c_int, C.c_void_p]
-        L.tt_track_vjp_bounds_device.restype = C.c_int
-        L.tt_track_vjp_bounds.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp,
-                                          C.POINTER(TTTrackVjpBoundsOut), C.c_int]
-        L.tt_track_vjp_bounds.restype = C.c_int
-        L.tt_set_bounds.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp]
-        L.tt_set_bounds.restype = C.c_int
-        L.tt_get_bounds.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp]
-        L.tt_get_bounds.restype = C.c_int
-    L.tt_plan_batch.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _ip]
-    L.tt_plan_batch.restype = C.c_int
-    L.tt_obca_solve_batch.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp]
-    L.tt_obca_solve_batch.restype = C.c_int
-    L.tt_obca_solve_batch_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 12
-    L.tt_obca_solve_batch_device.restype = C.c_int
-    if not os.environ.get("TTMPC_LIB") or hasattr(L, "tt_obca_iterate_len"):  # (A/B against a pre-round-5 build)
-        L.tt_obca_solve_batch_iterate.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip,
-                                                  _dp, _dp]
-        L.tt_obca_solve_batch_iterate.restype = C.c_int
-        L.tt_obca_solve_batch_iterate_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 13
-        L.tt_obca_solve_batch_iterate_device.restype = C.c_int
-        L.tt_obca_iterate_len.argtypes = [C.c_int, C.c_int]
-        L.tt_obca_iterate_len.restype = C.c_longlong
-    if not os.environ.get("TTMPC_LIB") or hasattr(L, "tt_obca_vjp_device"):  # (A/B against a build without them)
-        L.tt_obca_vjp_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.POINTER(TTObcaVjpOut), C.c_void_p]
-        L.tt_obca_vjp_device.restype = C.c_int
-        L.tt_obca_vjp.argtypes = [C.c_void_p, C.c_int, _dp, _ip, _dp, _dp, C.POINTER(TTObcaVjpOut)]
-        L.tt_obca_vjp.restype = C.c_int
-    if not os.environ.get("TTMPC_LIB") or hasattr(L, "tt_obca_vjp_params_device"):
-        po = C.POINTER(TTObcaVjpParamsOut)
-        L.tt_obca_vjp_params_work_bytes.argtypes = [C.c_int, C.c_int]
-        L.tt_obca_vjp_params_work_bytes.restype = C.c_longlong
-        L.tt_obca_vjp_params_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [po, C.c_void_p, C.c_void_p]
-        L.tt_obca_vjp_params_device.restype = C.c_int
-        L.tt_obca_vjp_params.argtypes = [C.c_void_p, C.c_int, _dp, _ip, _dp, _dp, _dp, _dp, po]
-        L.tt_obca_vjp_params.restype = C.c_int
-        L.tt_set_scene.argtypes = [C.c_void_p, _dp, _dp]
-        L.tt_set_scene.restype = C.c_int
-        L.tt_get_scene.argtypes = [C.c_void_p, _dp, _dp]
-        L.tt_get_scene.restype = C.c_int
-    if not os.environ.get("TTMPC_LIB") or hasattr(L, "tt_obca_solve_batch_scenes"):  # (A/B against a build without them)
-        po, ps = C.POINTER(TTObcaVjpParamsOut), C.POINTER(TTObcaScenes)
-        L.tt_obca_solve_batch_scenes.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip,
-                                                 _dp, _dp, ps]
-        L.tt_obca_solve_batch_scenes.restype = C.c_int
-        L.tt_obca_solve_batch_scenes_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 12 + [ps, C.c_void_p]
-        L.tt_obca_solve_batch_scenes_device.restype = C.c_int
-        L.tt_obca_vjp_scenes.argtypes = [C.c_void_p, C.c_int, _dp, _ip, _dp, _dp, _dp, _dp, po, ps]
-        L.tt_obca_vjp_scenes.restype = C.c_int
-        L.tt_obca_vjp_scenes_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [po, C.c_void_p, ps,
-                                                                                          C.c_void_p]
-        L.tt_obca_vjp_scenes_device.restype = C.c_int
-    if not os.environ.get("TTMPC_LIB") or hasattr(L, "tt_obca_vjp_geometry_device"):  # (A/B against a build without them)
-        pg, ps = C.POINTER(TTObcaVjpGeometryOut), C.POINTER(TTObcaScenes)
-        L.tt_obca_vjp_geometry.argtypes = [C.c_void_p, C.c_int, _dp, _ip, _dp, _dp, _dp, _dp, pg, ps]
-        L.tt_obca_vjp_geometry.restype = C.c_int
-        L.tt_obca_vjp_geometry_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [pg, C.c_void_p, ps,
-                                                                                            C.c_void_p]
-        L.tt_obca_vjp_geometry_device.restype = C.c_int
-        L.tt_set_geometry.argtypes = [C.c_void_p] + [C.c_double] * 5
-        L.tt_set_geometry.restype = C.c_int
-        L.tt_get_geometry.argtypes = [C.c_void_p] + [_dp] * 5
-        L.tt_get_geometry.restype = C.c_int
-    L.tt_obca_n.argtypes = [C.c_int, C.c_int]
-    L.tt_obca_n.restype = C.c_longlong
-    L.tt_obca_workspace_bytes.argtypes = [C.c_int, C.c_int]
-    L.tt_obca_workspace_bytes.restype = C.c_longlong
-    L.tt_destroy.argtypes = [C.c_void_p]
-    L.tt_destroy.restype = None
-    L.tt_last_error.argtypes = [C.c_void_p]
-    L.tt_last_error.restype = C.c_char_p
-    L.tt_lds_bytes.argtypes = [C.c_int]
-    L.tt_lds_bytes.restype = C.c_int
-    L.tt_max_horizon.argtypes = []
-    L.tt_max_horizon.restype = C.c_int
-    L.tt_version.argtypes = []
-    L.tt_version.restype = C.c_char_p
-    vp, i, ll = C.c_void_p, C.c_int, C.c_longlong
-    sim = {"tt_sim_window_device": [i, i, i, i, vp, vp, i, vp, vp, vp, vp, vp, vp],
-           "tt_collision_device": [i, i, vp, ll, i, vp, i, C.POINTER(TTPlant), vp, vp],
-           "tt_collision_scenes_device": [i, i, vp, ll, i, vp, i, C.POINTER(TTPlant), vp, vp],
-           "tt_plant_update_device": [i, C.POINTER(TTPlant), vp, vp, ll, vp, i, vp, vp],
-           "tt_warm_start_device": [i, i, vp, vp, vp, vp, i, vp, vp],
-           "tt_record_solution_device": [i, i, vp, vp, vp, vp, vp, vp],
-           "tt_interpolate_device": [i, i, i, vp, vp, vp, vp, vp],
-           "tt_lqr_score_device": [i, C.POINTER(TTPlant), _dp, _dp, vp, vp, vp, vp, vp, vp, vp],
-           "tt_sim_window_indexed_device": [i, i, vp, vp, i, vp, vp, i, vp, vp, vp, vp, vp, vp],
-           "tt_sim_log_advance_device": [i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-           "tt_policy_plant_device": [i, C.POINTER(TTPlant), i, vp, vp, ll, vp, vp, vp, vp, vp, vp, vp],
-           "tt_plant_update_noise_device": [i, C.POINTER(TTPlant), vp, vp, ll, vp, i, vp, vp, vp],
-           "tt_policy_plant_noise_device": [i, C.POINTER(TTPlant), i, vp, vp, ll, vp, vp, vp, vp, vp, vp, vp, vp],
-           "tt_fuzzy_weights_device": [i, i, vp, vp, vp, vp],
-           "tt_policy_plant_vjp_device": [i, i, C.POINTER(TTPlant), i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-           "tt_policy_plant_vjp_model_device": [i, i, C.POINTER(TTPlant), i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                                vp],
-           "tt_sim_window_vjp_device": [i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-           "tt_fuzzy_weights_rule_device": [i, i, C.POINTER(TTFuzzyRule), vp, vp, vp, vp],
-           "tt_fuzzy_weights_vjp_device": [i, i, C.POINTER(TTFuzzyRule), vp, vp, vp, vp, vp, vp, vp],
-           "tt_sim_window_vjp_fuzzy_device": [i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(TTFuzzyRule),
-                                              vp, vp, vp, vp, vp],
-           "tt_lqr_score_vjp_device": [i, C.POINTER(TTPlant), _dp, vp, vp, vp, vp, vp, vp, C.POINTER(TTLqrVjpOut),
-                                       vp]}
-    sim["ttx_obca_set_helpers"] = [C.c_void_p, i]  # diagnostics (not in include/ttmpc.h)
-    sim["ttx_obca_set_handoff_debug"] = [C.c_void_p, ll, i]
-    for name, args in sim.items():
+    for name, (argtypes, restype) in _SIGNATURES.items():
         if os.environ.get("TTMPC_LIB") and not hasattr(L, name):
-            continue  # A/B diagnostics against an older build
+            continue  # A/B diagnostics against an older build (otherwise a missing name is an error)
         fn = getattr(L, name)
-        fn.argtypes = args
-        fn.restype = C.c_int
+        fn.argtypes = argtypes
+        fn.restype = restype
     _lib = L
     return L
 
 
-EXPORTED_SYMBOLS = ("tt_create", "tt_solve_batch", "tt_solve_batch_device", "tt_plan_batch", "tt_obca_solve_batch",
-                    "tt_obca_solve_batch_device", "tt_obca_solve_batch_iterate", "tt_obca_solve_batch_iterate_device",
-                    "tt_obca_iterate_len", "tt_obca_n", "tt_obca_workspace_bytes", "tt_destroy",
-                    "tt_last_error", "tt_lds_bytes", "tt_max_horizon", "tt_version", "tt_sim_window_device",
-                    "tt_collision_device", "tt_plant_update_device", "tt_warm_start_device",
-                    "tt_record_solution_device", "tt_interpolate_device", "tt_lqr_score_device",
-                    "tt_sim_window_indexed_device", "tt_sim_log_advance_device", "tt_policy_plant_device",
-                    "tt_fuzzy_weights_device", "tt_plant_update_noise_device", "tt_policy_plant_noise_device",
-                    "tt_track_dual_len", "tt_solve_batch_ex", "tt_solve_batch_ex_device", "tt_track_sens_device",
-                    "tt_track_vjp_device", "tt_track_vjp", "tt_policy_plant_vjp_device", "tt_sim_window_vjp_device",
-                    "tt_lqr_score_vjp_device", "tt_track_vjp_model_device", "tt_track_vjp_model", "tt_set_model",
-                    "tt_get_model", "tt_policy_plant_vjp_model_device", "tt_fuzzy_weights_rule_device",
-                    "tt_fuzzy_weights_vjp_device", "tt_sim_window_vjp_fuzzy_device", "tt_obca_vjp_device",
-                    "tt_obca_vjp", "tt_obca_vjp_params_work_bytes", "tt_obca_vjp_params_device", "tt_obca_vjp_params",
-                    "tt_set_scene", "tt_get_scene", "tt_obca_solve_batch_scenes", "tt_obca_solve_batch_scenes_device",
-                    "tt_obca_vjp_scenes", "tt_obca_vjp_scenes_device", "tt_collision_scenes_device",
-                    "tt_obca_vjp_geometry", "tt_obca_vjp_geometry_device", "tt_set_geometry", "tt_get_geometry",
-                    "tt_track_vjp_bounds_device", "tt_track_vjp_bounds", "tt_set_bounds", "tt_get_bounds")
+def _signatures():
+    """name -> (argtypes, restype) of every entry ``lib()`` binds: include/ttmpc.h, then the ttx_* diagnostics."""
+    vp, i, ll, d, dp, ip, P = C.c_void_p, C.c_int, C.c_longlong, C.c_double, _dp, _ip, C.POINTER
+    plant, rule = P(TTPlant), P(TTFuzzyRule)
+    track_in = [vp, i, dp, dp, dp, dp, dp]          # handle, B, x0, xref, uref, wq_wr, z_guess
+    track_vjp = [vp, i, dp, dp, dp, dp, dp, dp, ip, dp, dp]
+    obca_in = [vp, i, dp, dp, dp, dp, dp]           # handle, B, x0, xgoal, xref, uref, z_guess
+    obca_out = [dp, dp, dp, ip, ip, dp]             # X, U, z, status, iters, kkt
+    # the out-struct of the OBCA adjoint entries goes as a plain address: tt_obca_vjp_out and tt_obca_vjp_params_out
+    # are prefixes of tt_obca_vjp_geometry_out, so one TTObcaVjpGeometryOut serves all eight
+    obca_vjp = [vp, i, dp, ip, dp, dp, dp, dp, vp]  # handle, B, iterate, status, xref, uref, grad_x, grad_u, out
+    scenes = P(TTObcaScenes)
+    ints = {  # the entries that return an int; the others follow
+        "tt_create": [P(TTConfig), dp, dp, dp, dp, dp, dp, dp, i, P(vp)],
+        "tt_solve_batch": track_in + [dp, dp, ip, ip, dp],
+        "tt_solve_batch_device": [vp, i] + [vp] * 11,
+        "tt_solve_batch_ex": track_in + [dp, dp, ip, ip, dp, P(TTTrackExtra)],
+        "tt_solve_batch_ex_device": [vp, i] + [vp] * 10 + [P(TTTrackExtra), vp],
+        "tt_track_sens_device": [vp, i] + [vp] * 10,
+        "tt_track_vjp_device": [vp, i] + [vp] * 9 + [P(TTTrackVjpOut), vp],
+        "tt_track_vjp": track_vjp + [P(TTTrackVjpOut)],
+        "tt_track_vjp_model_device": [vp, i] + [vp] * 9 + [P(TTTrackVjpModelOut), i, vp],
+        "tt_track_vjp_model": track_vjp + [P(TTTrackVjpModelOut), i],
+        "tt_set_model": [vp, d, d, d],
+        "tt_get_model": [vp, dp, dp, dp],
+        "tt_track_vjp_bounds_device": [vp, i] + [vp] * 9 + [P(TTTrackVjpBoundsOut), i, vp],
+        "tt_track_vjp_bounds": track_vjp + [P(TTTrackVjpBoundsOut), i],
+        "tt_set_bounds": [vp, dp, dp, dp, dp],
+        "tt_get_bounds": [vp, dp, dp, dp, dp],
+        "tt_plan_batch": [vp, i, dp, dp, dp, dp, dp, ip, ip],
+        "tt_obca_solve_batch": obca_in + obca_out,
+        "tt_obca_solve_batch_device": [vp, i] + [vp] * 12,
+        "tt_obca_solve_batch_iterate": obca_in + obca_out + [dp],
+        "tt_obca_solve_batch_iterate_device": [vp, i] + [vp] * 13,
+        "tt_obca_solve_batch_scenes": obca_in + obca_out + [dp, scenes],
+        "tt_obca_solve_batch_scenes_device": [vp, i] + [vp] * 12 + [scenes, vp],
+        "tt_obca_vjp": [vp, i, dp, ip, dp, dp, vp],
+        "tt_obca_vjp_device": [vp, i] + [vp] * 4 + [vp, vp],
+        "tt_obca_vjp_params": obca_vjp,
+        "tt_obca_vjp_params_device": [vp, i] + [vp] * 6 + [vp, vp, vp],
+        "tt_obca_vjp_scenes": obca_vjp + [scenes],
+        "tt_obca_vjp_scenes_device": [vp, i] + [vp] * 6 + [vp, vp, scenes, vp],
+        "tt_obca_vjp_geometry": obca_vjp + [scenes],
+        "tt_obca_vjp_geometry_device": [vp, i] + [vp] * 6 + [vp, vp, scenes, vp],
+        "tt_set_scene": [vp, dp, dp],
+        "tt_get_scene": [vp, dp, dp],
+        "tt_set_geometry": [vp] + [d] * 5,
+        "tt_get_geometry": [vp] + [dp] * 5,
+        "tt_lds_bytes": [i],
+        "tt_max_horizon": [],
+        "tt_sim_window_device": [i, i, i, i, vp, vp, i, vp, vp, vp, vp, vp, vp],
+        "tt_collision_device": [i, i, vp, ll, i, vp, i, plant, vp, vp],
+        "tt_collision_scenes_device": [i, i, vp, ll, i, vp, i, plant, vp, vp],
+        "tt_plant_update_device": [i, plant, vp, vp, ll, vp, i, vp, vp],
+        "tt_warm_start_device": [i, i, vp, vp, vp, vp, i, vp, vp],
+        "tt_record_solution_device": [i, i, vp, vp, vp, vp, vp, vp],
+        "tt_interpolate_device": [i, i, i, vp, vp, vp, vp, vp],
+        "tt_lqr_score_device": [i, plant, dp, dp, vp, vp, vp, vp, vp, vp, vp],
+        "tt_sim_window_indexed_device": [i, i, vp, vp, i, vp, vp, i, vp, vp, vp, vp, vp, vp],
+        "tt_sim_log_advance_device": [i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "tt_policy_plant_device": [i, plant, i, vp, vp, ll, vp, vp, vp, vp, vp, vp, vp],
+        "tt_plant_update_noise_device": [i, plant, vp, vp, ll, vp, i, vp, vp, vp],
+        "tt_policy_plant_noise_device": [i, plant, i, vp, vp, ll, vp, vp, vp, vp, vp, vp, vp, vp],
+        "tt_fuzzy_weights_device": [i, i, vp, vp, vp, vp],
+        "tt_policy_plant_vjp_device": [i, i, plant, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "tt_policy_plant_vjp_model_device": [i, i, plant, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "tt_sim_window_vjp_device": [i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "tt_fuzzy_weights_rule_device": [i, i, rule, vp, vp, vp, vp],
+        "tt_fuzzy_weights_vjp_device": [i, i, rule, vp, vp, vp, vp, vp, vp, vp],
+        "tt_sim_window_vjp_fuzzy_device": [i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, rule, vp, vp, vp, vp, vp],
+        "tt_lqr_score_vjp_device": [i, plant, dp, vp, vp, vp, vp, vp, vp, P(TTLqrVjpOut), vp],
+        "ttx_obca_set_helpers": [vp, i],  # diagnostics (not in include/ttmpc.h)
+        "ttx_obca_set_handoff_debug": [vp, ll, i],
+    }
+    sigs = {name: (args, i) for name, args in ints.items()}
+    sigs.update({"tt_track_dual_len": ([i], ll), "tt_obca_iterate_len": ([i, i], ll),
+                 "tt_obca_vjp_params_work_bytes": ([i, i], ll), "tt_obca_n": ([i, i], ll),
+                 "tt_obca_workspace_bytes": ([i, i], ll), "tt_destroy": ([vp], None),
+                 "tt_last_error": ([vp], C.c_char_p), "tt_version": ([], C.c_char_p)})
+    return sigs
+
+
+_SIGNATURES = _signatures()
+EXPORTED_SYMBOLS = tuple(name for name in _SIGNATURES if not name.startswith("ttx_"))  # (tests/test_abi.py)
 
 
 def _ptr(a):
@@ -609,22 +534,21 @@ class BatchSolver(_Solver):
         without g_model it launches the plain kernel instantiation, as tt_track_vjp_device does.  g_bounds (B,16): also
         dL/d(xlb 6, ulb 2, xub 6, uub 2) per instance, written or added as g_model is, from the same launch
         (tt_track_vjp_bounds_device; without it the call and its bits are the ones above)."""
-        if g_bounds:
-            out = TTTrackVjpBoundsOut(g_x0 or None, g_xref or None, g_uref or None, g_wq_wr or None, g_model or None,
-                                      g_bounds, vjp_status or None)
-            rc = self._L.tt_track_vjp_bounds_device(self._h, int(B), x, u, dual, xref or None, uref or None,
-                                                    wq_wr or None, status, grad_x or None, grad_u or None,
-                                                    C.byref(out), int(bool(accumulate)), stream or None)
-            if rc != 0:
-                self._err(rc, "tt_track_vjp_bounds_device")
-            return
-        out = TTTrackVjpModelOut(g_x0 or None, g_xref or None, g_uref or None, g_wq_wr or None, g_model or None,
-                                 vjp_status or None)
-        rc = self._L.tt_track_vjp_model_device(self._h, int(B), x, u, dual, xref or None, uref or None, wq_wr or None,
-                                               status, grad_x or None, grad_u or None, C.byref(out),
-                                               int(bool(accumulate)), stream or None)
+        self._vjp_call(True, (int(B), x, u, dual, xref or None, uref or None, wq_wr or None, status, grad_x or None,
+                              grad_u or None),
+                       [p or None for p in (g_x0, g_xref, g_uref, g_wq_wr, g_model, g_bounds, vjp_status)],
+                       (int(bool(accumulate)), stream or None))
+
+    def _vjp_call(self, device, args, outs, tail):
+        """The one library call behind ``vjp`` and ``vjp_device``.  outs: the seven members of tt_track_vjp_bounds_out as
+        addresses (None = not wanted).  tt_track_vjp_bounds* with g_bounds, else tt_track_vjp_model*, whose out-struct
+        has no such member; an error names the narrowest entry that carries what was asked for."""
+        g_model, g_bounds = outs[4], outs[5]
+        out = TTTrackVjpBoundsOut(*outs) if g_bounds else TTTrackVjpModelOut(*outs[:5], outs[6])
+        name = "tt_track_vjp" + ("_bounds" if g_bounds else "_model") + ("_device" if device else "")
+        rc = getattr(self._L, name)(self._h, *args, C.byref(out), *tail)
         if rc != 0:
-            self._err(rc, "tt_track_vjp_model_device" if g_model else "tt_track_vjp_device")
+            self._err(rc, name if g_bounds or g_model else name.replace("_model", ""))
 
     def vjp(self, x, u, dual, xref, uref, status, grad_x, grad_u, wq_wr=None, model=False, bounds=False):
         """Host arrays: the gradient of a scalar loss L(X, U) with respect to the inputs of the solve that returned
@@ -649,20 +573,10 @@ class BatchSolver(_Solver):
         r = TrackVjpResult(g_x0=np.empty((B, 6)), g_xref=np.empty((B, N + 1, 6)), g_uref=np.empty((B, N, 2)),
                            g_wq_wr=np.empty((B, 8)), g_model=np.empty((B, 3)) if model else None,
                            g_bounds=np.empty((B, 16)) if bounds else None, vjp_status=np.empty(B, dtype=np.int32))
-        if bounds:
-            out = TTTrackVjpBoundsOut(*[None if a is None else a.ctypes.data for a in (
-                r.g_x0, r.g_xref, r.g_uref, r.g_wq_wr, r.g_model, r.g_bounds, r.vjp_status)])
-            rc = self._L.tt_track_vjp_bounds(self._h, B, _ptr(x), _ptr(u), _ptr(dual), _ptr(xref), _ptr(uref), _ptr(w),
-                                             st.ctypes.data_as(_ip), _ptr(gx), _ptr(gu), C.byref(out), 0)
-            if rc != 0:
-                self._err(rc, "tt_track_vjp_bounds")
-            return r
-        out = TTTrackVjpModelOut(*[None if a is None else a.ctypes.data for a in (r.g_x0, r.g_xref, r.g_uref, r.g_wq_wr,
-                                                                                   r.g_model, r.vjp_status)])
-        rc = self._L.tt_track_vjp_model(self._h, B, _ptr(x), _ptr(u), _ptr(dual), _ptr(xref), _ptr(uref), _ptr(w),
-                                        st.ctypes.data_as(_ip), _ptr(gx), _ptr(gu), C.byref(out), 0)
-        if rc != 0:
-            self._err(rc, "tt_track_vjp_model" if model else "tt_track_vjp")
+        self._vjp_call(False, (B, _ptr(x), _ptr(u), _ptr(dual), _ptr(xref), _ptr(uref), _ptr(w), st.ctypes.data_as(_ip),
+                               _ptr(gx), _ptr(gu)),
+                       [None if a is None else a.ctypes.data for a in (r.g_x0, r.g_xref, r.g_uref, r.g_wq_wr, r.g_model,
+                                                                       r.g_bounds, r.vjp_status)], (0,))
         return r
 
 
@@ -858,40 +772,34 @@ class ObcaSolver(_Solver):
 
         g_geometry (B,5): also dL/d(L1, L2, M, W1, W2) per instance at the handle's geometry
         (tt_obca_vjp_geometry_device; needs ``work``); the other outputs are bitwise those of the call without it."""
-        if g_geometry:
-            gout = TTObcaVjpGeometryOut(g_x0 or None, g_xref or None, g_uref or None, vjp_status or None,
-                                        g_obstacles or None, g_dmin or None, g_Q or None, g_R or None, g_geometry)
-            sc = TTObcaScenes(obstacles or None, d_min or None)
-            rc = self._L.tt_obca_vjp_geometry_device(self._h, int(B), iterate or None, status or None, xref or None,
-                                                     uref or None, grad_x or None, grad_u or None, C.byref(gout),
-                                                     work or None, C.byref(sc), stream or None)
-            if rc != 0:
-                self._err(rc, "tt_obca_vjp_geometry_device")
-            return
-        if obstacles or d_min:
-            pout = TTObcaVjpParamsOut(g_x0 or None, g_xref or None, g_uref or None, vjp_status or None,
-                                      g_obstacles or None, g_dmin or None, g_Q or None, g_R or None)
-            sc = TTObcaScenes(obstacles or None, d_min or None)
-            rc = self._L.tt_obca_vjp_scenes_device(self._h, int(B), iterate or None, status or None, xref or None,
-                                                   uref or None, grad_x or None, grad_u or None, C.byref(pout),
-                                                   work or None, C.byref(sc), stream or None)
-            if rc != 0:
-                self._err(rc, "tt_obca_vjp_scenes_device")
-            return
-        if work or g_obstacles or g_dmin or g_Q or g_R:
-            pout = TTObcaVjpParamsOut(g_x0 or None, g_xref or None, g_uref or None, vjp_status or None,
-                                      g_obstacles or None, g_dmin or None, g_Q or None, g_R or None)
-            rc = self._L.tt_obca_vjp_params_device(self._h, int(B), iterate or None, status or None, xref or None,
-                                                   uref or None, grad_x or None, grad_u or None, C.byref(pout),
-                                                   work or None, stream or None)
-            if rc != 0:
-                self._err(rc, "tt_obca_vjp_params_device")
-            return
-        out = TTObcaVjpOut(g_x0 or None, g_xref or None, g_uref or None, vjp_status or None)
-        rc = self._L.tt_obca_vjp_device(self._h, int(B), iterate or None, status or None, grad_x or None,
-                                        grad_u or None, C.byref(out), stream or None)
+        self._vjp_call(True, B, iterate or None, status or None, xref or None, uref or None, grad_x or None,
+                       grad_u or None, [p or None for p in (g_x0, g_xref, g_uref, vjp_status, g_obstacles, g_dmin, g_Q,
+                                                             g_R, g_geometry)],
+                       TTObcaScenes(obstacles or None, d_min or None), work or None, stream or None)
+
+    def _vjp_call(self, device, B, iterate, status, xref, uref, grad_x, grad_u, outs, scenes, work=None, stream=None):
+        """The one library call behind ``vjp`` and ``vjp_device``.  outs: the nine members of tt_obca_vjp_geometry_out
+        as addresses (None = not wanted); the narrower out-structs are prefixes of it.  The entry is the narrowest that
+        carries what was asked for: geometry with g_geometry, else scenes with a per-instance scene, else params with
+        ``work`` or a parameter output, else the plain one."""
+        out = TTObcaVjpGeometryOut(*outs)
+        if out.g_geometry:
+            name = "tt_obca_vjp_geometry"
+        elif scenes.obstacles or scenes.d_min:
+            name = "tt_obca_vjp_scenes"
+        elif work or out.g_obstacles or out.g_dmin or out.g_Q or out.g_R:
+            name = "tt_obca_vjp_params"
+        else:
+            name = "tt_obca_vjp"
+        args = [self._h, int(B), iterate, status] + ([xref, uref] if name != "tt_obca_vjp" else [])
+        args += [grad_x, grad_u, C.byref(out)] + ([work] if device and name != "tt_obca_vjp" else [])
+        args += [C.byref(scenes)] if name in ("tt_obca_vjp_geometry", "tt_obca_vjp_scenes") else []
+        if device:
+            name += "_device"
+            args.append(stream)
+        rc = getattr(self._L, name)(*args)
         if rc != 0:
-            self._err(rc, "tt_obca_vjp_device")
+            self._err(rc, name)
 
     def vjp(self, iterate, status, grad_x, grad_u, xref=None, uref=None, params=False, obstacles=None, d_min=None,
             geometry=False):
@@ -907,67 +815,25 @@ class ObcaSolver(_Solver):
 
         ``geometry=True`` implies ``params=True`` and adds g_geometry (B,5) = dL/d(L1, L2, M, W1, W2) per instance
         (tt_obca_vjp_geometry); the other arrays are bitwise those of the params call."""
-        if params or geometry:
-            return self._vjp_params(iterate, status, grad_x, grad_u, xref, uref, obstacles, d_min, geometry)
-        N = self.N
-        I = _f64(iterate).reshape(-1, self.iterate_len())
-        B = I.shape[0]
-        if obstacles is not None or d_min is not None:
-            ob, dm, sc = self._scenes(B, obstacles, d_min)
-        st = np.ascontiguousarray(np.asarray(status, dtype=np.int32)).reshape(B)
-        gx = None if grad_x is None else _f64(grad_x, (B, N + 1, 6))
-        gu = None if grad_u is None else _f64(grad_u, (B, N, 2))
-        r = TrackVjpResult(g_x0=np.empty((B, 6)), g_xref=np.empty((B, N + 1, 6)), g_uref=np.empty((B, N, 2)),
-                           vjp_status=np.empty(B, dtype=np.int32))
-        out = TTObcaVjpOut(r.g_x0.ctypes.data, r.g_xref.ctypes.data, r.g_uref.ctypes.data, r.vjp_status.ctypes.data)
-        if obstacles is not None or d_min is not None:
-            pout = TTObcaVjpParamsOut(r.g_x0.ctypes.data, r.g_xref.ctypes.data, r.g_uref.ctypes.data,
-                                      r.vjp_status.ctypes.data, None, None, None, None)
-            rc = self._L.tt_obca_vjp_scenes(self._h, B, _ptr(I), st.ctypes.data_as(_ip), None, None, _ptr(gx), _ptr(gu),
-                                            C.byref(pout), C.byref(sc))
-            if rc != 0:
-                self._err(rc, "tt_obca_vjp_scenes")
-            return r
-        rc = self._L.tt_obca_vjp(self._h, B, _ptr(I), st.ctypes.data_as(_ip), _ptr(gx), _ptr(gu), C.byref(out))
-        if rc != 0:
-            self._err(rc, "tt_obca_vjp")
-        return r
-
-    def _vjp_params(self, iterate, status, grad_x, grad_u, xref, uref, obstacles=None, d_min=None, geometry=False):
         N, M = self.N, self.M
+        params = params or geometry
         I = _f64(iterate).reshape(-1, self.iterate_len())
         B = I.shape[0]
-        if obstacles is not None or d_min is not None or geometry:
-            ob, dm, sc = self._scenes(B, obstacles, d_min)
+        ob, dm, sc = self._scenes(B, obstacles, d_min)
         st = np.ascontiguousarray(np.asarray(status, dtype=np.int32)).reshape(B)
         gx = None if grad_x is None else _f64(grad_x, (B, N + 1, 6))
         gu = None if grad_u is None else _f64(grad_u, (B, N, 2))
-        xr = None if xref is None else _f64(xref, (B, N + 1, 6))
-        ur = None if uref is None else _f64(uref, (B, N, 2))
-        r = ObcaVjpParamsResult(g_x0=np.empty((B, 6)), g_xref=np.empty((B, N + 1, 6)), g_uref=np.empty((B, N, 2)),
-                                vjp_status=np.empty(B, dtype=np.int32), g_obstacles=np.empty((B, M, 4)),
-                                g_dmin=np.empty(B), g_Q=None if xr is None else np.empty((B, 6, 6)),
-                                g_R=None if ur is None else np.empty((B, 2, 2)),
-                                g_geometry=np.empty((B, 5)) if geometry else None)
-        if geometry:
-            gout = TTObcaVjpGeometryOut(*[None if a is None else a.ctypes.data for a in
-                                          (r.g_x0, r.g_xref, r.g_uref, r.vjp_status, r.g_obstacles, r.g_dmin, r.g_Q,
-                                           r.g_R, r.g_geometry)])
-            rc = self._L.tt_obca_vjp_geometry(self._h, B, _ptr(I), st.ctypes.data_as(_ip), _ptr(xr), _ptr(ur), _ptr(gx),
-                                              _ptr(gu), C.byref(gout), C.byref(sc))
-            if rc != 0:
-                self._err(rc, "tt_obca_vjp_geometry")
-            return r
-        out = TTObcaVjpParamsOut(*[None if a is None else a.ctypes.data for a in
-                                   (r.g_x0, r.g_xref, r.g_uref, r.vjp_status, r.g_obstacles, r.g_dmin, r.g_Q, r.g_R)])
-        if obstacles is not None or d_min is not None:
-            rc = self._L.tt_obca_vjp_scenes(self._h, B, _ptr(I), st.ctypes.data_as(_ip), _ptr(xr), _ptr(ur), _ptr(gx),
-                                            _ptr(gu), C.byref(out), C.byref(sc))
-            if rc != 0:
-                self._err(rc, "tt_obca_vjp_scenes")
-            return r
-        rc = self._L.tt_obca_vjp_params(self._h, B, _ptr(I), st.ctypes.data_as(_ip), _ptr(xr), _ptr(ur), _ptr(gx),
-                                        _ptr(gu), C.byref(out))
-        if rc != 0:
-            self._err(rc, "tt_obca_vjp_params")
+        xr = None if xref is None or not params else _f64(xref, (B, N + 1, 6))
+        ur = None if uref is None or not params else _f64(uref, (B, N, 2))
+        r = (ObcaVjpParamsResult if params else TrackVjpResult)(
+            g_x0=np.empty((B, 6)), g_xref=np.empty((B, N + 1, 6)), g_uref=np.empty((B, N, 2)),
+            vjp_status=np.empty(B, dtype=np.int32))
+        if params:
+            r.g_obstacles, r.g_dmin = np.empty((B, M, 4)), np.empty(B)
+            r.g_Q = None if xr is None else np.empty((B, 6, 6))
+            r.g_R = None if ur is None else np.empty((B, 2, 2))
+            r.g_geometry = np.empty((B, 5)) if geometry else None
+        outs = [getattr(r, k, None) for k in ObcaVjpParamsResult.__slots__]
+        self._vjp_call(False, B, _ptr(I), st.ctypes.data_as(_ip), _ptr(xr), _ptr(ur), _ptr(gx), _ptr(gu),
+                       [None if a is None else a.ctypes.data for a in outs], sc)
         return r

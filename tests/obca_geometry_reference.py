@@ -153,100 +153,14 @@ def _with_geometry(out, P, it, lx, ly, vblk):
 
 
 # ---- routes -------------------------------------------------------------------------------------------------------
-def dense_lam(P, it, gX, gU, sparse=False, refined=False):
-    """The un-condensed solve of obca_scene_reference.dense_scene_vjp -> (ln, lam, n, maps)."""
-    ln, trip, rhs, nt, n, maps = osr._assemble(P, it, gX, gU)
-    if sparse:
-        import scipy.sparse as sp
-        import scipy.sparse.linalg as spl
-        lu_ = spl.splu(sp.coo_matrix((trip[2], (trip[0], trip[1])), shape=(nt, nt)).tocsc())
-        lam = lu_.solve(rhs)
-        for _ in range(2):
-            lam = lam + lu_.solve(osr._residual_ld(trip, rhs, lam))
-    else:
-        K = np.zeros((nt, nt))
-        np.add.at(K, (trip[0], trip[1]), trip[2])
-        lam = np.linalg.solve(K, rhs)
-        if refined:
-            for _ in range(3):
-                lam = lam + np.linalg.solve(K, osr._residual_ld(trip, rhs, lam))
-    return ln, lam, n, maps
-
-
-def split_lam(P, lam, n, maps):
-    """lam -> (lx (N+1,6), lu (N,2), ly (N+1,6), vblk (N+1,2M,16))."""
-    N, nb = P.N, 2 * P.M
-    ox, ou, ow, rd = maps
-    lx = np.array([lam[ox(k):ox(k) + 6] for k in range(N + 1)])
-    lu = np.array([lam[ou(k):ou(k) + 2] for k in range(N)])
-    ly = lam[n:n + 6 * (N + 1)].reshape(N + 1, 6).copy()
-    vblk = np.zeros((N + 1, nb, 16))
-    for k in range(N + 1):
-        for j in range(nb):
-            vblk[k, j, :12] = lam[ow(k, j):ow(k, j) + 12]
-            vblk[k, j, 12:] = lam[rd(k, j):rd(k, j) + 4]
-    return lx, lu, ly, vblk
-
-
 def dense_geometry_vjp(P, it, gX, gU, xref, uref, sparse=False, refined=False, parts=False):
-    ln, lam, n, maps = dense_lam(P, it, gX, gU, sparse, refined)
+    ln, lam, n, maps = osr.dense_lam(P, it, gX, gU, sparse, refined)
     out = osr._from_lam(P, it, ln, lam, n, maps, xref, uref)
-    lx, lu, ly, vblk = split_lam(P, lam, n, maps)
+    lx, lu, ly, vblk = osr.split_lam(P, lam, n, maps)
     _with_geometry(out, P, it, lx, ly, vblk)
     if parts:
         out["parts"] = (lx, lu, ly, vblk)
     return out
-
-
-def _carried(P, it, gX, gU, steps):
-    """obca_scene_reference.model_scene_vjp's passes -> (ln, lx, lu, x0, ly of the last step, closed v) or None."""
-    ln = orf.linearise(P, it)
-    N, nb, A, Bm = ln["N"], 2 * ln["M"], ln["A"], ln["B"]
-    H = osr._condensed(ln)
-    first = None if H is None else orf._sweeps(ln, H, gX, gU)
-    if first is None:
-        return None
-    lx, lu, x0 = first
-    facs = {}
-    for k in range(1, N + 1):
-        for j in range(nb):
-            Kb, C = orf.block_matrix(*ln["blocks"][k][j], ln["sw"][k, j], ln["ss"][k, j])
-            fac = orf.factor_block(Kb)
-            if fac is None:
-                return None
-            facs[k, j] = (Kb, C, fac)
-    ublk = np.zeros((N + 1, nb, 16))
-    dlx = lx
-
-    def close(ub, dlx_):
-        vb = ub.copy()
-        for (k, j), (Kb, C, fac) in facs.items():
-            vb[k, j] = ub[k, j] + orf.solve_block(fac, -(C @ dlx_[k, :4]))
-        return vb
-    ly = np.zeros((N + 2, 6))
-    for _ in range(steps):
-        vblk = close(ublk, dlx)
-        w = np.zeros((N + 1, 4))
-        fold = np.zeros((N + 1, 6))
-        for (k, j), (Kb, C, fac) in facs.items():
-            v = vblk[k, j]
-            t = orf.solve_block(fac, -(C @ lx[k, :4]) - Kb @ v)
-            w[k] += ln["blocks"][k][j][2] @ lx[k, :4] + C.T @ v
-            fold[k, :4] -= C.T @ t
-            ublk[k, j] = v + t
-        ly = np.zeros((N + 2, 6))
-        for k in range(N, -1, -1):
-            ly[k] = gX[k] - ln["H"][k] @ lx[k]
-            ly[k, :4] -= w[k]
-            if k < N:
-                ly[k] += A[k].T @ ly[k + 1]
-        ru = np.array([gU[k] - (2.0 * ln["R"] + np.diag(ln["su"][k])) @ lu[k] + Bm.T @ ly[k + 1] for k in range(N)])
-        second = orf._sweeps(ln, H, fold, ru)
-        if second is None:
-            return None
-        dlx = second[0]
-        lx, lu, x0 = lx + second[0], lu + second[1], ly[0] + second[2]
-    return ln, lx, lu, x0, ly[:N + 1], close(ublk, dlx), facs
 
 
 def _zeros(P):
@@ -258,7 +172,7 @@ def _zeros(P):
 def model_geometry_vjp(P, it, gX, gU, xref, uref, steps=STEPS):
     """The geometry kernel's route (module docstring)."""
     out = _zeros(P)
-    got = _carried(P, it, gX, gU, steps)
+    got = osr._carried(P, it, gX, gU, steps)
     if got is None:
         return out
     ln, lx, lu, x0, ly, vblk, _ = got
@@ -271,7 +185,7 @@ def model_geometry_vjp(P, it, gX, gU, xref, uref, steps=STEPS):
 def recomputed_geometry_vjp(P, it, gX, gU, xref, uref, steps=STEPS):
     """The carried route's lam_x and lam_y, but v = -K_b^-1 C lx_pose recomputed from the final pose adjoint."""
     out = _zeros(P)
-    got = _carried(P, it, gX, gU, steps)
+    got = osr._carried(P, it, gX, gU, steps)
     if got is None:
         return out
     ln, lx, lu, x0, ly, _, facs = got
@@ -291,7 +205,7 @@ def scales(ref):
 
 
 def group_err(a, b):
-    return {k: float(np.max(np.abs(np.asarray(a[k]) - np.asarray(b[k])))) for k in KEYS}
+    return orf.group_err(a, b, KEYS)
 
 
 # ---- differences --------------------------------------------------------------------------------------------------

@@ -118,23 +118,31 @@ def _residual_ld(trip, rhs, lam):
     return np.asarray(rhs.astype(np.longdouble) - prod, dtype=np.float64)
 
 
-def _from_lam(P, it, ln, lam, n, maps, xref, uref):
+def split_lam(P, lam, n, maps):
+    """lam -> (lx (N+1,6), lu (N,2), ly (N+1,6), vblk (N+1,2M,16))."""
     N, nb = P.N, 2 * P.M
     ox, ou, ow, rd = maps
     lx = np.array([lam[ox(k):ox(k) + 6] for k in range(N + 1)])
     lu = np.array([lam[ou(k):ou(k) + 2] for k in range(N)])
+    ly = lam[n:n + 6 * (N + 1)].reshape(N + 1, 6).copy()
     vblk = np.zeros((N + 1, nb, 16))
     for k in range(N + 1):
         for j in range(nb):
             vblk[k, j, :12] = lam[ow(k, j):ow(k, j) + 12]
             vblk[k, j, 12:] = lam[rd(k, j):rd(k, j) + 4]
+    return lx, lu, ly, vblk
+
+
+def _from_lam(P, it, ln, lam, n, maps, xref, uref):
+    lx, lu, _, vblk = split_lam(P, lam, n, maps)
     out = {"x0": lam[n:n + 6].copy(), "xref": 2.0 * lx @ ln["Q"], "uref": 2.0 * lu @ ln["R"]}
     out["obs"], out["dmin"] = _scene_terms(P, it, vblk)
     out["Q"], out["R"] = _weight_terms(P, it, lx, lu, xref, uref)
     return out
 
 
-def dense_scene_vjp(P, it, gX, gU, xref, uref, sparse=False, refined=False):
+def dense_lam(P, it, gX, gU, sparse=False, refined=False):
+    """The un-condensed solve -> (ln, lam, n, maps)."""
     ln, trip, rhs, nt, n, maps = _assemble(P, it, gX, gU)
     if sparse:
         import scipy.sparse as sp
@@ -150,6 +158,11 @@ def dense_scene_vjp(P, it, gX, gU, xref, uref, sparse=False, refined=False):
         if refined:
             for _ in range(3):
                 lam = lam + np.linalg.solve(K, _residual_ld(trip, rhs, lam))
+    return ln, lam, n, maps
+
+
+def dense_scene_vjp(P, it, gX, gU, xref, uref, sparse=False, refined=False):
+    ln, lam, n, maps = dense_lam(P, it, gX, gU, sparse, refined)
     return _from_lam(P, it, ln, lam, n, maps, xref, uref)
 
 
@@ -183,18 +196,31 @@ def _finish(P, it, ln, out, lx, lu, x0, vblk, xref, uref):
     return out
 
 
-def model_scene_vjp(P, it, gX, gU, xref, uref, steps=STEPS, trace=None):
-    """The params kernel's route (module docstring).  trace: a list that receives the result after every step's
-    closing pass (the step-by-step record of DESIGN.md), at the cost of one extra pass per step."""
+def _stage_step(ln, H, gX, gU, lx, lu, w, fold):
+    """The stage part of a refinement step: lam_y from the x-rows with the blocks' w, the input rows' residual ru and
+    the sweeps on (fold, ru) -> (ly (N+2,6), the correction (dlx, dlu, p_0) or None)."""
+    N, A, Bm = ln["N"], ln["A"], ln["B"]
+    ly = np.zeros((N + 2, 6))
+    for k in range(N, -1, -1):
+        ly[k] = gX[k] - ln["H"][k] @ lx[k]
+        ly[k, :4] -= w[k]
+        if k < N:
+            ly[k] += A[k].T @ ly[k + 1]
+    ru = np.array([gU[k] - (2.0 * ln["R"] + np.diag(ln["su"][k])) @ lu[k] + Bm.T @ ly[k + 1] for k in range(N)])
+    return ly, orf._sweeps(ln, H, fold, ru)
+
+
+def _carried(P, it, gX, gU, steps, each=None):
+    """The params kernel's passes (module docstring): the first solve, `steps` refinement steps on the carried block
+    unknowns and the closing block pass -> (ln, lx, lu, x0, ly of the last step (N+1,6), closed v, the blocks'
+    (K_b, C, factors)) or None.  each(ln, lx, lu, x0, closed v) is called after every step, at the cost of one extra
+    pass per step."""
     ln = orf.linearise(P, it)
-    N, nb, A, Bm = ln["N"], 2 * ln["M"], ln["A"], ln["B"]
-    out = _zeros(P)
+    N, nb = ln["N"], 2 * ln["M"]
     H = _condensed(ln)
-    if H is None:
-        return out
-    first = orf._sweeps(ln, H, gX, gU)
+    first = None if H is None else orf._sweeps(ln, H, gX, gU)
     if first is None:
-        return out
+        return None
     lx, lu, x0 = first
     facs = {}
     for k in range(1, N + 1):
@@ -202,7 +228,7 @@ def model_scene_vjp(P, it, gX, gU, xref, uref, steps=STEPS, trace=None):
             Kb, C = orf.block_matrix(*ln["blocks"][k][j], ln["sw"][k, j], ln["ss"][k, j])
             fac = orf.factor_block(Kb)
             if fac is None:
-                return out
+                return None
             facs[k, j] = (Kb, C, fac)
     ublk = np.zeros((N + 1, nb, 16))  # the carried record u = v + t (zero before the first pass)
     dlx = lx                          # the last correction (the first solve itself before the first pass)
@@ -213,7 +239,8 @@ def model_scene_vjp(P, it, gX, gU, xref, uref, steps=STEPS, trace=None):
         for (k, j), (Kb, C, fac) in facs.items():
             vb[k, j] = ub[k, j] + orf.solve_block(fac, -(C @ dlx_[k, :4]))
         return vb
-    for step in range(steps):
+    ly = np.zeros((N + 2, 6))
+    for _ in range(steps):
         vblk = close(ublk, dlx)
         w = np.zeros((N + 1, 4))
         fold = np.zeros((N + 1, 6))
@@ -223,27 +250,33 @@ def model_scene_vjp(P, it, gX, gU, xref, uref, steps=STEPS, trace=None):
             w[k] += ln["blocks"][k][j][2] @ lx[k, :4] + C.T @ v
             fold[k, :4] -= C.T @ t
             ublk[k, j] = v + t
-        ly = np.zeros((N + 2, 6))
-        for k in range(N, -1, -1):
-            ly[k] = gX[k] - ln["H"][k] @ lx[k]
-            ly[k, :4] -= w[k]
-            if k < N:
-                ly[k] += A[k].T @ ly[k + 1]
-        ru = np.array([gU[k] - (2.0 * ln["R"] + np.diag(ln["su"][k])) @ lu[k] + Bm.T @ ly[k + 1] for k in range(N)])
-        second = orf._sweeps(ln, H, fold, ru)
+        ly, second = _stage_step(ln, H, gX, gU, lx, lu, w, fold)
         if second is None:
-            return out
+            return None
         dlx = second[0]
         lx, lu, x0 = lx + second[0], lu + second[1], ly[0] + second[2]
-        if trace is not None:
-            trace.append(_finish(P, it, ln, _zeros(P), lx, lu, x0, close(ublk, dlx), xref, uref))
-    return _finish(P, it, ln, out, lx, lu, x0, close(ublk, dlx), xref, uref)  # the closing pass
+        if each is not None:
+            each(ln, lx, lu, x0, close(ublk, dlx))
+    return ln, lx, lu, x0, ly[:N + 1], close(ublk, dlx), facs
+
+
+def model_scene_vjp(P, it, gX, gU, xref, uref, steps=STEPS, trace=None):
+    """The params kernel's route (module docstring).  trace: a list that receives the result after every step's
+    closing pass (the step-by-step record of DESIGN.md), at the cost of one extra pass per step."""
+    each = None
+    if trace is not None:
+        each = lambda ln, lx, lu, x0, v: trace.append(_finish(P, it, ln, _zeros(P), lx, lu, x0, v, xref, uref))  # noqa: E731
+    got = _carried(P, it, gX, gU, steps, each)
+    if got is None:
+        return _zeros(P)
+    ln, lx, lu, x0, _, vblk, _ = got
+    return _finish(P, it, ln, _zeros(P), lx, lu, x0, vblk, xref, uref)
 
 
 def recomputed_scene_vjp(P, it, gX, gU, xref, uref, with_t=False, steps=orf.REFINE_STEPS):
     """obca_vjp_kernel's own route to the pose adjoint, then v = -K_b^-1 C lx_pose (+ t = K_b^-1 (b0 - K_b v))."""
     ln = orf.linearise(P, it)
-    N, nb, A, Bm = ln["N"], 2 * ln["M"], ln["A"], ln["B"]
+    N, nb = ln["N"], 2 * ln["M"]
     out = _zeros(P)
     H = _condensed(ln)
     first = None if H is None else orf._sweeps(ln, H, gX, gU)
@@ -270,14 +303,7 @@ def recomputed_scene_vjp(P, it, gX, gU, xref, uref, with_t=False, steps=orf.REFI
         for (k, j), (Kb, C, fac) in facs.items():
             w[k] += ln["blocks"][k][j][2] @ lx[k, :4] + C.T @ vb[k, j]
             fold[k, :4] -= C.T @ tb[k, j]
-        ly = np.zeros((N + 2, 6))
-        for k in range(N, -1, -1):
-            ly[k] = gX[k] - ln["H"][k] @ lx[k]
-            ly[k, :4] -= w[k]
-            if k < N:
-                ly[k] += A[k].T @ ly[k + 1]
-        ru = np.array([gU[k] - (2.0 * ln["R"] + np.diag(ln["su"][k])) @ lu[k] + Bm.T @ ly[k + 1] for k in range(N)])
-        second = orf._sweeps(ln, H, fold, ru)
+        ly, second = _stage_step(ln, H, gX, gU, lx, lu, w, fold)
         if second is None:
             return out
         lx, lu, x0 = lx + second[0], lu + second[1], ly[0] + second[2]
@@ -295,7 +321,7 @@ def scales(ref):
 
 
 def group_err(a, b):
-    return {k: float(np.max(np.abs(np.asarray(a[k]) - np.asarray(b[k])))) for k in KEYS}
+    return orf.group_err(a, b, KEYS)
 
 
 def oracle_fd_scene(P, x0, xr, ur, gX, gU, h=1e-4, hw=1e-3):

@@ -412,9 +412,9 @@ def model_obca_vjp(P, it, gX, gU, steps=REFINE_STEPS):
     return out
 
 
-def group_err(a, b):
+def group_err(a, b, keys=KEYS):
     """Largest absolute difference per group."""
-    return {k: float(np.max(np.abs(np.asarray(a[k]) - np.asarray(b[k])))) for k in KEYS}
+    return {k: float(np.max(np.abs(np.asarray(a[k]) - np.asarray(b[k])))) for k in keys}
 
 
 def group_max(a):

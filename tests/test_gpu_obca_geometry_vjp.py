@@ -21,21 +21,17 @@ import numpy as np
 import pytest
 
 import obca_geometry_reference as ogr
+import obca_vjp_harness as hx
 import obca_vjp_reference as orf
 
 pytestmark = pytest.mark.gpu
 
-MODEL_CAP = 1e-9
-GOT = {"x0": "g_x0", "xref": "g_xref", "uref": "g_uref", "obs": "g_obstacles", "dmin": "g_dmin", "Q": "g_Q", "R": "g_R",
-       "geom": "g_geometry"}
+GOT = hx.GOT
 SHARED = ("g_x0", "g_xref", "g_uref", "vjp_status", "g_obstacles", "g_dmin", "g_Q", "g_R")
 NEW = dict(L1=7.3, L2=12.0, M=0.3, W1=2.9, W2=3.1)
 
 
-def _solver(case, **kw):
-    import ttmpc
-    N, p, Q, R, bnd, obs = case[:6]
-    return ttmpc.ObcaSolver(N, p, Q, R, *bnd, obs, variant=ttmpc.TT_VARIANT_TRACK_OBCA, **kw)
+_solver = hx.solver
 
 
 @functools.lru_cache(maxsize=None)
@@ -60,24 +56,9 @@ def batch_f():
     return f, s, (x0b, xrb, urb, obb), (X, U, st, I), (gXb, gUb), res
 
 
-def _row(r, b):
-    """Instance b of a result under the reference's keys."""
-    return {k: (float(getattr(r, a)[b]) if k == "dmin" else getattr(r, a)[b]) for k, a in GOT.items()}
-
-
 def _check_against_dense(P, I, gX, gU, xr, ur, r, b, label, sparse=False):
-    dense = ogr.dense_geometry_vjp(P, I, gX, gU, xr, ur, sparse=sparse)
-    model = ogr.model_geometry_vjp(P, I, gX, gU, xr, ur)
-    got = _row(r, b)
-    sc, em, eg = ogr.scales(dense), ogr.group_err(model, dense), ogr.group_err(got, dense)
-    print(f"{label}: scales {sc}\n   model vs dense {em}\n   gpu   vs dense {eg}\n   geometry dense {dense['geom']}\n"
-          f"   geometry gpu   {got['geom']}")
-    assert model["ok"] and r.vjp_status[b] == 0
-    for k in ogr.KEYS:
-        assert eg[k] <= 10.0 * em[k] + 1e-12 * sc[k], (label, k, eg[k], em[k])
-    for k in ogr.KEYS:
-        assert em[k] <= MODEL_CAP * sc[k], (label, k, em[k], MODEL_CAP * sc[k])
-    return dense
+    return hx.check_against_dense(ogr, ogr.dense_geometry_vjp, ogr.model_geometry_vjp, ogr.scales, ogr.KEYS,
+                                  (P, I, gX, gU, xr, ur), hx.row(r, b, GOT), r.vjp_status[b], label, sparse)
 
 
 @pytest.mark.parametrize("b,label", [(0, "F"), (1, "R"), (2, "F, obstacle 3 m away")])
@@ -105,12 +86,9 @@ def test_unsolved_instance_is_skipped():
 
 
 def test_kernel_matches_dense_with_several_blocks():
-    case = orf.case_b()
-    N, p, Q, R, bnd, obs, x0, xr, ur = case
-    s = _solver(case)
-    X, U, Z, st, it, kk, I = s.solve(x0[None], xref=xr[None], uref=ur[None], iterate=True)
+    case, s, (X, U, st, I), (gX, gU) = hx.solved_b()
+    xr, ur = case[7], case[8]
     assert st[0] <= 1
-    gX, gU = orf.upstream(N)
     r = s.vjp(I, st, gX[None], gU[None], xref=xr[None], uref=ur[None], geometry=True)
     dense = _check_against_dense(orf.problem(*case[:6]), I[0], gX, gU, xr, ur, r, 0, "N = 8, M = 2")
     assert abs(dense["geom"][0]) > 1.0  # the truck's front face is in contact
@@ -119,23 +97,10 @@ def test_kernel_matches_dense_with_several_blocks():
 def test_full_size_window():
     """One instance at the drivers' shape N = 50, M = 11 (1122 blocks: 70 full rounds and a tail of 2): window 10
     (obstacle rows active) of the golden MPC+OBCA windows against the sparse un-condensed solve."""
-    import ttmpc
-    from conftest import GOLDEN
-    from ttmpc import scenarios as sc
-    g = np.load(GOLDEN / "reference_numpy.npz")
-    obs = g["obstacles"]
-    x0, xr, ur = sc.mpc_obs_batch(g["state_traj"], g["input_traj"], 16, 50, seed=0)
-    pick = [10]
-    p = dict(sc.OBCA_PARAMS, dt=0.05)
-    bnd = (sc.XLB, sc.XUB, sc.ULB, sc.UUB)
-    s = ttmpc.ObcaSolver(50, p, sc.OBCA_Q, sc.OBCA_R, *bnd, obs, variant=ttmpc.TT_VARIANT_TRACK_OBCA)
-    X, U, Z, st, it, kk, I = s.solve(x0[pick], xref=xr[pick], uref=ur[pick], iterate=True)
-    assert np.all(st <= 1), st
-    gX, gU = orf.upstream(50)
-    r = s.vjp(I, st, gX[None], gU[None], xref=xr[pick], uref=ur[pick], geometry=True)
+    s, P, st, I, (gX, gU), xr, ur = hx.golden_windows([10])
+    r = s.vjp(I, st, gX[None], gU[None], xref=xr, uref=ur, geometry=True)
     assert np.all(r.vjp_status == 0), r.vjp_status
-    P = orf.problem(50, p, sc.OBCA_Q, sc.OBCA_R, bnd, obs)
-    dense = _check_against_dense(P, I[0], gX, gU, xr[10], ur[10], r, 0, "window 10", sparse=True)
+    dense = _check_against_dense(P, I[0], gX, gU, xr[0], ur[0], r, 0, "window 10", sparse=True)
     assert np.abs(dense["geom_block"]).max() > 1.0
 
 
@@ -204,22 +169,7 @@ def test_shared_outputs_are_the_params_call_bitwise():
 
 
 def _device_call(s, B, I, st, gX, gU, xr, ur, ob, work=True):
-    import torch
-    N, M = s.N, s.M
-    dev = torch.device("cuda", s.device)
-    t = lambda a: None if a is None else torch.as_tensor(a, device=dev).contiguous()  # noqa: E731
-    dI, dgx, dgu, dxr, dur, dob = t(I), t(gX), t(gU), t(xr), t(ur), t(ob)
-    dst = torch.as_tensor(st.astype(np.int32), device=dev)
-    shapes = {"g_x0": (B, 6), "g_xref": (B, N + 1, 6), "g_uref": (B, N, 2), "g_obstacles": (B, M, 4), "g_dmin": (B,),
-              "g_Q": (B, 6, 6), "g_R": (B, 2, 2), "g_geometry": (B, 5)}
-    out = {k: torch.full(v, 7.0, dtype=torch.float64, device=dev) for k, v in shapes.items()}
-    out["vjp_status"] = torch.full((B,), 7, dtype=torch.int32, device=dev)
-    wk = torch.empty((B * s.vjp_params_work_bytes() // 8,), dtype=torch.float64, device=dev)
-    s.vjp_device(B, dI.data_ptr(), dst.data_ptr(), grad_x=dgx.data_ptr(), grad_u=dgu.data_ptr(), xref=dxr.data_ptr(),
-                 uref=dur.data_ptr(), work=wk.data_ptr() if work else 0, obstacles=dob.data_ptr(),
-                 **{k: v.data_ptr() for k, v in out.items()}, stream=torch.cuda.current_stream(dev).cuda_stream)
-    torch.cuda.synchronize(dev)
-    return {k: v.cpu().numpy() for k, v in out.items()}
+    return hx.device_call(s, B, I, st, gX, gU, xr, ur, ob, keys=hx.OUT9, work=work)
 
 
 def test_determinism_tiling_and_host_entry():
@@ -231,12 +181,7 @@ def test_determinism_tiling_and_host_entry():
     for k in d4:
         assert np.array_equal(d4[k], getattr(r, k)), k
     T = 75
-    tile = lambda a: np.tile(a, (T,) + (1,) * (a.ndim - 1))  # noqa: E731
-    args = (s, 4 * T, tile(I), tile(st), tile(gXb), tile(gUb), tile(xrb), tile(urb), tile(obb))
-    big, again = _device_call(*args), _device_call(*args)
-    for k in d4:
-        assert np.array_equal(big[k], again[k]), k
-        assert np.array_equal(big[k].reshape((T,) + d4[k].shape), np.broadcast_to(d4[k], (T,) + d4[k].shape)), k
+    hx.check_tiling(lambda *a: _device_call(s, 4 * T, *a), d4, T, I, st, gXb, gUb, xrb, urb, obb)
     with pytest.raises(ttmpc.TTError, match="-22"):
         _device_call(s, 4, I, st, gXb, gUb, xrb, urb, obb, work=False)
 

@@ -20,76 +20,33 @@ import numpy as np
 import pytest
 
 import obca_scene_reference as osr
+import obca_vjp_harness as hx
 import obca_vjp_reference as orf
 
 pytestmark = pytest.mark.gpu
 
-MODEL_CAP = 1e-9
-GOT = {"x0": "g_x0", "xref": "g_xref", "uref": "g_uref", "obs": "g_obstacles", "dmin": "g_dmin", "Q": "g_Q", "R": "g_R"}
-
-
-def _solver(case, **kw):
-    import ttmpc
-    N, p, Q, R, bnd, obs = case[:6]
-    return ttmpc.ObcaSolver(N, p, Q, R, *bnd, obs, variant=ttmpc.TT_VARIANT_TRACK_OBCA, **kw)
+GOT = hx.got_map(7)
+_solver = hx.solver
 
 
 @functools.lru_cache(maxsize=None)
 def batch_a():
-    """B = 4 on case A's handle: case A; the inactive variant (the whole scene moved 2.5 m back, which is the obstacle
-    at cx = 13); x_init[1] = -0.1; x_init outside the box (v above its bound), which cannot be solved."""
-    case = orf.case_a()
-    N, p, Q, R, bnd, obs, x0, xr, ur = case
-    xs, rs = [x0], [xr]
-    a, b = x0.copy(), xr.copy()
-    a[0] -= 2.5
-    b[:, 0] -= 2.5
-    xs.append(a)
-    rs.append(b)
-    c = x0.copy()
-    c[1] = -0.1
-    xs.append(c)
-    rs.append(xr)
-    d = x0.copy()
-    d[5] = 11.0
-    xs.append(d)
-    rs.append(xr)
-    x0b, xrb, urb = np.array(xs), np.array(rs), np.tile(ur, (4, 1, 1))
-    s = _solver(case)
-    X, U, Z, st, it, kk, I = s.solve(x0b, xref=xrb, uref=urb, iterate=True)
-    gX, gU = orf.upstream(N)
-    gXb, gUb = np.tile(gX, (4, 1, 1)), np.tile(gU, (4, 1, 1))
+    """obca_vjp_harness.solved_a and its params adjoint."""
+    case, s, (x0b, xrb, urb), (X, U, st, I), (gXb, gUb) = hx.solved_a()
     r = s.vjp(I, st, gXb, gUb, xref=xrb, uref=urb, params=True)
     return case, s, (x0b, xrb, urb), (X, U, st, I), (gXb, gUb), r
 
 
 @functools.lru_cache(maxsize=None)
 def batch_b():
-    case = orf.case_b()
-    N, p, Q, R, bnd, obs, x0, xr, ur = case
-    s = _solver(case)
-    X, U, Z, st, it, kk, I = s.solve(x0[None], xref=xr[None], uref=ur[None], iterate=True)
-    gX, gU = orf.upstream(N)
+    case, s, (X, U, st, I), (gX, gU) = hx.solved_b()
+    xr, ur = case[7], case[8]
     return case, s, (X, U, st, I), (gX, gU), s.vjp(I, st, gX[None], gU[None], xref=xr[None], uref=ur[None], params=True)
 
 
-def _row(r, b):
-    """Instance b of a result under the reference's keys."""
-    return {k: (float(getattr(r, a)[b]) if k == "dmin" else getattr(r, a)[b]) for k, a in GOT.items()}
-
-
 def _check_against_dense(P, I, gX, gU, xr, ur, r, b, label, sparse=False):
-    dense = osr.dense_scene_vjp(P, I, gX, gU, xr, ur, sparse=sparse)
-    model = osr.model_scene_vjp(P, I, gX, gU, xr, ur)
-    got = _row(r, b)
-    sc, em, eg = osr.scales(dense), osr.group_err(model, dense), osr.group_err(got, dense)
-    print(f"{label}: scales {sc}\n   model vs dense {em}\n   gpu   vs dense {eg}")
-    assert model["ok"] and r.vjp_status[b] == 0
-    for k in osr.KEYS:
-        assert eg[k] <= 10.0 * em[k] + 1e-12 * sc[k], (label, k, eg[k], em[k])
-    for k in osr.KEYS:
-        assert em[k] <= MODEL_CAP * sc[k], (label, k, em[k], MODEL_CAP * sc[k])
-    return dense
+    return hx.check_against_dense(osr, osr.dense_scene_vjp, osr.model_scene_vjp, osr.scales, osr.KEYS,
+                                  (P, I, gX, gU, xr, ur), hx.row(r, b, GOT), r.vjp_status[b], label, sparse)
 
 
 @pytest.mark.parametrize("b,label", [(0, "case A"), (1, "inactive"), (2, "x_init[1] = -0.1")])
@@ -127,24 +84,11 @@ def test_kernel_matches_dense_with_several_blocks():
 def test_full_size_window():
     """One instance at the drivers' shape N = 50, M = 11 (1122 blocks: 70 full rounds and a tail of 2): window 10
     (obstacle rows active) of the golden MPC+OBCA windows against the sparse un-condensed solve."""
-    import ttmpc
-    from conftest import GOLDEN
-    from ttmpc import scenarios as sc
-    g = np.load(GOLDEN / "reference_numpy.npz")
-    obs = g["obstacles"]
-    x0, xr, ur = sc.mpc_obs_batch(g["state_traj"], g["input_traj"], 16, 50, seed=0)
-    pick = [10]
-    p = dict(sc.OBCA_PARAMS, dt=0.05)
-    bnd = (sc.XLB, sc.XUB, sc.ULB, sc.UUB)
-    s = ttmpc.ObcaSolver(50, p, sc.OBCA_Q, sc.OBCA_R, *bnd, obs, variant=ttmpc.TT_VARIANT_TRACK_OBCA)
-    X, U, Z, st, it, kk, I = s.solve(x0[pick], xref=xr[pick], uref=ur[pick], iterate=True)
-    assert np.all(st <= 1), st
-    gX, gU = orf.upstream(50)
-    r = s.vjp(I, st, gX[None], gU[None], xref=xr[pick], uref=ur[pick], params=True)
+    s, P, st, I, (gX, gU), xr, ur = hx.golden_windows([10])
+    r = s.vjp(I, st, gX[None], gU[None], xref=xr, uref=ur, params=True)
     assert np.all(r.vjp_status == 0), r.vjp_status
-    P = orf.problem(50, p, sc.OBCA_Q, sc.OBCA_R, bnd, obs)
     assert np.abs(orf.unpack(I[0], 50, 11)["yd"][..., 0]).max() > 1.0
-    dense = _check_against_dense(P, I[0], gX, gU, xr[10], ur[10], r, 0, "window 10", sparse=True)
+    dense = _check_against_dense(P, I[0], gX, gU, xr[0], ur[0], r, 0, "window 10", sparse=True)
     assert abs(dense["dmin"]) > 1.0
 
 
@@ -186,24 +130,8 @@ def test_end_to_end_through_set_scene():
     assert np.array_equal(Xa, Xb) and np.array_equal(Ua, Ub)
 
 
-def _device_call(s, B, I, st, gX, gU, xr, ur, want=tuple(GOT.values()) + ("vjp_status",), work=True):
-    import torch
-    N, M = s.N, s.M
-    dev = torch.device("cuda", s.device)
-    t = lambda a: None if a is None else torch.as_tensor(a, device=dev).contiguous()  # noqa: E731
-    dI, dgx, dgu, dxr, dur = t(I), t(gX), t(gU), t(xr), t(ur)
-    dst = torch.as_tensor(st.astype(np.int32), device=dev)
-    shapes = {"g_x0": (B, 6), "g_xref": (B, N + 1, 6), "g_uref": (B, N, 2), "g_obstacles": (B, M, 4), "g_dmin": (B,),
-              "g_Q": (B, 6, 6), "g_R": (B, 2, 2)}
-    out = {k: torch.full(v, 7.0, dtype=torch.float64, device=dev) for k, v in shapes.items()}
-    out["vjp_status"] = torch.full((B,), 7, dtype=torch.int32, device=dev)
-    wk = torch.empty((B * s.vjp_params_work_bytes() // 8,), dtype=torch.float64, device=dev)
-    p = lambda a: 0 if a is None else a.data_ptr()  # noqa: E731
-    s.vjp_device(B, dI.data_ptr(), dst.data_ptr(), grad_x=p(dgx), grad_u=p(dgu), xref=p(dxr), uref=p(dur),
-                 work=wk.data_ptr() if work else 0, **{k: (v.data_ptr() if k in want else 0) for k, v in out.items()},
-                 stream=torch.cuda.current_stream(dev).cuda_stream)
-    torch.cuda.synchronize(dev)
-    return {k: v.cpu().numpy() for k, v in out.items()}
+def _device_call(s, B, I, st, gX, gU, xr, ur, want=None, work=True):
+    return hx.device_call(s, B, I, st, gX, gU, xr, ur, keys=hx.OUT8, want=want, work=work)
 
 
 def test_determinism_tiling_and_host_entry():
@@ -214,12 +142,7 @@ def test_determinism_tiling_and_host_entry():
     for k in d4:
         assert np.array_equal(d4[k], getattr(r, k)), k
     T = 300
-    tile = lambda a: np.tile(a, (T,) + (1,) * (a.ndim - 1))  # noqa: E731
-    args = (s, 4 * T, tile(I), tile(st), tile(gXb), tile(gUb), tile(xrb), tile(urb))
-    big, again = _device_call(*args), _device_call(*args)
-    for k in d4:
-        assert np.array_equal(big[k], again[k]), k
-        assert np.array_equal(big[k].reshape((T,) + d4[k].shape), np.broadcast_to(d4[k], (T,) + d4[k].shape)), k
+    hx.check_tiling(lambda *a: _device_call(s, 4 * T, *a), d4, T, I, st, gXb, gUb, xrb, urb)
 
 
 def test_null_members_stay_untouched():

@@ -23,14 +23,14 @@ import numpy as np
 import pytest
 
 import obca_scene_reference as osr
+import obca_vjp_harness as hx
 import obca_vjp_reference as orf
 from conftest import GOLDEN
 from test_obca_oracle import P6, toy_plan
 
 pytestmark = pytest.mark.gpu
 
-OUT8 = ("g_x0", "g_xref", "g_uref", "g_obstacles", "g_dmin", "g_Q", "g_R", "vjp_status")
-OUT4 = ("g_x0", "g_xref", "g_uref", "vjp_status")
+OUT8, OUT4 = hx.OUT8, hx.OUT4
 
 
 def family(obs, widen=0, big=0.35):
@@ -49,10 +49,7 @@ def _case(name):
     return case, family(case[5], widen=1, big=0.22)
 
 
-def _solver(case, **kw):
-    import ttmpc
-    N, p, Q, R, bnd, obs = case[:6]
-    return ttmpc.ObcaSolver(N, p, Q, R, *bnd, obs, variant=ttmpc.TT_VARIANT_TRACK_OBCA, **kw)
+_solver = hx.solver
 
 
 @functools.lru_cache(maxsize=None)
@@ -287,18 +284,9 @@ def test_adjoint_matches_dense_in_the_rows_scene(b, label):
     I = out[6]
     P = orf.problem(N, p, Q, R, bnd, S[b])
     P.dmin = D[b]
-    dense = osr.dense_scene_vjp(P, I[b], gXb[b], gUb[b], xrb[b], urb[b])
-    model = osr.model_scene_vjp(P, I[b], gXb[b], gUb[b], xrb[b], urb[b])
-    names = {"x0": "g_x0", "xref": "g_xref", "uref": "g_uref", "obs": "g_obstacles", "dmin": "g_dmin", "Q": "g_Q",
-             "R": "g_R"}
-    got = {k: (float(getattr(rp, a)[b]) if k == "dmin" else getattr(rp, a)[b]) for k, a in names.items()}
-    sc, em, eg = osr.scales(dense), osr.group_err(model, dense), osr.group_err(got, dense)
-    print(f"{label}: scales {sc}\n   model vs dense {em}\n   gpu   vs dense {eg}")
-    assert model["ok"] and rp.vjp_status[b] == 0
-    for k in osr.KEYS:
-        assert eg[k] <= 10.0 * em[k] + 1e-12 * sc[k], (label, k, eg[k], em[k])
-    for k in osr.KEYS:
-        assert em[k] <= 1e-9 * sc[k], (label, k, em[k])
+    dense = hx.check_against_dense(osr, osr.dense_scene_vjp, osr.model_scene_vjp, osr.scales, osr.KEYS,
+                                   (P, I[b], gXb[b], gUb[b], xrb[b], urb[b]), hx.row(rp, b, hx.got_map(7)),
+                                   rp.vjp_status[b], label)
     assert abs(dense["dmin"]) > 1.0  # the row's d_min constraint is active
 
 

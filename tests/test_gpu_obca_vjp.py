@@ -13,74 +13,30 @@ import functools
 import numpy as np
 import pytest
 
+import obca_vjp_harness as hx
 import obca_vjp_reference as orf
 
 pytestmark = pytest.mark.gpu
 
-MODEL_CAP = 1e-9
-
-
-def _solver(case, **kw):
-    import ttmpc
-    N, p, Q, R, bnd, obs = case[:6]
-    return ttmpc.ObcaSolver(N, p, Q, R, *bnd, obs, variant=ttmpc.TT_VARIANT_TRACK_OBCA, **kw)
-
-
-def _shift(x0, xr, dx):
-    x0, xr = x0.copy(), xr.copy()
-    x0[0] += dx
-    xr[:, 0] += dx
-    return x0, xr
+GOT = hx.got_map(3)
 
 
 @functools.lru_cache(maxsize=None)
 def batch_a():
-    """B = 4 on case A's handle: case A; the inactive variant (the whole scene moved 2.5 m back, which is the obstacle
-    at cx = 13); x_init[1] = -0.1; x_init outside the box (v above its bound), which cannot be solved."""
-    case = orf.case_a()
-    N, p, Q, R, bnd, obs, x0, xr, ur = case
-    xs, rs = [x0], [xr]
-    a, b = _shift(x0, xr, -2.5)
-    xs.append(a)
-    rs.append(b)
-    c = x0.copy()
-    c[1] = -0.1
-    xs.append(c)
-    rs.append(xr)
-    d = x0.copy()
-    d[5] = 11.0
-    xs.append(d)
-    rs.append(xr)
-    x0b, xrb, urb = np.array(xs), np.array(rs), np.tile(ur, (4, 1, 1))
-    s = _solver(case)
-    X, U, Z, st, it, kk, I = s.solve(x0b, xref=xrb, uref=urb, iterate=True)
-    gX, gU = orf.upstream(N)
-    gXb, gUb = np.tile(gX, (4, 1, 1)), np.tile(gU, (4, 1, 1))
-    r = s.vjp(I, st, gXb, gUb)
-    return case, s, (x0b, xrb, urb), (X, U, st, I), (gXb, gUb), r
+    """obca_vjp_harness.solved_a and its plain adjoint."""
+    case, s, inputs, (X, U, st, I), (gXb, gUb) = hx.solved_a()
+    return case, s, inputs, (X, U, st, I), (gXb, gUb), s.vjp(I, st, gXb, gUb)
 
 
 @functools.lru_cache(maxsize=None)
 def batch_b():
-    case = orf.case_b()
-    N, p, Q, R, bnd, obs, x0, xr, ur = case
-    s = _solver(case)
-    X, U, Z, st, it, kk, I = s.solve(x0[None], xref=xr[None], uref=ur[None], iterate=True)
-    gX, gU = orf.upstream(N)
+    case, s, (X, U, st, I), (gX, gU) = hx.solved_b()
     return case, s, (X, U, st, I), (gX, gU), s.vjp(I, st, gX[None], gU[None])
 
 
 def _check_against_dense(P, I, gX, gU, r, b, label, sparse=False):
-    dense = orf.dense_obca_vjp(P, I, gX, gU, sparse=sparse)
-    model = orf.model_obca_vjp(P, I, gX, gU)
-    got = {"x0": r.g_x0[b], "xref": r.g_xref[b], "uref": r.g_uref[b]}
-    mx, em, eg = orf.group_max(dense), orf.group_err(model, dense), orf.group_err(got, dense)
-    print(f"{label}: largest {mx}\n   model vs dense {em}\n   gpu   vs dense {eg}")
-    assert model["ok"] and r.vjp_status[b] == 0
-    for k in orf.KEYS:
-        assert eg[k] <= 10.0 * em[k] + 1e-12 * mx[k], (label, k, eg[k], em[k])
-    for k in orf.KEYS:
-        assert em[k] <= MODEL_CAP * mx[k], (label, k, em[k], MODEL_CAP * mx[k])
+    hx.check_against_dense(orf, orf.dense_obca_vjp, orf.model_obca_vjp, orf.group_max, orf.KEYS, (P, I, gX, gU),
+                           hx.row(r, b, GOT), r.vjp_status[b], label, sparse, word="largest")
 
 
 @pytest.mark.parametrize("b,label", [(0, "case A"), (1, "inactive"), (2, "x_init[1] = -0.1")])
@@ -112,8 +68,7 @@ def test_kernel_matches_central_differences_of_the_oracle():
     case, s, _, (X, U, st, I), (gXb, gUb), r = batch_a()
     N, p, Q, R, bnd, obs, x0, xr, ur = case
     _, sto, fd = orf.oracle_fd_vjp(orf.problem(*case[:6]), x0, xr, ur, gXb[0], gUb[0])
-    got = {"x0": r.g_x0[0], "xref": r.g_xref[0], "uref": r.g_uref[0]}
-    err = orf.group_err(got, fd)
+    err = orf.group_err(hx.row(r, 0, GOT), fd)
     print("gpu vs central differences of the oracle", err)
     for k in orf.KEYS:
         assert err[k] <= 1e-5, (k, err[k])
@@ -123,45 +78,15 @@ def test_full_size_windows():
     """B = 2 at the drivers' shape N = 50, M = 11 (1122 blocks: 70 full rounds and a tail of 2): window 0 (open road)
     and window 10 (obstacle rows active) of the golden MPC+OBCA windows, both against the sparse un-condensed solve
     (SuperLU, refined on an extended-precision residual) by the module's rule."""
-    import ttmpc
-    from conftest import GOLDEN
-    from ttmpc import scenarios as sc
-    g = np.load(GOLDEN / "reference_numpy.npz")
-    obs = g["obstacles"]
-    x0, xr, ur = sc.mpc_obs_batch(g["state_traj"], g["input_traj"], 16, 50, seed=0)
-    pick = [0, 10]
-    p = dict(sc.OBCA_PARAMS, dt=0.05)
-    bnd = (sc.XLB, sc.XUB, sc.ULB, sc.UUB)
-    s = ttmpc.ObcaSolver(50, p, sc.OBCA_Q, sc.OBCA_R, *bnd, obs, variant=ttmpc.TT_VARIANT_TRACK_OBCA)
-    X, U, Z, st, it, kk, I = s.solve(x0[pick], xref=xr[pick], uref=ur[pick], iterate=True)
-    assert np.all(st <= 1), st
-    gX, gU = orf.upstream(50)
+    s, P, st, I, (gX, gU), _, _ = hx.golden_windows([0, 10])
     r = s.vjp(I, st, np.tile(gX, (2, 1, 1)), np.tile(gU, (2, 1, 1)))
     assert np.all(r.vjp_status == 0), r.vjp_status
-    P = orf.problem(50, p, sc.OBCA_Q, sc.OBCA_R, bnd, obs)
     _check_against_dense(P, I[0], gX, gU, r, 0, "window 0", sparse=True)
     assert np.abs(orf.unpack(I[1], 50, 11)["yd"][..., 0]).max() > 1.0
     _check_against_dense(P, I[1], gX, gU, r, 1, "window 10", sparse=True)
 
 
-def _device_call(s, B, I, st, gX, gU, want=("g_x0", "g_xref", "g_uref", "vjp_status")):
-    import torch
-    N = s.N
-    dev = torch.device("cuda", s.device)
-    dI = torch.as_tensor(I, device=dev).contiguous()
-    dst = torch.as_tensor(st.astype(np.int32), device=dev)
-    dgx = None if gX is None else torch.as_tensor(gX, device=dev).contiguous()
-    dgu = None if gU is None else torch.as_tensor(gU, device=dev).contiguous()
-    out = {"g_x0": torch.full((B, 6), 7.0, dtype=torch.float64, device=dev),
-           "g_xref": torch.full((B, N + 1, 6), 7.0, dtype=torch.float64, device=dev),
-           "g_uref": torch.full((B, N, 2), 7.0, dtype=torch.float64, device=dev),
-           "vjp_status": torch.full((B,), 7, dtype=torch.int32, device=dev)}
-    s.vjp_device(B, dI.data_ptr(), dst.data_ptr(), grad_x=0 if dgx is None else dgx.data_ptr(),
-                 grad_u=0 if dgu is None else dgu.data_ptr(),
-                 **{k: (v.data_ptr() if k in want else 0) for k, v in out.items()},
-                 stream=torch.cuda.current_stream(dev).cuda_stream)
-    torch.cuda.synchronize(dev)
-    return {k: v.cpu().numpy() for k, v in out.items()}
+_device_call = hx.device_call
 
 
 def test_determinism_tiling_and_host_entry():
@@ -172,11 +97,7 @@ def test_determinism_tiling_and_host_entry():
     for k, ref in (("g_x0", r.g_x0), ("g_xref", r.g_xref), ("g_uref", r.g_uref), ("vjp_status", r.vjp_status)):
         assert np.array_equal(d4[k], ref), k
     T = 300
-    big = _device_call(s, 4 * T, np.tile(I, (T, 1)), np.tile(st, T), np.tile(gXb, (T, 1, 1)), np.tile(gUb, (T, 1, 1)))
-    again = _device_call(s, 4 * T, np.tile(I, (T, 1)), np.tile(st, T), np.tile(gXb, (T, 1, 1)), np.tile(gUb, (T, 1, 1)))
-    for k in d4:
-        assert np.array_equal(big[k], again[k]), k
-        assert np.array_equal(big[k].reshape((T,) + d4[k].shape), np.broadcast_to(d4[k], (T,) + d4[k].shape)), k
+    hx.check_tiling(lambda *a: _device_call(s, 4 * T, *a), d4, T, I, st, gXb, gUb)
 
 
 def test_null_members_and_null_gradient():
