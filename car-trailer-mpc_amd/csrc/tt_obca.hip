@@ -803,6 +803,27 @@ __device__ __forceinline__ void ftb_lo(double v, double lo, double d, double tau
 __device__ __forceinline__ void ftb_hi(double v, double hi, double d, double tau, double& a) {
     if (d > 0.0) a = fmin(a, tau * (hi - v) * inv(d));
 }
+// ---- one bound row: slack sl > 0 moving by d (a lower bound's own step; an upper bound passes -d, which is exact)
+// and its multiplier z, whose Newton step is dz = mu / sl - z - z / sl d.  Two spellings that round differently, each
+// the oracle's expression at its place: the quotient form divides (phase_recover, pn_step, phase_leave_resto); the
+// reciprocal form multiplies by isl = inv(sl), so the product is rounded twice (nres_block, phase_nres' stage rows,
+// the update pass).  The final rows of phase_nres are mixed, as the oracle is there: dz_quot under ftb_dual_rcp.
+// A site never moves from one form to the other.
+__device__ __forceinline__ double dz_quot(double z, double sl, double d, double mu) { return mu / sl - z - z / sl * d; }
+__device__ __forceinline__ double dz_rcp(double z, double isl, double d, double mu) { return mu * isl - z - z * isl * d; }
+// dual fraction to the boundary of z + az dz >= (1 - tau) z, in the same two forms
+__device__ __forceinline__ void ftb_dual_quot(double z, double dz, double tau, double& az) {
+    if (dz < 0.0) az = fmin(az, -tau * z / dz);
+}
+__device__ __forceinline__ void ftb_dual_rcp(double z, double dz, double tau, double& az) {
+    if (dz < 0.0) az = fmin(az, -tau * z * inv(dz));
+}
+// the accepted multiplier z + az dz (reciprocal form) under the kappa_sigma clamp at the new slack sn
+__device__ __forceinline__ double mult_step(double z, double sl, double d, double sn, double mu, double az) {
+    double zn = z + az * dz_rcp(z, inv(sl), d, mu);
+    clamp_mult(zn, sn, mu);
+    return zn;
+}
 
 // ---------------- restoration-phase elastic pairs (IPOPT MinC_1NrmRestorationPhase) ----------------
 // closed-form start: argmin rho (p + n) - mu (ln p + ln n) subject to p - n = r
@@ -970,7 +991,7 @@ struct ChunkPass {
     double mu, dw, tau;
     int pass, buf, prep, mode;
 };
-__device__ void do_chunks(const Ctx& c, const LShared& sh, ChunkPass p, int c0, int c1, bool helper);
+__device__ void do_chunks(const Ctx& c, const LShared& sh, ChunkPass p, int c0, int c1);
 
 __device__ __forceinline__ gu64* board_line(LArgs& a, int b) { return (gu64*)(a.board + (size_t)b * kObcaBoardStride); }
 __device__ __forceinline__ unsigned long long ld_rlx(gu64* p) {
@@ -987,9 +1008,6 @@ __device__ __forceinline__ double bitsd(unsigned long long v) { return __longlon
 constexpr unsigned long long kSpinTicks = 500000000ull;  // 5 s of the 100 MHz s_memrealtime clock
 constexpr unsigned long long kStartTicks = 2000ull;  // 20 us: how long a helper waits for the batch to have started
 constexpr int kStatusHandoffTimeout = 6;  // TT_HANDOFF_TIMEOUT (include/ttmpc.h)
-#ifndef OBCA_HELPER_RELEASE
-#define OBCA_HELPER_RELEASE 1
-#endif
 
 // one block pass of this instance (every thread of its workgroup), ending with a workgroup barrier
 __device__ void run_pass(const Ctx& c, LShared& sh, const ChunkPass& p) {
@@ -1012,7 +1030,7 @@ __device__ void run_pass(const Ctx& c, LShared& sh, const ChunkPass& p) {
     const bool shared = sh.hcur != 0;
     __syncthreads();
     if (!shared) {
-        do_chunks(c, sh, p, 0, nch, false);
+        do_chunks(c, sh, p, 0, nch);
         __syncthreads();
         return;
     }
@@ -1039,7 +1057,7 @@ __device__ void run_pass(const Ctx& c, LShared& sh, const ChunkPass& p) {
         const int ci = sh.hcur;
         __syncthreads();
         if (ci >= nch) break;
-        do_chunks(c, sh, p, ci, ci + 1, false);
+        do_chunks(c, sh, p, ci, ci + 1);
         ++own;
     }
     if (threadIdx.x == 0) {
@@ -1227,9 +1245,10 @@ __device__ __noinline__ int phase_factor(const Ctx& c, LShared& sh, double mu, d
     return fail[0] != 0.0 ? F_ZERO : fail[1] != 0.0 ? F_MANY : fail[2] != 0.0 ? F_FEW : F_OK;
 }
 
-// Stage data of the serial sweeps, either straight from the HBM workspace (GSrc) or from LDS copies
-// staged by all four waves before the sweep (LSrc: region A = sweep inputs, region B = its outputs).
-// CR is the effective dynamics-row residual S_CE.
+// Stage data of the serial sweeps, either straight from the HBM workspace (GSrc: the one HBM source of every sweep,
+// horizons whose records do not fit the LDS budget) or from LDS copies staged by all four waves before the sweep
+// (LSrc: region A = sweep inputs, region B = its outputs; SoftA, SoftF, VecL below).  CR is the effective
+// dynamics-row residual S_CE.
 struct GSrc {
     const Ctx& c;
     __device__ double QT(int i, int k) const { return c.S(S_QT + i, k); }
@@ -1242,6 +1261,9 @@ struct GSrc {
     __device__ double PV(int i, int k) const { return c.S(S_PV + i, k); }
     __device__ double K(int i, int k) const { return c.S(S_K + i, k); }
     __device__ double KF(int i, int k) const { return c.S(S_KF + i, k); }
+    __device__ double SD(int i, int k) const { return c.S(S_SD + i, k); }
+    __device__ double Y(int i, int k) const { return c.S(S_Y + i, k); }
+    __device__ double GI(int i, int k) const { return c.S(S_GI + i, k); }
     __device__ void setP(int i, int k, double v) const { c.S(S_P + i, k) = v; }
     __device__ void setPV(int i, int k, double v) const { c.S(S_PV + i, k) = v; }
     __device__ void setK(int i, int k, double v) const { c.S(S_K + i, k) = v; }
@@ -1249,27 +1271,29 @@ struct GSrc {
     __device__ void setGI(int i, int k, double v) const { c.S(S_GI + i, k) = v; }
 };
 // region A per stage: QT 21 | QV 6 | RT 3 | RV 2 | AJ 9 | CR 6  (47);  region B: P 21 | PV 6 | K 12 | KF 2 | G^-1 3 (44)
-constexpr int LA = 47, LB = 44;
 struct LSrc {
+    enum : int { aQT = 0, aQV = 21, aRT = 27, aRV = 30, aAJ = 32, aCR = 41, aEND = 47 };
+    enum : int { bP = 0, bPV = 21, bK = 27, bKF = 39, bGI = 41, bEND = 44 };
     const lds_double* A;
     lds_double* B;
-    __device__ double QT(int i, int k) const { return A[k * LA + i]; }
-    __device__ double QV(int i, int k) const { return A[k * LA + 21 + i]; }
-    __device__ double RT(int i, int k) const { return A[k * LA + 27 + i]; }
-    __device__ double RV(int i, int k) const { return A[k * LA + 30 + i]; }
-    __device__ double AJ(int i, int k) const { return A[k * LA + 32 + i]; }
-    __device__ double CR(int i, int k) const { return A[k * LA + 41 + i]; }
-    __device__ double P(int i, int k) const { return B[k * LB + i]; }
-    __device__ double PV(int i, int k) const { return B[k * LB + 21 + i]; }
-    __device__ double K(int i, int k) const { return B[k * LB + 27 + i]; }
-    __device__ double KF(int i, int k) const { return B[k * LB + 39 + i]; }
-    __device__ void setP(int i, int k, double v) const { B[k * LB + i] = v; }
-    __device__ void setPV(int i, int k, double v) const { B[k * LB + 21 + i] = v; }
-    __device__ void setK(int i, int k, double v) const { B[k * LB + 27 + i] = v; }
-    __device__ void setKF(int i, int k, double v) const { B[k * LB + 39 + i] = v; }
-    __device__ double GI(int i, int k) const { return B[k * LB + 41 + i]; }
-    __device__ void setGI(int i, int k, double v) const { B[k * LB + 41 + i] = v; }
+    __device__ double QT(int i, int k) const { return A[k * aEND + aQT + i]; }
+    __device__ double QV(int i, int k) const { return A[k * aEND + aQV + i]; }
+    __device__ double RT(int i, int k) const { return A[k * aEND + aRT + i]; }
+    __device__ double RV(int i, int k) const { return A[k * aEND + aRV + i]; }
+    __device__ double AJ(int i, int k) const { return A[k * aEND + aAJ + i]; }
+    __device__ double CR(int i, int k) const { return A[k * aEND + aCR + i]; }
+    __device__ double P(int i, int k) const { return B[k * bEND + bP + i]; }
+    __device__ double PV(int i, int k) const { return B[k * bEND + bPV + i]; }
+    __device__ double K(int i, int k) const { return B[k * bEND + bK + i]; }
+    __device__ double KF(int i, int k) const { return B[k * bEND + bKF + i]; }
+    __device__ double GI(int i, int k) const { return B[k * bEND + bGI + i]; }
+    __device__ void setP(int i, int k, double v) const { B[k * bEND + bP + i] = v; }
+    __device__ void setPV(int i, int k, double v) const { B[k * bEND + bPV + i] = v; }
+    __device__ void setK(int i, int k, double v) const { B[k * bEND + bK + i] = v; }
+    __device__ void setKF(int i, int k, double v) const { B[k * bEND + bKF + i] = v; }
+    __device__ void setGI(int i, int k, double v) const { B[k * bEND + bGI + i] = v; }
 };
+constexpr int LA = LSrc::aEND, LB = LSrc::bEND;
 __host__ __device__ inline size_t obca_lds_bytes(int N) { return (size_t)(LA + LB) * (N + 1) * 8; }  // >= the soft records (53, 77)
 constexpr size_t kObcaLdsMax = 150 * 1024;  // dynamic LDS budget for the staged sweeps (+ static Shared)
 
@@ -1301,15 +1325,16 @@ __device__ __forceinline__ void stage_copy(const Ctx& c, double* A, Val value) {
 }
 __device__ __noinline__ void stage_inputs(const Ctx& c, double* A) {
     const WsView vw = ws_view(c);
+    using L = LSrc;
     stage_copy<LA>(c, A, [&](int f, int k) -> double {
         int g;
-        if (f < 21) g = S_QT + f;
-        else if (f < 27) g = S_QV + f - 21;
-        else if (f < 30) g = S_RT + f - 27;
-        else if (f < 32) g = S_RV + f - 30;
-        else if (f < 41) g = S_AJ + f - 32;
-        else g = S_CE + f - 41;
-        return (k < c.N || (f < 27 || f >= 41)) ? (double)vw.S(g, k) : 0.0;
+        if (f < L::aQV) g = S_QT + f - L::aQT;
+        else if (f < L::aRT) g = S_QV + f - L::aQV;
+        else if (f < L::aRV) g = S_RT + f - L::aRT;
+        else if (f < L::aAJ) g = S_RV + f - L::aRV;
+        else if (f < L::aCR) g = S_AJ + f - L::aAJ;
+        else g = S_CE + f - L::aCR;
+        return (k < c.N || (f < L::aRT || f >= L::aCR)) ? (double)vw.S(g, k) : 0.0;  // stage N: RT, RV, AJ zero
     });
 }
 
@@ -1568,39 +1593,30 @@ __device__ __noinline__ void forward(const Ctx& c, const Src src, int buf) {
 __device__ __forceinline__ void lds_order() { asm volatile("" ::: "memory"); }
 
 // region of the soft sweep's inputs, per stage: QT 21 | QV 6 | RT 3 | RV 2 | AJ 9 | CE 6 | SD 6  (53)
-constexpr int LAS = 53;
 struct SoftA {
+    enum : int { oQT = 0, oQV = 21, oRT = 27, oRV = 30, oAJ = 32, oCR = 41, oSD = 47, oEND = 53 };
     const lds_double* A;
-    __device__ double QT(int i, int k) const { return A[k * LAS + i]; }
-    __device__ double QV(int i, int k) const { return A[k * LAS + 21 + i]; }
-    __device__ double RT(int i, int k) const { return A[k * LAS + 27 + i]; }
-    __device__ double RV(int i, int k) const { return A[k * LAS + 30 + i]; }
-    __device__ double AJ(int i, int k) const { return A[k * LAS + 32 + i]; }
-    __device__ double CR(int i, int k) const { return A[k * LAS + 41 + i]; }
-    __device__ double SD(int i, int k) const { return A[k * LAS + 47 + i]; }
-};
-struct SoftG {
-    const Ctx& c;
-    __device__ double QT(int i, int k) const { return c.S(S_QT + i, k); }
-    __device__ double QV(int i, int k) const { return c.S(S_QV + i, k); }
-    __device__ double RT(int i, int k) const { return c.S(S_RT + i, k); }
-    __device__ double RV(int i, int k) const { return c.S(S_RV + i, k); }
-    __device__ double AJ(int i, int k) const { return c.S(S_AJ + i, k); }
-    __device__ double CR(int i, int k) const { return c.S(S_CE + i, k); }
-    __device__ double SD(int i, int k) const { return c.S(S_SD + i, k); }
+    __device__ double QT(int i, int k) const { return A[k * oEND + oQT + i]; }
+    __device__ double QV(int i, int k) const { return A[k * oEND + oQV + i]; }
+    __device__ double RT(int i, int k) const { return A[k * oEND + oRT + i]; }
+    __device__ double RV(int i, int k) const { return A[k * oEND + oRV + i]; }
+    __device__ double AJ(int i, int k) const { return A[k * oEND + oAJ + i]; }
+    __device__ double CR(int i, int k) const { return A[k * oEND + oCR + i]; }
+    __device__ double SD(int i, int k) const { return A[k * oEND + oSD + i]; }
 };
 __device__ __noinline__ void stage_soft_inputs(const Ctx& c, double* A) {
     const WsView vw = ws_view(c);
-    stage_copy<LAS>(c, A, [&](int f, int k) -> double {
+    using L = SoftA;
+    stage_copy<L::oEND>(c, A, [&](int f, int k) -> double {
         int g;
-        if (f < 21) g = S_QT + f;
-        else if (f < 27) g = S_QV + f - 21;
-        else if (f < 30) g = S_RT + f - 27;
-        else if (f < 32) g = S_RV + f - 30;
-        else if (f < 41) g = S_AJ + f - 32;
-        else if (f < 47) g = S_CE + f - 41;
-        else g = S_SD + f - 47;
-        return (k < c.N || f < 27 || f >= 41) ? (double)vw.S(g, k) : 0.0;
+        if (f < L::oQV) g = S_QT + f - L::oQT;
+        else if (f < L::oRT) g = S_QV + f - L::oQV;
+        else if (f < L::oRV) g = S_RT + f - L::oRT;
+        else if (f < L::oAJ) g = S_RV + f - L::oRV;
+        else if (f < L::oCR) g = S_AJ + f - L::oAJ;
+        else if (f < L::oSD) g = S_CE + f - L::oCR;
+        else g = S_SD + f - L::oSD;
+        return (k < c.N || f < L::oRT || f >= L::oCR) ? (double)vw.S(g, k) : 0.0;  // stage N: RT, RV, AJ zero
     });
 }
 // operands of one soft stage: the softening of stage k (S entries of the lane) and the hard step k-1
@@ -1768,43 +1784,35 @@ __device__ __noinline__ void riccati_soft(const Ctx& c, LShared& sh, const Src s
 }
 
 // forward sweep with soft rows: yhat = A dx + B du - r~; dx = yhat - Y (P yhat + p).  Operands from LDS
-// copies staged by all four waves (SoftF) or from HBM (GSrc + S_Y); the 6-vector chain is carried by
+// copies staged by all four waves (SoftF) or from HBM (GSrc); the 6-vector chain is carried by
 // every lane (wave-uniform), lanes 0..5 write row r of the stage outputs.
 // staged record per stage: P 21 | PV 6 | K 12 | KF 2 | Y 21 | AJ 9 | CE 6  (77)
-constexpr int LFS = 77;
 struct SoftF {
+    enum : int { oP = 0, oPV = 21, oK = 27, oKF = 39, oY = 41, oAJ = 62, oCR = 71, oEND = 77 };
     const lds_double* A;
-    __device__ double P(int i, int k) const { return A[k * LFS + i]; }
-    __device__ double PV(int i, int k) const { return A[k * LFS + 21 + i]; }
-    __device__ double K(int i, int k) const { return A[k * LFS + 27 + i]; }
-    __device__ double KF(int i, int k) const { return A[k * LFS + 39 + i]; }
-    __device__ double Y(int i, int k) const { return A[k * LFS + 41 + i]; }
-    __device__ double AJ(int i, int k) const { return A[k * LFS + 62 + i]; }
-    __device__ double CR(int i, int k) const { return A[k * LFS + 71 + i]; }
-};
-struct SoftFG {
-    const Ctx& c;
-    __device__ double P(int i, int k) const { return c.S(S_P + i, k); }
-    __device__ double PV(int i, int k) const { return c.S(S_PV + i, k); }
-    __device__ double K(int i, int k) const { return c.S(S_K + i, k); }
-    __device__ double KF(int i, int k) const { return c.S(S_KF + i, k); }
-    __device__ double Y(int i, int k) const { return c.S(S_Y + i, k); }
-    __device__ double AJ(int i, int k) const { return c.S(S_AJ + i, k); }
-    __device__ double CR(int i, int k) const { return c.S(S_CE + i, k); }
+    __device__ double P(int i, int k) const { return A[k * oEND + oP + i]; }
+    __device__ double PV(int i, int k) const { return A[k * oEND + oPV + i]; }
+    __device__ double K(int i, int k) const { return A[k * oEND + oK + i]; }
+    __device__ double KF(int i, int k) const { return A[k * oEND + oKF + i]; }
+    __device__ double Y(int i, int k) const { return A[k * oEND + oY + i]; }
+    __device__ double AJ(int i, int k) const { return A[k * oEND + oAJ + i]; }
+    __device__ double CR(int i, int k) const { return A[k * oEND + oCR + i]; }
 };
 __device__ __noinline__ void stage_soft_forward(const Ctx& c, double* A, bool soft = true) {
     const WsView vw = ws_view(c);
-    stage_copy<LFS>(c, A, [&](int f, int k) -> double {
-        if (!soft && f >= 41 && f < 62) return 0.0;  // hard rows: Y unused
+    using L = SoftF;
+    stage_copy<L::oEND>(c, A, [&](int f, int k) -> double {
+        if (!soft && f >= L::oY && f < L::oAJ) return 0.0;  // hard rows: Y unused
         int g;
-        if (f < 21) g = S_P + f;
-        else if (f < 27) g = S_PV + f - 21;
-        else if (f < 39) g = S_K + f - 27;
-        else if (f < 41) g = S_KF + f - 39;
-        else if (f < 62) g = S_Y + f - 41;
-        else if (f < 71) g = S_AJ + f - 62;
-        else g = S_CE + f - 71;
-        return (k < c.N || f < 27 || (f >= 41 && f < 62) || f >= 71) ? (double)vw.S(g, k) : 0.0;
+        if (f < L::oPV) g = S_P + f - L::oP;
+        else if (f < L::oK) g = S_PV + f - L::oPV;
+        else if (f < L::oKF) g = S_K + f - L::oK;
+        else if (f < L::oY) g = S_KF + f - L::oKF;
+        else if (f < L::oAJ) g = S_Y + f - L::oY;
+        else if (f < L::oCR) g = S_AJ + f - L::oAJ;
+        else g = S_CE + f - L::oCR;
+        // stage N: K, KF, AJ zero
+        return (k < c.N || f < L::oK || (f >= L::oY && f < L::oAJ) || f >= L::oCR) ? (double)vw.S(g, k) : 0.0;
     });
 }
 template <class Src>
@@ -1904,9 +1912,8 @@ __device__ __forceinline__ void pn_step(double p, double n, double zp, double zn
     dn = (-yp - t.gn) / t.Dn;
     ftb_lo(p, 0.0, dp, tau, ap);
     ftb_lo(n, 0.0, dn, tau, ap);
-    const double dzp = mu / p - zp - zp / p * dp, dzn = mu / n - zn - zn / n * dn;
-    if (dzp < 0.0) az = fmin(az, -tau * zp / dzp);
-    if (dzn < 0.0) az = fmin(az, -tau * zn / dzn);
+    ftb_dual_quot(zp, dz_quot(zp, p, dp, mu), tau, az);
+    ftb_dual_quot(zn, dz_quot(zn, n, dn, mu), tau, az);
     Dm += t.gp * dp + t.gn * dn;
     rel = fmax(rel, fmax(fabs(dp) / (1.0 + fabs(p)), fabs(dn) / (1.0 + fabs(n))));
 }
@@ -1934,15 +1941,13 @@ __device__ __noinline__ void phase_recover(const Ctx& c, LShared& sh, double mu,
                 const double sl = xv - c.xl[i], z = vw.S(S_ZLX + i, k);
                 g -= mu / sl;
                 ftb_lo(xv, c.xl[i], d, tau, ap);
-                const double dz = mu / sl - z - z / sl * d;
-                if (dz < 0.0) az = fmin(az, -tau * z / dz);
+                ftb_dual_quot(z, dz_quot(z, sl, d, mu), tau, az);
             }
             if (c.hux(i)) {
                 const double sl = c.xu[i] - xv, z = vw.S(S_ZUX + i, k);
                 g += mu / sl;
                 ftb_hi(xv, c.xu[i], d, tau, ap);
-                const double dz = mu / sl - z + z / sl * d;
-                if (dz < 0.0) az = fmin(az, -tau * z / dz);
+                ftb_dual_quot(z, dz_quot(z, sl, -d, mu), tau, az);
             }
             Dm += g * d;
             const double yp = vw.S(S_YCP + 6 * buf + i, k);
@@ -1965,15 +1970,13 @@ __device__ __noinline__ void phase_recover(const Ctx& c, LShared& sh, double mu,
                     const double sl = uv - c.ul[i], z = vw.S(S_ZLU + i, k);
                     g -= mu / sl;
                     ftb_lo(uv, c.ul[i], d, tau, ap);
-                    const double dz = mu / sl - z - z / sl * d;
-                    if (dz < 0.0) az = fmin(az, -tau * z / dz);
+                    ftb_dual_quot(z, dz_quot(z, sl, d, mu), tau, az);
                 }
                 if (c.huu(i)) {
                     const double sl = c.uu[i] - uv, z = vw.S(S_ZUU + i, k);
                     g += mu / sl;
                     ftb_hi(uv, c.uu[i], d, tau, ap);
-                    const double dz = mu / sl - z + z / sl * d;
-                    if (dz < 0.0) az = fmin(az, -tau * z / dz);
+                    ftb_dual_quot(z, dz_quot(z, sl, -d, mu), tau, az);
                 }
                 Dm += g * d;
             }
@@ -1993,8 +1996,7 @@ __device__ __noinline__ void phase_recover(const Ctx& c, LShared& sh, double mu,
                 rel = fmax(rel, fabs(d) / (1.0 + fabs(wv)));
                 Dm += fw[e] * d;
                 ftb_lo(wv, -RELAX, d, tau, ap);
-                const double dz = mu / sl - z - z / sl * d;
-                if (dz < 0.0) az = fmin(az, -tau * z / dz);
+                ftb_dual_quot(z, dz_quot(z, sl, d, mu), tau, az);
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -2008,13 +2010,11 @@ __device__ __noinline__ void phase_recover(const Ctx& c, LShared& sh, double mu,
                 Dm += gs * ds;
                 const double slu = c.rU(r) - s;
                 ftb_hi(s, c.rU(r), ds, tau, ap);
-                const double dvu = mu / slu - vu + vu / slu * ds;
-                if (dvu < 0.0) az = fmin(az, -tau * vu / dvu);
+                ftb_dual_quot(vu, dz_quot(vu, slu, -ds, mu), tau, az);
                 if (c.hrl(r)) {
                     const double sll = s - c.rL(r);
                     ftb_lo(s, c.rL(r), ds, tau, ap);
-                    const double dvl = mu / sll - vl - vl / sll * ds;
-                    if (dvl < 0.0) az = fmin(az, -tau * vl / dvl);
+                    ftb_dual_quot(vl, dz_quot(vl, sll, ds, mu), tau, az);
                 }
                 if (rs) {
                     double dp, dn;
@@ -2038,10 +2038,8 @@ __device__ __noinline__ void phase_recover(const Ctx& c, LShared& sh, double mu,
                 Dm += gs * ds;
                 ftb_lo(sh.sf[i], c.fL, ds, tau, ap);
                 ftb_hi(sh.sf[i], c.fU, ds, tau, ap);
-                const double dvl = mu / sl - sh.vLf[i] - sh.vLf[i] / sl * ds;
-                const double dvu = mu / su - sh.vUf[i] + sh.vUf[i] / su * ds;
-                if (dvl < 0.0) az = fmin(az, -tau * sh.vLf[i] / dvl);
-                if (dvu < 0.0) az = fmin(az, -tau * sh.vUf[i] / dvu);
+                ftb_dual_quot(sh.vLf[i], dz_quot(sh.vLf[i], sl, ds, mu), tau, az);
+                ftb_dual_quot(sh.vUf[i], dz_quot(sh.vUf[i], su, -ds, mu), tau, az);
                 if (rs) {
                     double dp, dn;
                     pn_step(sh.pf[i], sh.nf[i], sh.zpf[i], sh.znf[i], yp, mu, dw, tau, dp, dn, ap, az, Dm, rel);
@@ -2056,191 +2054,21 @@ __device__ __noinline__ void phase_recover(const Ctx& c, LShared& sh, double mu,
     wg_reduce(sh, out, ops);
 }
 
-// ======== phase: trial point x + alpha d (step buffer buf) -> theta, phi (barrier objective), bad ========
-// of the current NLP; also stores the trial residual rows (for second-order corrections)
-template <bool RS_>
-__device__ __noinline__ void phase_trial_t(const Ctx& c, LShared& sh, double mu, double alpha, int buf, double (&out)[3]) {
-    LArgs& a = *c.a;
-    const int N = c.N;
-    const bool plan = c.plan();
-    constexpr bool rs = RS_;
-    double th = 0.0, F = 0.0, logs = 0.0, bad = 0.0;
-    for (int k = (int)threadIdx.x; k <= N; k += T) {
-        double x[6], u[2] = {0.0, 0.0};
-#pragma unroll
-        for (int i = 0; i < 6; ++i) x[i] = c.S(S_X + i, k) + alpha * c.S(S_DX + 6 * buf + i, k);
-        if (k < N)
-#pragma unroll
-            for (int i = 0; i < 2; ++i) u[i] = c.S(S_U + i, k) + alpha * c.S(S_DU + 2 * buf + i, k);
-        // the tracking / plan cost first: its target loads are issued before any of the pass's stores (a load behind a
-        // store waits for it)
-        const double scost = rs ? 0.0 : stage_cost(c, k, x, u);
-        LogSum ls;
-        bool ok = true;
-        double Fr = 0.0, prox = 0.0;  // restoration objective of this stage: rho sum(p + n), D_R-weighted distances
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            if (c.hlx(i)) { const double sl = x[i] - c.xl[i]; ok &= sl > 0.0; ls.add(sl); }
-            if (c.hux(i)) { const double sl = c.xu[i] - x[i]; ok &= sl > 0.0; ls.add(sl); }
-            if (rs) { const double e = x[i] - c.S(S_XR + i, k); prox += c.S(S_DRX + i, k) * e * e; }
-        }
-        if (k < N)
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                if (c.hlu(i)) { const double sl = u[i] - c.ul[i]; ok &= sl > 0.0; ls.add(sl); }
-                if (c.huu(i)) { const double sl = c.uu[i] - u[i]; ok &= sl > 0.0; ls.add(sl); }
-                if (rs) { const double e = u[i] - c.S(S_UR + i, k); prox += c.S(S_DRU + i, k) * e * e; }
-            }
-        // dynamics residual c_{k+1} = x_{k+1} - F(x_k, u_k) (thread k), c_0 = x_0 - x_init; stored after the
-        // block loop (and each block's trial residual after the next block's loads): a store ahead of a load
-        // in the in-order vmcnt queue makes the load's wait include it
-        double ck[6] = {0, 0, 0, 0, 0, 0}, cn[6] = {0, 0, 0, 0, 0, 0};
-        if (k == 0) {
-#pragma unroll
-            for (int i = 0; i < 6; ++i) ck[i] = x[i] - a.x0[6 * (size_t)c.b + i];
-        }
-        if (k < N) {
-            double fo[6];
-            model_f(a, x, u, fo);
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                const double xn = c.S(S_X + i, k + 1) + alpha * c.S(S_DX + 6 * buf + i, k + 1);
-                double cv = xn - (x[i] + a.dt * fo[i]);
-                if (rs) {  // row of stage k+1 (owned there: read its elastic pair)
-                    const double p = c.S(S_PR + i, k + 1) + alpha * c.S(S_DP + 6 * buf + i, k + 1);
-                    const double n = c.S(S_NR + i, k + 1) + alpha * c.S(S_DN + 6 * buf + i, k + 1);
-                    cv -= p - n;
-                }
-                cn[i] = cv;
-                th += fabs(cv);
-            }
-        }
-        if (rs)  // elastic pairs of this stage's own dynamics rows: barrier + objective (+ row 0's residual)
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                const double p = c.S(S_PR + i, k) + alpha * c.S(S_DP + 6 * buf + i, k);
-                const double n = c.S(S_NR + i, k) + alpha * c.S(S_DN + 6 * buf + i, k);
-                ok &= p > 0.0 && n > 0.0;
-                ls.add(p);
-                ls.add(n);
-                Fr += p + n;
-                if (k == 0) ck[i] -= p - n;
-            }
-        if (k == 0)
-#pragma unroll
-            for (int i = 0; i < 6; ++i) th += fabs(ck[i]);
-        const Trig tr = stage_trig(x);
-        double pdt[4] = {0, 0, 0, 0};
-        int pj = -1;
-        for (int j = 0; j < c.nbk; ++j) {
-            double w[8], d[4], wr[8], drw[8], sv[4], pv[4], nv[4];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                w[e] = c.B(B_W + e, j, k) + alpha * c.B(B_DW + 8 * buf + e, j, k);
-                if (rs) { wr[e] = c.B(B_WR + e, j, k); drw[e] = c.B(B_DRW + e, j, k); }
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                sv[r] = c.B(B_S + r, j, k) + alpha * c.B(B_DS + 4 * buf + r, j, k);
-                if (rs) {
-                    pv[r] = c.B(B_PR + r, j, k) + alpha * c.B(B_DP + 4 * buf + r, j, k);
-                    nv[r] = c.B(B_NR + r, j, k) + alpha * c.B(B_DN + 4 * buf + r, j, k);
-                }
-            }
-            if (pj >= 0)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) c.B(B_DT + r, pj, k) = pdt[r];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const double sl = w[e] + RELAX;
-                ok &= sl > 0.0;
-                ls.add(sl);
-                if (rs) { const double ew = w[e] - wr[e]; prox += drw[e] * ew * ew; }
-            }
-            blk_vals(a, x, tr, j, w, d);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const double s = sv[r];
-                double res = d[r] - s;
-                if (rs) {
-                    const double p = pv[r];
-                    const double n = nv[r];
-                    ok &= p > 0.0 && n > 0.0;
-                    ls.add(p);
-                    ls.add(n);
-                    Fr += p + n;
-                    res -= p - n;
-                }
-                pdt[r] = res;
-                th += fabs(res);
-                const double su = c.rU(r) - s;
-                ok &= su > 0.0;
-                ls.add(su);
-                if (c.hrl(r)) { const double sl = s - c.rL(r); ok &= sl > 0.0; ls.add(sl); }
-            }
-            pj = j;
-        }
-        if (pj >= 0)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) c.B(B_DT + r, pj, k) = pdt[r];
-        if (k < N)
-#pragma unroll
-            for (int i = 0; i < 6; ++i) c.S(S_CT + i, k + 1) = cn[i];
-        if (k == 0)
-#pragma unroll
-            for (int i = 0; i < 6; ++i) c.S(S_CT + i, 0) = ck[i];
-        if (k == N && plan)
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                const double s = sh.sf[i] + alpha * sh.dsf[buf][i];
-                double res = (x[i] - c.tgt_x[i]) - s;
-                if (rs) {
-                    const double p = sh.pf[i] + alpha * sh.dpf[buf][i], n = sh.nf[i] + alpha * sh.dnf[buf][i];
-                    ok &= p > 0.0 && n > 0.0;
-                    ls.add(p);
-                    ls.add(n);
-                    Fr += p + n;
-                    res -= p - n;
-                }
-                sh.dft[i] = res;
-                th += fabs(res);
-                const double sl = s - c.fL, su = c.fU - s;
-                ok &= sl > 0.0 && su > 0.0;
-                ls.add(sl);
-                ls.add(su);
-            }
-        F += rs ? RHO * Fr + 0.5 * sh.zeta * prox : scost;
-        if (!ok) bad = 1.0;
-        else logs += ls.value();
-    }
-    double v[4] = {th, F, logs, bad};
-    const int ops[4] = {R_SUM, R_SUM, R_SUM, R_MAX};
-    wg_reduce(sh, v, ops);
-    out[0] = v[3] > 0.0 ? INFINITY : v[0];
-    out[1] = v[3] > 0.0 ? INFINITY : v[1] - mu * v[2];
-    out[2] = v[3];
-}
-
-// one instantiation per problem (original / restoration phase): the original problem's skips every restoration
-// branch and its loads (bitwise the same results, profiles/r03/ab_one/)
-__device__ __forceinline__ void phase_trial(const Ctx& c, LShared& sh, double mu, double alpha, int buf, double (&out)[3]) {
-    sh.R ? phase_trial_t<true>(c, sh, mu, alpha, buf, out) : phase_trial_t<false>(c, sh, mu, alpha, buf, out);
-}
-
-
-// ======== phase: NA line-search trial points in one pass (the backtracking trials after the first) ========
-// The filter line search tries alpha, alpha/2, ... one after the other (8.8 trial points per iteration in the C4 tail,
-// profiles/r05/session_o/tail.txt), and each trial is a full pass over the trajectory whose time is its memory latency,
-// not its arithmetic.  This pass loads the iterate and the step once and evaluates NA step lengths: for each the same
-// expressions as phase_trial_t in the same order, so out[a] is bitwise phase_trial_t's result for alphas[a].  No
-// trial residual rows are stored: only the first trial of an iteration feeds a second-order correction.
-template <bool RS_, int NA>
+// ======== phase: NA trial points x + al[q] d (step buffer buf) -> theta, phi (barrier objective), bad ========
+// of the current NLP.  The filter line search tries alpha, alpha/2, ... one after the other (8.8 trial points per
+// iteration in the C4 tail, profiles/r05/session_o/tail.txt), and each trial is a full pass over the trajectory whose
+// time is its memory latency, not its arithmetic.  This pass loads the iterate and the step once and evaluates NA step
+// lengths, each with the same expressions in the same order, so out[q] does not depend on NA.  STORE (one step length
+// only: phase_trial, the first trial of an iteration) also stores the trial residual rows B_DT, S_CT and sh.dft that a
+// second-order correction reads; the batched backtracking trials (phase_trial_multi) store nothing.
+template <bool RS_, int NA, bool STORE = false>
 __device__ __noinline__ void phase_trial_multi_t(const Ctx& c, LShared& sh, double mu, const double (&al)[NA], int buf,
                                                  double (&out)[NA][3]) {
     LArgs& a = *c.a;
     const int N = c.N;
     const bool plan = c.plan();
     constexpr bool rs = RS_;
+    static_assert(!STORE || NA == 1, "the trial residual rows are those of one step length");
     double th[NA], F[NA], logs[NA], bad[NA];
 #pragma unroll
     for (int q = 0; q < NA; ++q) { th[q] = 0.0; F[q] = 0.0; logs[q] = 0.0; bad[q] = 0.0; }
@@ -2293,7 +2121,10 @@ __device__ __noinline__ void phase_trial_multi_t(const Ctx& c, LShared& sh, doub
                     if (rs) { const double e = u[q][i] - ur[i]; prox[q] += dru[i] * e * e; }
                 }
         }
-        double ck[NA][6];
+        // dynamics residual c_{k+1} = x_{k+1} - F(x_k, u_k) (thread k), c_0 = x_0 - x_init; STORE: stored after the
+        // block loop (and each block's trial residual after the next block's loads): a store ahead of a load
+        // in the in-order vmcnt queue makes the load's wait include it
+        double ck[NA][6], cn[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll
         for (int q = 0; q < NA; ++q)
 #pragma unroll
@@ -2321,6 +2152,7 @@ __device__ __noinline__ void phase_trial_multi_t(const Ctx& c, LShared& sh, doub
                         const double n = NN[i] + al[q] * DNN[i];
                         cv -= p - n;
                     }
+                    if (STORE) cn[i] = cv;
                     th[q] += fabs(cv);
                 }
             }
@@ -2353,6 +2185,8 @@ __device__ __noinline__ void phase_trial_multi_t(const Ctx& c, LShared& sh, doub
         Trig tr[NA];
 #pragma unroll
         for (int q = 0; q < NA; ++q) tr[q] = stage_trig(x[q]);
+        double pdt[4] = {0, 0, 0, 0};
+        int pj = -1;
         for (int j = 0; j < c.nbk; ++j) {
             double W[8], DW[8], wr[8], drw[8], S[4], DS[4], PV[4], DPV[4], NV[4], DNV[4];
 #pragma unroll
@@ -2368,6 +2202,9 @@ __device__ __noinline__ void phase_trial_multi_t(const Ctx& c, LShared& sh, doub
                     NV[r] = c.B(B_NR + r, j, k); DNV[r] = c.B(B_DN + 4 * buf + r, j, k);
                 }
             }
+            if (STORE && pj >= 0)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) c.B(B_DT + r, pj, k) = pdt[r];
 #pragma unroll
             for (int q = 0; q < NA; ++q) {
                 double w[8], d[4];
@@ -2394,6 +2231,7 @@ __device__ __noinline__ void phase_trial_multi_t(const Ctx& c, LShared& sh, doub
                         Fr[q] += p + n;
                         res -= p - n;
                     }
+                    if (STORE) pdt[r] = res;
                     th[q] += fabs(res);
                     const double su = c.rU(r) - s;
                     ok[q] &= su > 0.0;
@@ -2401,6 +2239,18 @@ __device__ __noinline__ void phase_trial_multi_t(const Ctx& c, LShared& sh, doub
                     if (c.hrl(r)) { const double sl = s - c.rL(r); ok[q] &= sl > 0.0; ls[q].add(sl); }
                 }
             }
+            pj = j;
+        }
+        if (STORE) {
+            if (pj >= 0)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) c.B(B_DT + r, pj, k) = pdt[r];
+            if (k < N)
+#pragma unroll
+                for (int i = 0; i < 6; ++i) c.S(S_CT + i, k + 1) = cn[i];
+            if (k == 0)
+#pragma unroll
+                for (int i = 0; i < 6; ++i) c.S(S_CT + i, 0) = ck[0][i];
         }
         if (k == N && plan)
 #pragma unroll
@@ -2417,6 +2267,7 @@ __device__ __noinline__ void phase_trial_multi_t(const Ctx& c, LShared& sh, doub
                         Fr[q] += p + n;
                         res -= p - n;
                     }
+                    if (STORE) sh.dft[i] = res;
                     th[q] += fabs(res);
                     const double sl = s - c.fL, su = c.fU - s;
                     ok[q] &= sl > 0.0 && su > 0.0;
@@ -2449,67 +2300,76 @@ __device__ __noinline__ void phase_trial_multi_t(const Ctx& c, LShared& sh, doub
 #define OBCA_TRIAL_BATCH 4
 #endif
 constexpr int kTrialBatch = OBCA_TRIAL_BATCH;  // trials per batched pass (A/B builds: -DOBCA_TRIAL_BATCH=n)
+// one instantiation per problem (original / restoration phase): the original problem's skips every restoration
+// branch and its loads (bitwise the same results, profiles/r03/ab_one/)
+__device__ __forceinline__ void phase_trial(const Ctx& c, LShared& sh, double mu, double alpha, int buf, double (&out)[3]) {
+    const double al[1] = {alpha};
+    double o[1][3];
+    sh.R ? phase_trial_multi_t<true, 1, true>(c, sh, mu, al, buf, o)
+         : phase_trial_multi_t<false, 1, true>(c, sh, mu, al, buf, o);
+    out[0] = o[0][0]; out[1] = o[0][1]; out[2] = o[0][2];
+}
 __device__ __forceinline__ void phase_trial_multi(const Ctx& c, LShared& sh, double mu, const double (&al)[kTrialBatch],
                                                   int buf, double (&out)[kTrialBatch][3]) {
     sh.R ? phase_trial_multi_t<true, kTrialBatch>(c, sh, mu, al, buf, out)
          : phase_trial_multi_t<false, kTrialBatch>(c, sh, mu, al, buf, out);
 }
 
-// ======== phase: second-order-correction residual r <- a_soc r + r(trial) ========
-// (both residual phases load every value before the stores that would precede it in program order -- their
-// waits would include those stores, one in-order vmcnt queue -- so a block's results are stored after the
-// next block's loads)
-__device__ __noinline__ void phase_soc_resid(const Ctx& c, LShared& sh, double a_soc) {
-    const WsView vw = ws_view(c);
+// ======== the residual phases: rows S_CR, B_DR and sh.dfr from the formulas cr(i, k), dr(r, j, k), df(i) ========
+// (w: the phase's own view of the workspace.  Every value is loaded before the stores that would precede it in program
+// order -- their waits would include those stores, one in-order vmcnt queue -- so a block's results are stored after
+// the next block's loads)
+template <class Ws, class StageRow, class BlockRow, class FinalRow>
+__device__ __forceinline__ void resid_rows(const Ctx& c, LShared& sh, const Ws& w, StageRow crf, BlockRow drf,
+                                           FinalRow dff) {
     for (int k = (int)threadIdx.x; k <= c.N; k += T) {
         double cr[6];
 #pragma unroll
-        for (int i = 0; i < 6; ++i) cr[i] = a_soc * vw.S(S_CR + i, k) + vw.S(S_CT + i, k);
+        for (int i = 0; i < 6; ++i) cr[i] = crf(i, k);
         double dr[4], nx[4];
         auto blk = [&](int j, double* v) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = a_soc * vw.B(B_DR + r, j, k) + vw.B(B_DT + r, j, k);
+            for (int r = 0; r < 4; ++r) v[r] = drf(r, j, k);
         };
         if (c.nbk > 0) blk(0, dr);
 #pragma unroll
-        for (int i = 0; i < 6; ++i) vw.S(S_CR + i, k) = cr[i];
+        for (int i = 0; i < 6; ++i) w.S(S_CR + i, k) = cr[i];
         for (int j = 0; j < c.nbk; ++j) {
             if (j + 1 < c.nbk) blk(j + 1, nx);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) { vw.B(B_DR + r, j, k) = dr[r]; dr[r] = nx[r]; }
+            for (int r = 0; r < 4; ++r) { w.B(B_DR + r, j, k) = dr[r]; dr[r] = nx[r]; }
         }
         if (k == c.N && c.plan())
 #pragma unroll
-            for (int i = 0; i < 6; ++i) sh.dfr[i] = a_soc * sh.dfr[i] + sh.dft[i];
+            for (int i = 0; i < 6; ++i) sh.dfr[i] = dff(i);
     }
+}
+
+// ======== phase: second-order-correction residual r <- a_soc r + r(trial) ========
+__device__ __noinline__ void phase_soc_resid(const Ctx& c, LShared& sh, double a_soc) {
+    const WsView vw = ws_view(c);
+    resid_rows(c, sh, vw,
+               [&](int i, int k) __attribute__((always_inline)) { return a_soc * vw.S(S_CR + i, k) + vw.S(S_CT + i, k); },
+               [&](int r, int j, int k) __attribute__((always_inline)) {
+                   return a_soc * vw.B(B_DR + r, j, k) + vw.B(B_DT + r, j, k);
+               },
+               [&](int i) __attribute__((always_inline)) { return a_soc * sh.dfr[i] + sh.dft[i]; });
 }
 
 // ======== phase: residual rows of the Newton right-hand side at the iterate (zero: least squares) ========
 __device__ __noinline__ void phase_resid(const Ctx& c, LShared& sh, bool zero) {
     const bool rs = sh.R != 0;
-    for (int k = (int)threadIdx.x; k <= c.N; k += T) {
-        double cr[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i)
-            cr[i] = zero ? 0.0 : c.S(S_C + i, k) - (rs ? c.S(S_PR + i, k) - c.S(S_NR + i, k) : 0.0);
-        double dr[4], nx[4];
-        auto blk = [&](int j, double* v) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                v[r] = zero ? 0.0 : c.B(B_D + r, j, k) - c.B(B_S + r, j, k) - (rs ? c.B(B_PR + r, j, k) - c.B(B_NR + r, j, k) : 0.0);
-        };
-        if (c.nbk > 0) blk(0, dr);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) c.S(S_CR + i, k) = cr[i];
-        for (int j = 0; j < c.nbk; ++j) {
-            if (j + 1 < c.nbk) blk(j + 1, nx);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { c.B(B_DR + r, j, k) = dr[r]; dr[r] = nx[r]; }
-        }
-        if (k == c.N && c.plan())
-#pragma unroll
-            for (int i = 0; i < 6; ++i) sh.dfr[i] = zero ? 0.0 : sh.df[i] - sh.sf[i] - (rs ? sh.pf[i] - sh.nf[i] : 0.0);
-    }
+    resid_rows(c, sh, c,
+               [&](int i, int k) __attribute__((always_inline)) {
+                   return zero ? 0.0 : c.S(S_C + i, k) - (rs ? c.S(S_PR + i, k) - c.S(S_NR + i, k) : 0.0);
+               },
+               [&](int r, int j, int k) __attribute__((always_inline)) {
+                   return zero ? 0.0
+                               : c.B(B_D + r, j, k) - c.B(B_S + r, j, k) - (rs ? c.B(B_PR + r, j, k) - c.B(B_NR + r, j, k) : 0.0);
+               },
+               [&](int i) __attribute__((always_inline)) {
+                   return zero ? 0.0 : sh.df[i] - sh.sf[i] - (rs ? sh.pf[i] - sh.nf[i] : 0.0);
+               });
 }
 
 // inputs of one block's update (restoration pairs only when rs)
@@ -2548,35 +2408,25 @@ __device__ __forceinline__ void update_block(const Ctx& c, const WsView& vw, int
         const double w = cur.w[e], dv = cur.dw[e], z = cur.zw[e];
         const double sl = w + RELAX;
         wn[e] = w + alpha * dv;
-        double zn2 = z + az * (mu * inv(sl) - z - z * inv(sl) * dv);
-        clamp_mult(zn2, wn[e] + RELAX, mu);
-        zwn[e] = zn2;
+        zwn[e] = mult_step(z, sl, dv, wn[e] + RELAX, mu, az);
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const double sv = cur.s[r], dv = cur.ds[r];
         sn[r] = sv + alpha * dv;
         const double vu = cur.vu[r], slu = c.rU(r) - sv;
-        double vu2 = vu + az * (mu * inv(slu) - vu + vu * inv(slu) * dv);
-        clamp_mult(vu2, c.rU(r) - sn[r], mu);
-        vun[r] = vu2;
+        vun[r] = mult_step(vu, slu, -dv, c.rU(r) - sn[r], mu, az);
         if (c.hrl(r)) {
             const double vl = cur.vl[r], sll = sv - c.rL(r);
-            double vl2 = vl + az * (mu * inv(sll) - vl - vl * inv(sll) * dv);
-            clamp_mult(vl2, sn[r] - c.rL(r), mu);
-            vln[r] = vl2;
+            vln[r] = mult_step(vl, sll, dv, sn[r] - c.rL(r), mu, az);
         }
         ydn[r] = cur.yd[r] + alpha * (cur.yp[r] - cur.yd[r]);
         if (rs) {
             const double p = cur.pr[r], n = cur.nr[r], zpv = cur.zp[r], znv = cur.zn[r];
             prn[r] = p + alpha * cur.dp[r];
             nrn[r] = n + alpha * cur.dn[r];
-            double a1 = zpv + az * (mu * inv(p) - zpv - zpv * inv(p) * cur.dp[r]);
-            double a2 = znv + az * (mu * inv(n) - znv - znv * inv(n) * cur.dn[r]);
-            clamp_mult(a1, prn[r], mu);
-            clamp_mult(a2, nrn[r], mu);
-            zpn[r] = a1;
-            znn[r] = a2;
+            zpn[r] = mult_step(zpv, p, cur.dp[r], prn[r], mu, az);
+            znn[r] = mult_step(znv, n, cur.dn[r], nrn[r], mu, az);
         }
     }
 #pragma unroll
@@ -2634,24 +2484,18 @@ __device__ __noinline__ void phase_update_t(const Ctx& c, LShared& sh, double mu
             const double xn = xv + alpha * dv;
             if (c.hlx(i)) {
                 const double sl = xv - c.xl[i], z = zl[i];
-                double zn2 = z + az * (mu * inv(sl) - z - z * inv(sl) * dv);
-                clamp_mult(zn2, xn - c.xl[i], mu);
-                c.S(S_ZLX + i, k) = zn2;
+                c.S(S_ZLX + i, k) = mult_step(z, sl, dv, xn - c.xl[i], mu, az);
             }
             if (c.hux(i)) {
                 const double sl = c.xu[i] - xv, z = zu[i];
-                double zn2 = z + az * (mu * inv(sl) - z + z * inv(sl) * dv);
-                clamp_mult(zn2, c.xu[i] - xn, mu);
-                c.S(S_ZUX + i, k) = zn2;
+                c.S(S_ZUX + i, k) = mult_step(z, sl, -dv, c.xu[i] - xn, mu, az);
             }
             c.S(S_X + i, k) = xn;
             c.S(S_YC + i, k) = y[i] + alpha * (yp[i] - y[i]);
             if (rs) {
                 const double p = pr[i], n = nr[i], zpv = zp[i], znv = zn[i];
                 const double pn = p + alpha * dp[i], nn = n + alpha * dn[i];
-                double zpn = zpv + az * (mu * inv(p) - zpv - zpv * inv(p) * dp[i]), znn = znv + az * (mu * inv(n) - znv - znv * inv(n) * dn[i]);
-                clamp_mult(zpn, pn, mu);
-                clamp_mult(znn, nn, mu);
+                const double zpn = mult_step(zpv, p, dp[i], pn, mu, az), znn = mult_step(znv, n, dn[i], nn, mu, az);
                 c.S(S_PR + i, k) = pn;
                 c.S(S_NR + i, k) = nn;
                 c.S(S_ZP + i, k) = zpn;
@@ -2665,15 +2509,11 @@ __device__ __noinline__ void phase_update_t(const Ctx& c, LShared& sh, double mu
                 const double un = uv + alpha * dv;
                 if (c.hlu(i)) {
                     const double sl = uv - c.ul[i], z = zlu[i];
-                    double zn2 = z + az * (mu * inv(sl) - z - z * inv(sl) * dv);
-                    clamp_mult(zn2, un - c.ul[i], mu);
-                    c.S(S_ZLU + i, k) = zn2;
+                    c.S(S_ZLU + i, k) = mult_step(z, sl, dv, un - c.ul[i], mu, az);
                 }
                 if (c.huu(i)) {
                     const double sl = c.uu[i] - uv, z = zuu[i];
-                    double zn2 = z + az * (mu * inv(sl) - z + z * inv(sl) * dv);
-                    clamp_mult(zn2, c.uu[i] - un, mu);
-                    c.S(S_ZUU + i, k) = zn2;
+                    c.S(S_ZUU + i, k) = mult_step(z, sl, -dv, c.uu[i] - un, mu, az);
                 }
                 c.S(S_U + i, k) = un;
             }
@@ -2682,25 +2522,18 @@ __device__ __noinline__ void phase_update_t(const Ctx& c, LShared& sh, double mu
             for (int i = 0; i < 6; ++i) {
                 const double s = sh.sf[i], d = sh.dsf[buf][i], sn = s + alpha * d;
                 const double sl = s - c.fL, su = c.fU - s;
-                double vl = sh.vLf[i] + az * (mu * inv(sl) - sh.vLf[i] - sh.vLf[i] * inv(sl) * d);
-                double vu = sh.vUf[i] + az * (mu * inv(su) - sh.vUf[i] + sh.vUf[i] * inv(su) * d);
-                clamp_mult(vl, sn - c.fL, mu);
-                clamp_mult(vu, c.fU - sn, mu);
-                sh.vLf[i] = vl;
-                sh.vUf[i] = vu;
+                sh.vLf[i] = mult_step(sh.vLf[i], sl, d, sn - c.fL, mu, az);
+                sh.vUf[i] = mult_step(sh.vUf[i], su, -d, c.fU - sn, mu, az);
                 sh.sf[i] = sn;
                 sh.ydf[i] += alpha * (sh.ydpf[buf][i] - sh.ydf[i]);
                 if (rs) {
                     const double p = sh.pf[i], n = sh.nf[i], zp = sh.zpf[i], zn = sh.znf[i];
                     const double dp = sh.dpf[buf][i], dn = sh.dnf[buf][i];
                     const double pn = p + alpha * dp, nn = n + alpha * dn;
-                    double zpn = zp + az * (mu * inv(p) - zp - zp * inv(p) * dp), znn = zn + az * (mu * inv(n) - zn - zn * inv(n) * dn);
-                    clamp_mult(zpn, pn, mu);
-                    clamp_mult(znn, nn, mu);
                     sh.pf[i] = pn;
                     sh.nf[i] = nn;
-                    sh.zpf[i] = zpn;
-                    sh.znf[i] = znn;
+                    sh.zpf[i] = mult_step(zp, p, dp, pn, mu, az);
+                    sh.znf[i] = mult_step(zn, n, dn, nn, mu, az);
                 }
             }
     }
@@ -3130,7 +2963,7 @@ __device__ __noinline__ int newton_solve(const Ctx& c, LShared& sh, double mu, d
             __syncthreads();
             if (threadIdx.x < 64) riccati_soft(c, sh, SoftA{(const lds_double*)c.lds});
         } else if (threadIdx.x < 64) {
-            riccati_soft(c, sh, SoftG{c});
+            riccati_soft(c, sh, GSrc{c});
         }
         __syncthreads();
         stamp(sh, on, OPH_RIC_SOFT);
@@ -3140,7 +2973,7 @@ __device__ __noinline__ int newton_solve(const Ctx& c, LShared& sh, double mu, d
             __syncthreads();
             if (threadIdx.x < 64) forward_soft(c, SoftF{(const lds_double*)c.lds}, buf);
         } else if (threadIdx.x < 64) {
-            forward_soft(c, SoftFG{c}, buf);
+            forward_soft(c, GSrc{c}, buf);
         }
         __syncthreads();
         stamp(sh, on, OPH_FWD_SOFT);
@@ -3179,23 +3012,23 @@ __device__ __noinline__ int newton_solve(const Ctx& c, LShared& sh, double mu, d
 // Per stage k = N..1 (A = I + D, B = dt [e5 e4]):
 //   s = p_k - P_k c_k,  p' = s - P_k Y_k s  (= p~_k - P~_k c_k of the soft sweep; Y = 0 outside the restoration phase),
 //   g = r_{k-1} + B'p',  kf_{k-1} = -G^-1 g,  p_{k-1} = q_{k-1} + A'p' + K'g   (K'g = H' kf)
-// P_k c_k and P_k Y_k do not depend on the recursion: all four waves stage them per stage (record LV) before the
+// P_k c_k and P_k Y_k do not depend on the recursion: all four waves stage them per stage (record VecL) before the
 // sweep, so the serial chain is one 6x6 product (restoration only) plus the sparse A' and K' products, carried
 // redundantly by every lane; lanes 0..5 / lane 0 store p / kf for the forward sweep.
-constexpr int LV = 74;  // W = P c 6 | PY 36 | QV 6 | RV 2 | GI 3 | K 12 | AJ 9
+// record per stage: W = P c 6 | PY 36 | QV 6 | RV 2 | GI 3 | K 12 | AJ 9  (74)
 struct VecL {
+    enum : int { oW = 0, oPY = 6, oQV = 42, oRV = 48, oGI = 50, oK = 53, oAJ = 65, oEND = 74 };
     const lds_double* A;
-    __device__ double W(int i, int k) const { return A[k * LV + i]; }
-    __device__ double PY(int i, int j, int k) const { return A[k * LV + 6 + 6 * i + j]; }
-    __device__ double QV(int i, int k) const { return A[k * LV + 42 + i]; }
-    __device__ double RV(int i, int k) const { return A[k * LV + 48 + i]; }
-    __device__ double GI(int i, int k) const { return A[k * LV + 50 + i]; }
-    __device__ double K(int i, int k) const { return A[k * LV + 53 + i]; }
-    __device__ double AJ(int i, int k) const { return A[k * LV + 65 + i]; }
+    __device__ double W(int i, int k) const { return A[k * oEND + oW + i]; }
+    __device__ double PY(int i, int j, int k) const { return A[k * oEND + oPY + 6 * i + j]; }
+    __device__ double QV(int i, int k) const { return A[k * oEND + oQV + i]; }
+    __device__ double RV(int i, int k) const { return A[k * oEND + oRV + i]; }
+    __device__ double GI(int i, int k) const { return A[k * oEND + oGI + i]; }
+    __device__ double K(int i, int k) const { return A[k * oEND + oK + i]; }
+    __device__ double AJ(int i, int k) const { return A[k * oEND + oAJ + i]; }
 };
-// the same operands straight from the HBM workspace (horizons whose records do not fit the LDS budget)
-struct VecG {
-    const Ctx& c;
+// the same operands straight from the HBM workspace: GSrc's fields and the two products, formed on the read
+struct VecG : GSrc {
     __device__ double W(int i, int k) const {
         double t = 0.0;
 #pragma unroll
@@ -3208,17 +3041,12 @@ struct VecG {
         for (int l = 0; l < 6; ++l) t = fma((double)c.S(S_P + sy6(i, l), k), (double)c.S(S_Y + sy6(l, j), k), t);
         return t;
     }
-    __device__ double QV(int i, int k) const { return c.S(S_QV + i, k); }
-    __device__ double RV(int i, int k) const { return c.S(S_RV + i, k); }
-    __device__ double GI(int i, int k) const { return c.S(S_GI + i, k); }
-    __device__ double K(int i, int k) const { return c.S(S_K + i, k); }
-    __device__ double AJ(int i, int k) const { return c.S(S_AJ + i, k); }
 };
 template <bool SOFT>
 __device__ __noinline__ void stage_vec_inputs_t(const Ctx& c, double* A) {
     constexpr bool soft = SOFT;
     for (int k = (int)threadIdx.x; k <= c.N; k += T) {
-        lds_double* r = (lds_double*)A + (size_t)k * LV;
+        lds_double* r = (lds_double*)A + (size_t)k * VecL::oEND;
         double P[21], e[6];
 #pragma unroll
         for (int i = 0; i < 21; ++i) P[i] = c.S(S_P + i, k);
@@ -3243,7 +3071,7 @@ __device__ __noinline__ void stage_vec_inputs_t(const Ctx& c, double* A) {
             double t = 0.0;
 #pragma unroll
             for (int l = 0; l < 6; ++l) t = fma(P[sy6(i, l)], e[l], t);
-            r[i] = t;
+            r[VecL::oW + i] = t;
         }
 #pragma unroll
         for (int i = 0; i < 6; ++i)
@@ -3253,16 +3081,16 @@ __device__ __noinline__ void stage_vec_inputs_t(const Ctx& c, double* A) {
                 if (soft)
 #pragma unroll
                     for (int l = 0; l < 6; ++l) t = fma(P[sy6(i, l)], Y[sy6(l, j)], t);
-                r[6 + 6 * i + j] = t;
+                r[VecL::oPY + 6 * i + j] = t;
             }
 #pragma unroll
-        for (int i = 0; i < 6; ++i) r[42 + i] = q[i];
-        r[48] = rv[0]; r[49] = rv[1];
-        r[50] = gi[0]; r[51] = gi[1]; r[52] = gi[2];
+        for (int i = 0; i < 6; ++i) r[VecL::oQV + i] = q[i];
+        r[VecL::oRV] = rv[0]; r[VecL::oRV + 1] = rv[1];
+        r[VecL::oGI] = gi[0]; r[VecL::oGI + 1] = gi[1]; r[VecL::oGI + 2] = gi[2];
 #pragma unroll
-        for (int i = 0; i < 12; ++i) r[53 + i] = kk[i];
+        for (int i = 0; i < 12; ++i) r[VecL::oK + i] = kk[i];
 #pragma unroll
-        for (int i = 0; i < 9; ++i) r[65 + i] = aj[i];
+        for (int i = 0; i < 9; ++i) r[VecL::oAJ + i] = aj[i];
     }
 }
 __device__ __forceinline__ void stage_vec_inputs(const Ctx& c, double* A, bool soft) {
@@ -3384,7 +3212,7 @@ __device__ __forceinline__ void nres_block(const Ctx& c, const LShared& sh, cons
     double cb[CB_END] = {};
     auto R = [&](double v) { rmax = fmax(rmax, fabs(v)); return v; };
     auto Bc = [&](double v) { bmax = fmax(bmax, fabs(v)); return v; };
-    auto dual = [&](double z, double dz) { if (dz < 0.0) az = fmin(az, -tau * z * inv(dz)); };
+    auto dual = [&](double z, double dz) { ftb_dual_rcp(z, dz, tau, az); };
     BlkIn in;
     load_blk_in(c, rs, j, k, in);
     const double *w = in.w, *zw = in.zw, *sv = in.s, *vl = in.vl, *vu = in.vu, *dres = in.dr;
@@ -3481,7 +3309,7 @@ __device__ __forceinline__ void nres_block(const Ctx& c, const LShared& sh, cons
         rel = fmax(rel, fabs(d) * inv(1.0 + fabs(w[e])));
         snorm = fmax(snorm, fabs(d));
         ftb_lo(w[e], -RELAX, d, tau, ap);
-        dual(zw[e], mu * isl - zw[e] - zw[e] * isl * d);
+        dual(zw[e], dz_rcp(zw[e], isl, d, mu));
     }
     // slack, row and elastic-pair rows
     double rsl[4], rdv[4], rpv[4] = {0, 0, 0, 0}, rnv[4] = {0, 0, 0, 0}, Dpv[4] = {1, 1, 1, 1}, Dnv[4] = {1, 1, 1, 1};
@@ -3509,8 +3337,8 @@ __device__ __forceinline__ void nres_block(const Ctx& c, const LShared& sh, cons
             rnv[r] = R(Bc(gn) + Dnv[r] * dn + ydp[r]);
             ftb_lo(p, 0.0, dp, tau, ap);
             ftb_lo(n, 0.0, dn, tau, ap);
-            dual(zp, mu * ip - zp - zp * ip * dp);
-            dual(zn, mu * in_ - zn - zn * in_ * dn);
+            dual(zp, dz_rcp(zp, ip, dp, mu));
+            dual(zn, dz_rcp(zn, in_, dn, mu));
             Dmb += gp * dp + gn * dn;
             rel = fmax(rel, fmax(fabs(dp) * inv(1.0 + fabs(p)), fabs(dn) * inv(1.0 + fabs(n))));
         }
@@ -3519,10 +3347,10 @@ __device__ __forceinline__ void nres_block(const Ctx& c, const LShared& sh, cons
         Dmb += gs * d;
         rel = fmax(rel, fabs(d) * inv(1.0 + fabs(s)));
         ftb_hi(s, c.rU(r), d, tau, ap);
-        dual(vu[r], mu * iu - vu[r] + vu[r] * iu * d);
+        dual(vu[r], dz_rcp(vu[r], iu, -d, mu));
         if (c.hrl(r)) {
             ftb_lo(s, c.rL(r), d, tau, ap);
-            dual(vl[r], mu * il - vl[r] - vl[r] * il * d);
+            dual(vl[r], dz_rcp(vl[r], il, d, mu));
         }
     }
     if (prep) {  // bk holds the elimination (block_refactor above)
@@ -3550,7 +3378,9 @@ __device__ __forceinline__ void nres_block(const Ctx& c, const LShared& sh, cons
 // chunks [c0, c1) of a block pass: thread t runs block f = ci T + t of the flat block index (one function per pass, so
 // that neither block part's registers constrain the other's).  The helpers' write-through instances (SC1) are inlined
 // into the helper path of the kernel entry, which saves no registers: as calls, every chunk paid the callee-saved
-// register saves and restores of a ~270-register frame.
+// register saves and restores of a ~270-register frame.  The loop is written out in each body: behind one shared loop
+// template taking the block as a functor, the kernel entry spilled 241 VGPRs instead of 236
+// (profiles/r21_obca_one_copy/README.md).
 template <bool SC1>
 __device__ __forceinline__ void nres_chunks_body(const Ctx& c, const LShared& sh, ChunkPass p, int c0, int c1) {
     const WsView vw = ws_view(c);
@@ -3595,8 +3425,7 @@ __device__ __noinline__ void update_chunks(const Ctx& c, ChunkPass p, int c0, in
     update_chunks_body<RS_, false>(c, p, c0, c1);
 }
 // the instance's own chunks (plain stores, calls)
-__device__ void do_chunks(const Ctx& c, const LShared& sh, ChunkPass p, int c0, int c1, bool helper) {
-    (void)helper;
+__device__ void do_chunks(const Ctx& c, const LShared& sh, ChunkPass p, int c0, int c1) {
     if (p.pass == PASS_NRES) nres_chunks(c, sh, p, c0, c1);
     else if (p.pass == PASS_FACTOR) factor_chunks(c, sh, p, c0, c1);
     else if (sh.R) update_chunks<true>(c, p, c0, c1);
@@ -3709,13 +3538,8 @@ __device__ __forceinline__ void helper_main(LArgs& a, Ctx& cw, LShared& sh) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         // the done count publishes the chunk: a release add (advisor r5), so the instance's acquire synchronizes with
-        // it under the HIP memory model and not only by the sc1 + vmcnt(0) drain above (OBCA_HELPER_RELEASE 0: relaxed)
-        if (lane == 0) {
-            if constexpr (OBCA_HELPER_RELEASE)
-                __hip_atomic_fetch_add(board_line(a, b) + 1, 1ull, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-            else
-                add_rlx(board_line(a, b) + 1, 1);
-        }
+        // it under the HIP memory model and not only by the sc1 + vmcnt(0) drain above
+        if (lane == 0) __hip_atomic_fetch_add(board_line(a, b) + 1, 1ull, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -3729,7 +3553,7 @@ __device__ __noinline__ void phase_nres(const Ctx& c, LShared& sh, double mu, do
     double rmax = 0.0, bmax = 0.0, snorm = 0.0, ap = 1.0, az = 1.0, Dm = 0.0, rel = 0.0;
     auto R = [&](double v) { rmax = fmax(rmax, fabs(v)); return v; };
     auto Bc = [&](double v) { bmax = fmax(bmax, fabs(v)); return v; };
-    auto dual = [&](double z, double dz) { if (dz < 0.0) az = fmin(az, -tau * z * inv(dz)); };
+    auto dual = [&](double z, double dz) { ftb_dual_rcp(z, dz, tau, az); };
     // the block part over the flat block index (all threads busy: 2M (N + 1) blocks in ceil(2M (N + 1) / T) rounds), by
     // this workgroup and any helpers
     run_pass(c, sh, ChunkPass{mu, dw, tau, PASS_NRES, buf, prep ? 1 : 0, mode});
@@ -3767,14 +3591,14 @@ __device__ __noinline__ void phase_nres(const Ctx& c, LShared& sh, double mu, do
                 g -= mu * is;
                 sg += z * is;
                 ftb_lo(xv, c.xl[i], d, tau, ap);
-                dual(z, mu * is - z - z * is * d);
+                dual(z, dz_rcp(z, is, d, mu));
             }
             if (c.hux(i)) {
                 const double is = inv(c.xu[i] - xv), z = vw.S(S_ZUX + i, k);
                 g += mu * is;
                 sg += z * is;
                 ftb_hi(xv, c.xu[i], d, tau, ap);
-                dual(z, mu * is - z + z * is * d);
+                dual(z, dz_rcp(z, is, -d, mu));
             }
             Dm += g * d;
             double t = Bc(g) + sg * d + yp[i] - ypn[i];
@@ -3829,14 +3653,14 @@ __device__ __noinline__ void phase_nres(const Ctx& c, LShared& sh, double mu, do
                     g -= mu * is;
                     sg += z * is;
                     ftb_lo(uv, c.ul[i], d, tau, ap);
-                    dual(z, mu * is - z - z * is * d);
+                    dual(z, dz_rcp(z, is, d, mu));
                 }
                 if (c.huu(i)) {
                     const double is = inv(c.uu[i] - uv), z = vw.S(S_ZUU + i, k);
                     g += mu * is;
                     sg += z * is;
                     ftb_hi(uv, c.uu[i], d, tau, ap);
-                    dual(z, mu * is - z + z * is * d);
+                    dual(z, dz_rcp(z, is, -d, mu));
                 }
                 Dm += g * d;
                 double t = Bc(g) + sg * d - dt * (i == 0 ? yn5 : yn4);
@@ -3889,8 +3713,8 @@ __device__ __noinline__ void phase_nres(const Ctx& c, LShared& sh, double mu, do
                 gpnc[i] = rpc[i] / Dp - rnc[i] / Dn;
                 ftb_lo(p, 0.0, dp, tau, ap);
                 ftb_lo(n, 0.0, dn, tau, ap);
-                dual(zp, mu * ip - zp - zp * ip * dp);
-                dual(zn, mu * in_ - zn - zn * in_ * dn);
+                dual(zp, dz_rcp(zp, ip, dp, mu));
+                dual(zn, dz_rcp(zn, in_, dn, mu));
                 Dm += gp * dp + gn * dn;
                 rel = fmax(rel, fmax(fabs(dp) * inv(1.0 + fabs(p)), fabs(dn) * inv(1.0 + fabs(n))));
             }
@@ -3931,8 +3755,8 @@ __device__ __noinline__ void phase_nres(const Ctx& c, LShared& sh, double mu, do
                     if (prep) { sh.opf[i] = rp; sh.onf[i] = rn; }
                     ftb_lo(p, 0.0, dp, tau, ap);
                     ftb_lo(n, 0.0, dn, tau, ap);
-                    dual(zp, mu / p - zp - zp / p * dp);
-                    dual(zn, mu / n - zn - zn / n * dn);
+                    dual(zp, dz_quot(zp, p, dp, mu));  // the final rows divide in dz (as the oracle does here)
+                    dual(zn, dz_quot(zn, n, dn, mu));
                     Dm += gp * dp + gn * dn;
                     rel = fmax(rel, fmax(fabs(dp) * inv(1.0 + fabs(p)), fabs(dn) * inv(1.0 + fabs(n))));
                 }
@@ -3942,8 +3766,8 @@ __device__ __noinline__ void phase_nres(const Ctx& c, LShared& sh, double mu, do
                 rel = fmax(rel, fabs(d) * inv(1.0 + fabs(s)));
                 ftb_lo(s, c.fL, d, tau, ap);
                 ftb_hi(s, c.fU, d, tau, ap);
-                dual(sh.vLf[i], mu / sl - sh.vLf[i] - sh.vLf[i] / sl * d);
-                dual(sh.vUf[i], mu / su - sh.vUf[i] + sh.vUf[i] / su * d);
+                dual(sh.vLf[i], dz_quot(sh.vLf[i], sl, d, mu));
+                dual(sh.vUf[i], dz_quot(sh.vUf[i], su, -d, mu));
                 if (prep) {
                     const double rfp = rf + rsf / sh.Dsf[i] + gpn;
                     sh.rf[i] = rfp;
@@ -4035,11 +3859,11 @@ __device__ __noinline__ void correction_solve(const Ctx& c, LShared& sh, double 
             else forward(c, SoftF{(const lds_double*)c.lds}, 2);
         }
     } else {
-        if (threadIdx.x < 64) riccati_vec(c, VecG{c}, soft);
+        if (threadIdx.x < 64) riccati_vec(c, VecG{{c}}, soft);
         __syncthreads();
         if (threadIdx.x < 64) {
-            if (soft) forward_soft(c, SoftFG{c}, 2);
-            else forward(c, SoftFG{c}, 2);
+            if (soft) forward_soft(c, GSrc{c}, 2);
+            else forward(c, GSrc{c}, 2);
         }
     }
     __syncthreads();
@@ -4254,13 +4078,13 @@ __device__ __noinline__ void phase_enter_resto(const Ctx& c, LShared& sh, double
 __device__ __noinline__ void phase_leave_resto(const Ctx& c, LShared& sh, double mu, double tau) {
     const int N = c.N;
     double red[1] = {1.0};
-    // dz of a lower-bound multiplier z0 whose slack moved from sl0 by d
-    auto dzl = [&](double z0, double sl0, double d) { return mu / sl0 - z0 - z0 / sl0 * d; };
+    // dz of a bound multiplier z0 whose slack moved from sl0 by d (quotient form)
+    auto dzl = [&](double z0, double sl0, double d) { return dz_quot(z0, sl0, d, mu); };
     for (int pass = 0; pass < 2; ++pass) {
         double acc = pass == 0 ? 1.0 : 0.0;  // pass 0: fraction to the boundary; pass 1: max multiplier
         const double al = red[0];
         auto use = [&](double z0, double dz, gdouble& z, double slnew) {
-            if (pass == 0) { if (dz < 0.0) acc = fmin(acc, -tau * z0 / dz); }
+            if (pass == 0) ftb_dual_quot(z0, dz, tau, acc);
             else { double zn = z0 + al * dz; clamp_mult(zn, slnew, mu); z = zn; acc = fmax(acc, zn); }
         };
         for (int k = (int)threadIdx.x; k <= N; k += T) {
@@ -4297,8 +4121,8 @@ __device__ __noinline__ void phase_leave_resto(const Ctx& c, LShared& sh, double
                     const double s = sh.sf[i], sr = sh.sfR[i], d = s - sr;
                     const double dl = dzl(sh.svLf[i], sr - c.fL, d), du = dzl(sh.svUf[i], c.fU - sr, -d);
                     if (pass == 0) {
-                        if (dl < 0.0) acc = fmin(acc, -tau * sh.svLf[i] / dl);
-                        if (du < 0.0) acc = fmin(acc, -tau * sh.svUf[i] / du);
+                        ftb_dual_quot(sh.svLf[i], dl, tau, acc);
+                        ftb_dual_quot(sh.svUf[i], du, tau, acc);
                     } else {
                         double vl = sh.svLf[i] + al * dl, vu = sh.svUf[i] + al * du;
                         clamp_mult(vl, s - c.fL, mu);

@@ -271,8 +271,8 @@ def test_obca_lockstep_with_oracle():
 
 def test_hbm_source_sweeps_lockstep():
     """N = 230: the serial sweeps' stage records no longer fit the dynamic LDS (kObcaLdsMax), so the Riccati, forward,
-    soft and correction sweeps read their operands straight from the HBM workspace (the GSrc / SoftG / VecG / SoftFG
-    sources) -- a path no other test reaches.  Lockstep with the oracle at max_iter 25, as the census above."""
+    soft and correction sweeps read their operands straight from the HBM workspace (the one HBM source GSrc, and VecG
+    on top of it) -- a path no other test reaches.  Lockstep with the oracle at max_iter 25, as the census above."""
     from oracle import c_oracle as co
     from ttmpc import scenarios as sc
     import json
