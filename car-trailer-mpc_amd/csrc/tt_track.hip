@@ -296,9 +296,11 @@ struct Stamps {
 #define SUBSTAMP(c, n) ((void)0)
 #endif
 
-// Armijo test with IPOPT's round-off allowance (Compare_le: lhs - rhs <= 10 eps |reference|)
+// IPOPT's round-off allowance of a comparison (Compare_le: lhs - rhs <= 10 eps |reference|)
+constexpr double kRoundOff = 10.0 * 2.220446049250313e-16;
+// Armijo test with that allowance
 __device__ __forceinline__ bool armijo(double trial, double ref, double alpha, double D) {
-    return trial - (ref + 1e-4 * alpha * D) <= 10.0 * 2.220446049250313e-16 * fabs(ref);
+    return trial - (ref + 1e-4 * alpha * D) <= kRoundOff * fabs(ref);
 }
 
 // IPOPT filter constants (gamma_theta, gamma_phi, s_phi, s_theta; delta = 1, eta_phi = 1e-4)
@@ -307,6 +309,34 @@ constexpr double kGTh = 1e-5, kGPh = 1e-8, kSPh = 2.3, kSTh = 1.1;
 // fraction-to-boundary: largest a with s + a*d >= (1-tau) s  (divide only when the bound is active)
 __device__ __forceinline__ void ftb(double s, double d, double tau, double& a) {
     if (d < 0.0 && tau * s < -a * d) a = -tau * s / d;
+}
+
+// ---- the algebra of one bound row (z its multiplier, s its slack, rs = frcp(s): this file multiplies by the reciprocal
+// and never divides), stated once for every stage-parallel pass ----
+// barrier term of a slack: outside the relaxed box the point is rejected, inside it log s joins the stage's sum
+__device__ __forceinline__ void slack_log(double s, bool& bad, LogSum& ls) {
+    if (s <= 0.0) bad = true; else ls.add(s);
+}
+// a bound's share of the linearisation: the Lagrangian gradient g (-z_L, +z_U), the extremes of z s (complementarity),
+// sum z, Sigma += z / s, dB (-1/s_L, +1/s_U) and the barrier term
+template <bool UP>
+__device__ __forceinline__ void bound_row(double z, double s, double rs, double& g, double& zmx, double& zmn, double& sz,
+                                          double& sg, double& db, bool& bad, LogSum& ls) {
+    if (UP) g += z; else g -= z;
+    zmx = fmax(zmx, z * s);
+    zmn = fmin(zmn, z * s);
+    sz += z;
+    sg += z * rs;
+    if (UP) db += rs; else db -= rs;
+    slack_log(s, bad, ls);
+}
+// Newton step of a bound multiplier, (mu - z d) / s - z, with d the step of the slack: a lower bound passes the step of
+// its variable, an upper bound its negative (negation is exact, so mu - z_U (-d) is the mu + z_U d of the formula)
+__device__ __forceinline__ double dz_bound(double z, double d, double rs, double mu) { return (mu - z * d) * rs - z; }
+// the accepted multiplier z + az dz under IPOPT's kappa_sigma clamp around rn = mu / s_new
+constexpr double kKappaSigma = 1e10, kKappaSigmaInv = 1e-10;
+__device__ __forceinline__ double mult_step(double z, double az, double dz, double rn) {
+    return fmax(fmin(z + az * dz, kKappaSigma * rn), kKappaSigmaInv * rn);
 }
 
 // Per-wave solver context: a handful of scalars; the data lives in LDS
@@ -342,6 +372,9 @@ struct Ctx {
     // bit 17: the two-waves-per-SIMD build.  The one-wave builds issue every LDS read of a stage-parallel pass before its
     // stores (kLF, "loads first": with one wave per SIMD nothing hides a read queued behind a store); the two-wave build
     // keeps the per-variable order, whose shorter live ranges suit its 256-register budget.  Same arithmetic either way.
+    // Two waves => lane pairs: launch_track sets the bit (kOccBit) only with NS = 20 and NS = 30, where `pair` below is
+    // always true, and the !kLF arm of phase_linearize is written for lane pairs alone.  A two-wave build at N >= 32
+    // needs its one-stage-per-lane form first (track_kernel asserts the pairing).
     static constexpr bool kLF = !(BM >= 0 && ((BM >> 17) & 1));
     __device__ __forceinline__ bool hl(int v) const {
         if constexpr (BM >= 0) return (BM >> v) & 1;
@@ -386,6 +419,22 @@ struct Ctx {
     struct Stamps* st;  // diagnostic build: sub-phase clocks (SUBSTAMP)
 #endif
 };
+
+// The operands of a bound row of slot t (variable v of stage k, at xv), a compile-time choice of the stage-parallel
+// passes: the carried state (CR), or the multiplier row, the slack formed from the point and frcp of it.  The carried
+// values are those expressions on those operands (struct Carry), so both sources give the same bits.
+struct BoundOps {
+    double z, s, rs;
+};
+template <bool CR, bool UP, int BM>
+__device__ __forceinline__ BoundOps bound_ops(const Ctx<BM>& c, const Carry& cy, int t, int v, int k, double xv) {
+    if constexpr (CR) {
+        return UP ? BoundOps{cy.zu[t], cy.su[t], cy.ru[t]} : BoundOps{cy.zl[t], cy.sl[t], cy.rl[t]};
+    } else {
+        const double s = UP ? c.ub(v) - xv : xv - c.lb(v);
+        return {c.r((UP ? rZU : rZL) + v, k), s, frcp(s)};
+    }
+}
 
 // sin / cos of theta, psi, phi of a stage.  Lane pairs: the two lanes evaluate theta (part 0) and phi
 // (part 1) in the same instruction stream and swap the results with one DPP quad_perm [1,0,3,2], so the
@@ -555,26 +604,9 @@ __device__ __forceinline__ Lin phase_linearize(const Ctx<BM>& c, Carry& cy) {
                 }
                 gfv[t] = gf;
                 double sg = 0.0, db = 0.0;
-                if (c.hl(vb)) {
-                    const double zl = cy.zl[t], sl = cy.sl[t], rs = cy.rl[t];  // sl = xv - lb, rs = frcp(sl)
-                    g -= zl;
-                    zmx = fmax(zmx, zl * sl);
-                    zmn = fmin(zmn, zl * sl);
-                    sz += zl;
-                    sg += zl * rs;
-                    db -= rs;
-                    if (sl <= 0.0) bad = true; else ls.add(sl);
-                }
-                if (c.hu(vb)) {
-                    const double zu = cy.zu[t], su = cy.su[t], rs = cy.ru[t];  // su = ub - xv, rs = frcp(su)
-                    g += zu;
-                    zmx = fmax(zmx, zu * su);
-                    zmn = fmin(zmn, zu * su);
-                    sz += zu;
-                    sg += zu * rs;
-                    db += rs;
-                    if (su <= 0.0) bad = true; else ls.add(su);
-                }
+                // carried: sl = xv - lb, su = ub - xv and their frcp
+                if (c.hl(vb)) bound_row<false>(cy.zl[t], cy.sl[t], cy.rl[t], g, zmx, zmn, sz, sg, db, bad, ls);
+                if (c.hu(vb)) bound_row<true>(cy.zu[t], cy.su[t], cy.ru[t], g, zmx, zmn, sz, sg, db, bad, ls);
                 sgv[t] = sg;
                 dbv[t] = db;
                 if (!isfinite(g)) fin = false;
@@ -692,25 +724,13 @@ __device__ __forceinline__ Lin phase_linearize(const Ctx<BM>& c, Carry& cy) {
                 double zl, s, rs;
                 if constexpr (CR) { zl = cy.zl[v]; s = cy.sl[v]; rs = cy.rl[v]; }
                 else { zl = c.r(rZL + v, k); s = xv - c.lb(v); rs = frcp(s); }
-                g -= zl;
-                zmx = fmax(zmx, zl * s);
-                zmn = fmin(zmn, zl * s);
-                sz += zl;
-                sg += zl * rs;
-                db -= rs;
-                if (s <= 0.0) bad = true; else ls.add(s);
+                bound_row<false>(zl, s, rs, g, zmx, zmn, sz, sg, db, bad, ls);
             }
             if (c.hu(v)) {
                 double zu, s, rs;
                 if constexpr (CR) { zu = cy.zu[v]; s = cy.su[v]; rs = cy.ru[v]; }
                 else { zu = c.r(rZU + v, k); s = c.ub(v) - xv; rs = frcp(s); }
-                g += zu;
-                zmx = fmax(zmx, zu * s);
-                zmn = fmin(zmn, zu * s);
-                sz += zu;
-                sg += zu * rs;
-                db += rs;
-                if (s <= 0.0) bad = true; else ls.add(s);
+                bound_row<true>(zu, s, rs, g, zmx, zmn, sz, sg, db, bad, ls);
             }
             sgv[v] = sg;
             dbv[v] = db;
@@ -750,7 +770,8 @@ __device__ __forceinline__ Lin phase_linearize(const Ctx<BM>& c, Carry& cy) {
     }
     } else {
     // the two-wave build: the other wave on the SIMD hides the LDS round trips, and the load-first order's
-    // longer live ranges cost it more than they save (C5, profiles/r05/track_ab/)
+    // longer live ranges cost it more than they save (C5, profiles/r05/track_ab/).  It always runs lane pairs (see
+    // Ctx::kLF), so this arm has no one-stage-per-lane form.
     if (c.pair) {
         // lane pairs: both lanes linearise the dynamics (the curvature and dt*J feed both lanes' gradient
         // rows), each writes and accounts for its own rows (2q + part) and its own variables (2t + part)
@@ -823,23 +844,11 @@ __device__ __forceinline__ Lin phase_linearize(const Ctx<BM>& c, Carry& cy) {
                 double sg = 0.0, db = 0.0;
                 if (c.hl(vb)) {
                     const double zl = c.r(rZL + v, k), sl = xv - c.lb(v), rs = frcp(sl);
-                    g -= zl;
-                    zmx = fmax(zmx, zl * sl);
-                    zmn = fmin(zmn, zl * sl);
-                    sz += zl;
-                    sg += zl * rs;
-                    db -= rs;
-                    if (sl <= 0.0) bad = true; else ls.add(sl);
+                    bound_row<false>(zl, sl, rs, g, zmx, zmn, sz, sg, db, bad, ls);
                 }
                 if (c.hu(vb)) {
                     const double zu = c.r(rZU + v, k), su = c.ub(v) - xv, rs = frcp(su);
-                    g += zu;
-                    zmx = fmax(zmx, zu * su);
-                    zmn = fmin(zmn, zu * su);
-                    sz += zu;
-                    sg += zu * rs;
-                    db += rs;
-                    if (su <= 0.0) bad = true; else ls.add(su);
+                    bound_row<true>(zu, su, rs, g, zmx, zmn, sz, sg, db, bad, ls);
                 }
                 c.g(rSG + v, k) = sg;
                 c.g(rDB + v, k) = db;
@@ -848,106 +857,6 @@ __device__ __forceinline__ Lin phase_linearize(const Ctx<BM>& c, Carry& cy) {
             }
             logs += ls.value();
         }
-    } else
-    for (int k = c.lane; k <= N; k += W) {
-        double x[6], u[2] = {0.0, 0.0}, yk[6], y1[6] = {0, 0, 0, 0, 0, 0}, aj[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int i = 0; i < 6; ++i) { x[i] = c.r(rX + i, k); yk[i] = c.r(rY + i, k); sy += fabs(yk[i]); }
-        if (k == 0) {
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                const double cc = x[i] - c.h(hXI + i);
-                c.r(rCC + i, 0) = cc;
-                pinf = fmax(pinf, fabs(cc));
-                th += fabs(cc);
-            }
-        }
-        if (k < N) {
-            double fo[6], wc[7];
-            u[0] = c.r(rX + 6, k);
-            u[1] = c.r(rX + 7, k);
-#pragma unroll
-            for (int i = 0; i < 6; ++i) y1[i] = c.r(rY + i, k + 1);
-            model_lin(c, x, u, y1, fo, aj, wc);
-#pragma unroll
-            for (int i = 0; i < 9; ++i) c.r(rAJ + i, k) = aj[i];
-#pragma unroll
-            for (int i = 0; i < 7; ++i) c.r(rWC + i, k) = wc[i];
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                const double cc = c.r(rX + i, k + 1) - (x[i] + c.dt * fo[i]);
-                c.r(rCC + i, k + 1) = cc;
-                pinf = fmax(pinf, fabs(cc));
-                th += fabs(cc);
-            }
-        }
-        // tracking cost and its gradient (no 1/2: F = dx' Qw dx + du' Rw du, grad = 2 Qw dx)
-        double dxr[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) dxr[i] = x[i] - c.xr(i, k);
-        double du0 = 0.0, du1 = 0.0;
-        if (k < N) { du0 = u[0] - c.ur(0, k); du1 = u[1] - c.ur(1, k); }
-        LogSum ls;
-#pragma unroll
-        for (int v = 0; v < 8; ++v) {
-            if (v >= 6 && k == N) break;
-            double gf;
-            if (v < 6) {
-                if constexpr (Ctx<BM>::kDiag) {
-                    gf = c.h(hQW + v * 7) * dxr[v];
-                } else {
-                    gf = 0.0;
-#pragma unroll
-                    for (int j = 0; j < 6; ++j) gf += c.h(hQW + v * 6 + j) * dxr[j];
-                }
-                cost += dxr[v] * gf;
-                gf *= 2.0;
-            } else {
-                const int rr = v - 6;
-                if constexpr (Ctx<BM>::kDiag)
-                    gf = c.h(hRW + rr * 3) * (rr == 0 ? du0 : du1);
-                else
-                    gf = c.h(hRW + rr * 2) * du0 + c.h(hRW + rr * 2 + 1) * du1;
-                cost += (rr == 0 ? du0 : du1) * gf;
-                gf *= 2.0;
-            }
-            c.r(rGF + v, k) = gf;
-            // d/dz of the Lagrangian: grad F + y_k - A'y_{k+1} - zL + zU
-            double g = gf;
-            if (v < 6) {
-                g += yk[v];
-                if (k < N) g -= y1[v] + colJ(aj, v, y1, 1);
-            } else {
-                g -= c.dt * y1[v == 6 ? 5 : 4];
-            }
-            const double xv = v < 6 ? x[v] : u[v - 6];
-            double sg = 0.0, db = 0.0;
-            if (c.hl(v)) {
-                const double zl = c.r(rZL + v, k), s = xv - c.lb(v), rs = frcp(s);
-                g -= zl;
-                zmx = fmax(zmx, zl * s);
-                zmn = fmin(zmn, zl * s);
-                sz += zl;
-                sg += zl * rs;
-                db -= rs;
-                if (s <= 0.0) bad = true; else ls.add(s);
-            }
-            if (c.hu(v)) {
-                const double zu = c.r(rZU + v, k), s = c.ub(v) - xv, rs = frcp(s);
-                g += zu;
-                zmx = fmax(zmx, zu * s);
-                zmn = fmin(zmn, zu * s);
-                sz += zu;
-                sg += zu * rs;
-                db += rs;
-                if (s <= 0.0) bad = true; else ls.add(s);
-            }
-            c.g(rSG + v, k) = sg;
-            c.g(rDB + v, k) = db;
-            if (!isfinite(g)) fin = false;
-            dinf = fmax(dinf, fabs(g));
-        }
-        logs += ls.value();
     }
     }
     Lin e;
@@ -1025,53 +934,64 @@ __device__ __forceinline__ void ric_gu_shift(const Ctx<BM>& c, double dw) {
     __syncthreads();
 }
 
-// stage-parallel: fold the barrier, curvature and constraint terms into the Riccati operand rows
+// The Riccati operand rows of stage k: the barrier, curvature and constraint terms folded into grad F + mu dB,
+// diag(Sigma) + diag(W), Sigma_u, b^ = -c_{k+1} and the shifted input gradient.  One text for both sources of grad F, dB,
+// Sigma, the curvature diagonal and c_{k+1}: the rows (cy == nullptr; every source row is read before the first overlay
+// write), or the carried values, each made opaque first (opq) so that the rows' values are the ones formed from the
+// stored operands.
+template <bool CARRIED, int BM>
+__device__ __forceinline__ void ric_operands(const Ctx<BM>& c, int k, const Carry* cy) {
+    const bool st = k < c.N;
+    double g[8], hd[6];
+#pragma unroll
+    for (int v = 0; v < 8; ++v)
+        g[v] = (v >= 6 && !st) ? 0.0
+             : CARRIED ? opq(cy->gf[v]) + c.mu * opq(cy->db[v]) : c.r(rGF + v, k) + c.mu * (double)c.g(rDB + v, k);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        const int wi = w_idx(i, i);
+        double d = CARRIED ? opq(cy->sg[i]) : (double)c.g(rSG + i, k);
+        if (wi >= 0 && st) d += CARRIED ? opq(cy->wd[i]) : c.r(rWC + wi, k);
+        hd[i] = d;
+    }
+    const double su0 = !st ? 0.0 : CARRIED ? opq(cy->sg[6]) : (double)c.g(rSG + 6, k);
+    const double su1 = !st ? 0.0 : CARRIED ? opq(cy->sg[7]) : (double)c.g(rSG + 7, k);
+#pragma unroll
+    for (int v = 0; v < 8; ++v) {
+        if (v >= 6 && !st) break;
+        c.r(rGF + v, k) = g[v];
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) c.r(rHD + i, k) = hd[i];
+    c.r(rSGU, k) = su0;
+    c.r(rSGU + 1, k) = su1;
+    if (st) {
+        double cn[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) cn[i] = CARRIED ? opq(cy->cn[i]) : c.r(rCC + i, k + 1);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) c.r(rBH + i, k) = -cn[i];
+        double g0, g1;
+        gu_shift(c, g[6], g[7], su0, su1, cn[4], cn[5], 0.0, g0, g1);
+        c.r(rGU, k) = g0;
+        c.r(rGU + 1, k) = g1;
+    } else {  // terminal stage: no dynamics, so no curvature
+#pragma unroll
+        for (int i = 0; i < 7; ++i) c.r(rWC + i, k) = 0.0;
+    }
+}
+
+// stage-parallel: the operand rows from the rows the linearisation stored
 template <int BM>
 __device__ __forceinline__ void phase_ric_prep(const Ctx<BM>& c) {
-    const int N = c.N;
-    for (int k = c.lane; k <= N; k += W) {
-        double g[8], hd[6], su0 = 0.0, su1 = 0.0;   // read every source row before the first overlay write
-#pragma unroll
-        for (int v = 0; v < 8; ++v) g[v] = (v >= 6 && k == N) ? 0.0 : c.r(rGF + v, k) + c.mu * c.g(rDB + v, k);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            const int wi = w_idx(i, i);
-            double d = c.g(rSG + i, k);
-            if (wi >= 0 && k < N) d += c.r(rWC + wi, k);
-            hd[i] = d;
-        }
-        if (k < N) { su0 = c.g(rSG + 6, k); su1 = c.g(rSG + 7, k); }
-#pragma unroll
-        for (int v = 0; v < 8; ++v) {
-            if (v >= 6 && k == N) break;
-            c.r(rGF + v, k) = g[v];
-        }
-#pragma unroll
-        for (int i = 0; i < 6; ++i) c.r(rHD + i, k) = hd[i];
-        c.r(rSGU, k) = su0;
-        c.r(rSGU + 1, k) = su1;
-        if (k < N) {
-            double cn[6];
-#pragma unroll
-            for (int i = 0; i < 6; ++i) cn[i] = c.r(rCC + i, k + 1);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) c.r(rBH + i, k) = -cn[i];
-            double g0, g1;
-            gu_shift(c, g[6], g[7], su0, su1, cn[4], cn[5], 0.0, g0, g1);
-            c.r(rGU, k) = g0;
-            c.r(rGU + 1, k) = g1;
-        } else {  // terminal stage: no dynamics, so no curvature
-#pragma unroll
-            for (int i = 0; i < 7; ++i) c.r(rWC + i, k) = 0.0;
-        }
-    }
+    for (int k = c.lane; k <= c.N; k += W) ric_operands<false>(c, k, nullptr);
     __syncthreads();
 }
 
 // The carried builds' phase_ric_prep: the same operand rows, written by the lanes that produced their sources in
 // phase_linearize, from registers (Carry) -- no Sigma / dB rows, no reads at all but gu_shift's weights.  Each source is
-// made opaque first (opq): the rows' values are the ones phase_ric_prep forms from the stored operands.  Lane pairs:
-// lane `part` writes the rows of its own variables 2t + part and residual rows 2q + part; g_u' needs the partner's input
+// made opaque first (opq): the rows' values are the ones phase_ric_prep forms from the stored operands.  One stage per
+// lane: ric_operands from the carried source.  Lane pairs keep a text of their own (the DPP exchange below): lane `part` writes the rows of its own variables 2t + part and residual rows 2q + part; g_u' needs the partner's input
 // gradient, Sigma_u and c_{k+1}[4 + part], exchanged by the DPP quad swap of stage_trig.
 template <int BM>
 __device__ __forceinline__ void phase_ric_tail(const Ctx<BM>& c, const Carry& cy) {
@@ -1119,42 +1039,7 @@ __device__ __forceinline__ void phase_ric_tail(const Ctx<BM>& c, const Carry& cy
             }
         }
     } else {
-        for (int k = c.lane; k <= N; k += W) {
-            const bool st = k < N;
-            double g[8], hd[6];
-#pragma unroll
-            for (int v = 0; v < 8; ++v) g[v] = (v >= 6 && !st) ? 0.0 : opq(cy.gf[v]) + c.mu * opq(cy.db[v]);
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                double d = opq(cy.sg[i]);
-                if (w_idx(i, i) >= 0 && st) d += opq(cy.wd[i]);
-                hd[i] = d;
-            }
-            const double su0 = st ? opq(cy.sg[6]) : 0.0, su1 = st ? opq(cy.sg[7]) : 0.0;
-#pragma unroll
-            for (int v = 0; v < 8; ++v) {
-                if (v >= 6 && !st) break;
-                c.r(rGF + v, k) = g[v];
-            }
-#pragma unroll
-            for (int i = 0; i < 6; ++i) c.r(rHD + i, k) = hd[i];
-            c.r(rSGU, k) = su0;
-            c.r(rSGU + 1, k) = su1;
-            if (st) {
-                double cn[6];
-#pragma unroll
-                for (int i = 0; i < 6; ++i) cn[i] = opq(cy.cn[i]);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) c.r(rBH + i, k) = -cn[i];
-                double g0, g1;
-                gu_shift(c, g[6], g[7], su0, su1, cn[4], cn[5], 0.0, g0, g1);
-                c.r(rGU, k) = g0;
-                c.r(rGU + 1, k) = g1;
-            } else {  // terminal stage: no dynamics, so no curvature
-#pragma unroll
-                for (int i = 0; i < 7; ++i) c.r(rWC + i, k) = 0.0;
-            }
-        }
+        for (int k = c.lane; k <= N; k += W) ric_operands<true>(c, k, &cy);
     }
     __syncthreads();
 }
@@ -1480,35 +1365,19 @@ __device__ __forceinline__ StepInfo phase_step(const Ctx<BM>& c, Carry& cy, int 
             if (c.pair && t >= 4) break;
             const int vb = c.pair ? 2 * t : t, v = vb + p;
             if (vb >= 6 && k == N) break;
-            if constexpr (CR) {
-                const double d = c.r(dzr + v, k), xv = cy.x[t];
-                cy.d[t] = d;
-                Dg += c.gr(v, k) * d;
-                rel = fmax(rel, fabs(d) * frcp(1.0 + fabs(xv)));
-                if (c.hl(vb)) {
-                    const double s = cy.sl[t], rs = cy.rl[t], zl = cy.zl[t];
-                    ftb(s, d, c.tau, ap);
-                    ftb(zl, (c.mu - zl * d) * rs - zl, c.tau, az);
-                }
-                if (c.hu(vb)) {
-                    const double s = cy.su[t], rs = cy.ru[t], zu = cy.zu[t];
-                    ftb(s, -d, c.tau, ap);
-                    ftb(zu, (c.mu + zu * d) * rs - zu, c.tau, az);
-                }
-            } else {
-            const double d = c.r(dzr + v, k), xv = c.r(rX + v, k);
+            const double d = c.r(dzr + v, k), xv = CR ? cy.x[t] : c.r(rX + v, k);
+            if constexpr (CR) cy.d[t] = d;
             Dg += c.gr(v, k) * d;
             rel = fmax(rel, fabs(d) * frcp(1.0 + fabs(xv)));  // only tested against 1e-15
             if (c.hl(vb)) {
-                const double s = xv - c.lb(v), rs = frcp(s), zl = c.r(rZL + v, k);
-                ftb(s, d, c.tau, ap);
-                ftb(zl, (c.mu - zl * d) * rs - zl, c.tau, az);
+                const BoundOps o = bound_ops<CR, false>(c, cy, t, v, k, xv);
+                ftb(o.s, d, c.tau, ap);
+                ftb(o.z, dz_bound(o.z, d, o.rs, c.mu), c.tau, az);
             }
             if (c.hu(vb)) {
-                const double s = c.ub(v) - xv, rs = frcp(s), zu = c.r(rZU + v, k);
-                ftb(s, -d, c.tau, ap);
-                ftb(zu, (c.mu + zu * d) * rs - zu, c.tau, az);
-            }
+                const BoundOps o = bound_ops<CR, true>(c, cy, t, v, k, xv);
+                ftb(o.s, -d, c.tau, ap);
+                ftb(o.z, dz_bound(o.z, -d, o.rs, c.mu), c.tau, az);
             }
         }
         if constexpr (CR) {
@@ -1602,8 +1471,8 @@ __device__ __forceinline__ Trial phase_trial(const Ctx<BM>& c, double alpha, int
             const int vb = c.pair ? 2 * t : t, v = vb + p;
             if (vb >= 6 && k == N) break;
             const double xv = vb < 6 ? psel(p, x[vb], x[c.pair ? vb + 1 : vb]) : psel(p, u[vb - 6], u[c.pair ? vb - 5 : vb - 6]);
-            if (c.hl(vb)) { const double s = xv - c.lb(v); if (s <= 0.0) bad = true; else ls.add(s); }
-            if (c.hu(vb)) { const double s = c.ub(v) - xv; if (s <= 0.0) bad = true; else ls.add(s); }
+            if (c.hl(vb)) slack_log(xv - c.lb(v), bad, ls);
+            if (c.hu(vb)) slack_log(c.ub(v) - xv, bad, ls);
         }
         const int nrow = c.pair ? 3 : 6;
         SUBSTAMP(c, 1);
@@ -1726,150 +1595,89 @@ __device__ __forceinline__ bool filter_ok(const Ctx<BM>& c, int nf, const Trial&
         return armijo(t.phi, phi0, alpha, D);
     }
     ftype = false;
-    return t.th <= (1.0 - kGTh) * th0 || t.phi - (phi0 - kGPh * th0) <= 10.0 * 2.220446049250313e-16 * fabs(phi0);
+    return t.th <= (1.0 - kGTh) * th0 || t.phi - (phi0 - kGPh * th0) <= kRoundOff * fabs(phi0);
 }
 
 // ============ accept the step (stage-parallel) ============
-// CR (carried builds): everything but y comes from the carried state, which leaves with the new point, the new
-// multipliers and the slacks and reciprocals at the new point (rn = mu / s_new needs them anyway) for the next
-// linearisation; X, z_L, z_U and Y are stored as ever (the partner lane, the trial and the output copy read them).
+// One stage body.  Two things are chosen at compile time.
+//   * The operands: the carried state (CR: d, x, z, the slack reciprocals and y+ from struct Carry) or the rows
+//     (bound_ops; y+ from the rYP rows).  The carried state leaves with the new point, the new multipliers and the slacks
+//     and reciprocals at the new point (rn = mu / s_new needs them anyway) for the next linearisation; X, z_L, z_U and
+//     Y are stored as ever (the partner lane, the trial and the output copy read them).
+//   * The store schedule: the new z, x, y are held back until every LDS read of the stage is issued (kLF: a read queued
+//     behind a store waits for it) or stored in place (the two-wave build).  The carried builds hold them in the carried
+//     arrays themselves and read their bounds ahead of the slot loop, as their own body did.
+
+// the accepted multiplier of a bound row at the new point xn (bnd: the bound); CR: its slack and reciprocal move on
+template <bool CR, bool UP, int BM>
+__device__ __forceinline__ double accept_bound(const Ctx<BM>& c, Carry& cy, int t, int v, int k, double xo, double xn,
+                                               double d, double az, double bnd) {
+    const BoundOps o = bound_ops<CR, UP>(c, cy, t, v, k, xo);
+    const double sn = UP ? bnd - xn : xn - bnd, rsn = frcp(sn);
+    const double zn = mult_step(o.z, az, dz_bound(o.z, UP ? -d : d, o.rs, c.mu), c.mu * rsn);
+    if constexpr (CR) {
+        (UP ? cy.su : cy.sl)[t] = sn;
+        (UP ? cy.ru : cy.rl)[t] = rsn;
+    }
+    return zn;
+}
 template <int BM, bool CR>
 __device__ __forceinline__ void phase_update(const Ctx<BM>& c, Carry& cy, int dzr, double alpha, double az) {
-    if constexpr (CR) {
+    constexpr bool LF = Ctx<BM>::kLF;
     const int N = c.N, p = c.part();
     for (int k = c.k0(); k <= N; k += c.kst()) {
-        double ynv[6], lbv[8], ubv[8];
+        double xloc[8], zlloc[8], zuloc[8], ynv[6], lbv[8], ubv[8];
+        double *xnv = CR ? cy.x : xloc, *zlv = CR ? cy.zl : zlloc, *zuv = CR ? cy.zu : zuloc;
+        if constexpr (CR)
 #pragma unroll
-        for (int q = 0; q < 6; ++q) {
-            if (c.pair && q >= 3) break;
-            ynv[q] = c.r(rY + (c.pair ? 2 * q + p : q), k);
-        }
+            for (int t = 0; t < 8; ++t) {
+                if (c.pair && t >= 4) break;
+                const int vb = c.pair ? 2 * t : t, v = vb + p;
+                if (vb >= 6 && k == N) break;
+                if (c.hl(vb)) lbv[t] = c.lb(v);
+                if (c.hu(vb)) ubv[t] = c.ub(v);
+            }
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
             if (c.pair && t >= 4) break;
             const int vb = c.pair ? 2 * t : t, v = vb + p;
             if (vb >= 6 && k == N) break;
-            if (c.hl(vb)) lbv[t] = c.lb(v);
-            if (c.hu(vb)) ubv[t] = c.ub(v);
-        }
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            if (c.pair && t >= 4) break;
-            const int vb = c.pair ? 2 * t : t;
-            if (vb >= 6 && k == N) break;
-            const double d = cy.d[t], xo = cy.x[t], xn = xo + alpha * d;
+            const double d = CR ? cy.d[t] : c.r(dzr + v, k), xo = CR ? cy.x[t] : c.r(rX + v, k), xn = xo + alpha * d;
             if (c.hl(vb)) {
-                const double zl = cy.zl[t], rs = cy.rl[t];
-                const double sn = xn - lbv[t], rsn = frcp(sn);
-                const double znew = zl + az * ((c.mu - zl * d) * rs - zl), rn = c.mu * rsn;
-                cy.zl[t] = fmax(fmin(znew, 1e10 * rn), 1e-10 * rn);  // kappa_sigma = 1e10
-                cy.sl[t] = sn;
-                cy.rl[t] = rsn;
+                zlv[t] = accept_bound<CR, false>(c, cy, t, v, k, xo, xn, d, az, CR ? lbv[t] : c.lb(v));
+                if constexpr (!LF) c.r(rZL + v, k) = zlv[t];
             }
             if (c.hu(vb)) {
-                const double zu = cy.zu[t], rs = cy.ru[t];
-                const double sn = ubv[t] - xn, rsn = frcp(sn);
-                const double znew = zu + az * ((c.mu + zu * d) * rs - zu), rn = c.mu * rsn;
-                cy.zu[t] = fmax(fmin(znew, 1e10 * rn), 1e-10 * rn);
-                cy.su[t] = sn;
-                cy.ru[t] = rsn;
-            }
-            cy.x[t] = xn;
-        }
-#pragma unroll
-        for (int q = 0; q < 6; ++q) {
-            if (c.pair && q >= 3) break;
-            const double y = ynv[q];
-            ynv[q] = y + alpha * (cy.yp[q] - y);
-        }
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            if (c.pair && t >= 4) break;
-            const int vb = c.pair ? 2 * t : t, v = vb + p;
-            if (vb >= 6 && k == N) break;
-            if (c.hl(vb)) c.r(rZL + v, k) = cy.zl[t];
-            if (c.hu(vb)) c.r(rZU + v, k) = cy.zu[t];
-            c.r(rX + v, k) = cy.x[t];
-        }
-#pragma unroll
-        for (int q = 0; q < 6; ++q) {
-            if (c.pair && q >= 3) break;
-            c.r(rY + (c.pair ? 2 * q + p : q), k) = ynv[q];
-        }
-    }
-    } else if constexpr (Ctx<BM>::kLF) {
-    const int N = c.N, p = c.part();
-    for (int k = c.k0(); k <= N; k += c.kst()) {
-        // every LDS read of the stage before its stores (a read queued behind a store waits for it)
-        double xnv[8], zlv[8], zuv[8], ynv[6];
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            if (c.pair && t >= 4) break;
-            const int vb = c.pair ? 2 * t : t, v = vb + p;
-            if (vb >= 6 && k == N) break;
-            const double d = c.r(dzr + v, k), xo = c.r(rX + v, k), xn = xo + alpha * d;
-            if (c.hl(vb)) {
-                const double zl = c.r(rZL + v, k), rs = frcp(xo - c.lb(v));
-                const double znew = zl + az * ((c.mu - zl * d) * rs - zl), rn = c.mu * frcp(xn - c.lb(v));
-                zlv[t] = fmax(fmin(znew, 1e10 * rn), 1e-10 * rn);  // kappa_sigma = 1e10
-            }
-            if (c.hu(vb)) {
-                const double zu = c.r(rZU + v, k), rs = frcp(c.ub(v) - xo);
-                const double znew = zu + az * ((c.mu + zu * d) * rs - zu), rn = c.mu * frcp(c.ub(v) - xn);
-                zuv[t] = fmax(fmin(znew, 1e10 * rn), 1e-10 * rn);
+                zuv[t] = accept_bound<CR, true>(c, cy, t, v, k, xo, xn, d, az, CR ? ubv[t] : c.ub(v));
+                if constexpr (!LF) c.r(rZU + v, k) = zuv[t];
             }
             xnv[t] = xn;
+            if constexpr (!LF) c.r(rX + v, k) = xn;
         }
 #pragma unroll
         for (int q = 0; q < 6; ++q) {
             if (c.pair && q >= 3) break;
             const int i = c.pair ? 2 * q + p : q;
             const double y = c.r(rY + i, k);
-            ynv[q] = y + alpha * (c.r(rYP + i, k) - y);
+            ynv[q] = y + alpha * ((CR ? cy.yp[q] : c.r(rYP + i, k)) - y);
+            if constexpr (!LF) c.r(rY + i, k) = ynv[q];
         }
+        if constexpr (LF) {
 #pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            if (c.pair && t >= 4) break;
-            const int vb = c.pair ? 2 * t : t, v = vb + p;
-            if (vb >= 6 && k == N) break;
-            if (c.hl(vb)) c.r(rZL + v, k) = zlv[t];
-            if (c.hu(vb)) c.r(rZU + v, k) = zuv[t];
-            c.r(rX + v, k) = xnv[t];
-        }
-#pragma unroll
-        for (int q = 0; q < 6; ++q) {
-            if (c.pair && q >= 3) break;
-            c.r(rY + (c.pair ? 2 * q + p : q), k) = ynv[q];
-        }
-    }
-    } else {
-    const int N = c.N, p = c.part();
-    for (int k = c.k0(); k <= N; k += c.kst()) {
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            if (c.pair && t >= 4) break;
-            const int vb = c.pair ? 2 * t : t, v = vb + p;
-            if (vb >= 6 && k == N) break;
-            const double d = c.r(dzr + v, k), xo = c.r(rX + v, k), xn = xo + alpha * d;
-            if (c.hl(vb)) {
-                const double zl = c.r(rZL + v, k), rs = frcp(xo - c.lb(v));
-                const double znew = zl + az * ((c.mu - zl * d) * rs - zl), rn = c.mu * frcp(xn - c.lb(v));
-                c.r(rZL + v, k) = fmax(fmin(znew, 1e10 * rn), 1e-10 * rn);  // kappa_sigma = 1e10
+            for (int t = 0; t < 8; ++t) {
+                if (c.pair && t >= 4) break;
+                const int vb = c.pair ? 2 * t : t, v = vb + p;
+                if (vb >= 6 && k == N) break;
+                if (c.hl(vb)) c.r(rZL + v, k) = zlv[t];
+                if (c.hu(vb)) c.r(rZU + v, k) = zuv[t];
+                c.r(rX + v, k) = xnv[t];
             }
-            if (c.hu(vb)) {
-                const double zu = c.r(rZU + v, k), rs = frcp(c.ub(v) - xo);
-                const double znew = zu + az * ((c.mu + zu * d) * rs - zu), rn = c.mu * frcp(c.ub(v) - xn);
-                c.r(rZU + v, k) = fmax(fmin(znew, 1e10 * rn), 1e-10 * rn);
-            }
-            c.r(rX + v, k) = xn;
-        }
 #pragma unroll
-        for (int q = 0; q < 6; ++q) {
-            if (c.pair && q >= 3) break;
-            const int i = c.pair ? 2 * q + p : q;
-            c.r(rY + i, k) += alpha * (c.r(rYP + i, k) - c.r(rY + i, k));
+            for (int q = 0; q < 6; ++q) {
+                if (c.pair && q >= 3) break;
+                c.r(rY + (c.pair ? 2 * q + p : q), k) = ynv[q];
+            }
         }
-    }
     }
     __syncthreads();
 }
@@ -1905,10 +1713,10 @@ __device__ __forceinline__ double phase_soc_alpha(const Ctx<BM>& c) {
     return wmin(as);
 }
 
-// ---------------- load one instance into LDS (coalesced flat copies) ----------------
+// ---------------- the LDS head of one instance: relaxed bounds, weights, x_init ----------------
 template <int BM>
-__device__ __forceinline__ void phase_load(const Ctx<BM>& c, const TrackArgs& a, int b) {
-    const int lane = c.lane, N = c.N, n = 8 * N + 6;
+__device__ __forceinline__ void load_head(const Ctx<BM>& c, const TrackArgs& a, int b) {
+    const int lane = c.lane;
     if (lane < 8) {  // relaxed bounds (bound_relax_factor 1e-8), -inf/+inf = free
         const int v = lane;
         const double l = v < 6 ? a.xlb[v] : a.ulb[v - 6];
@@ -1929,6 +1737,25 @@ __device__ __forceinline__ void phase_load(const Ctx<BM>& c, const TrackArgs& a,
     } else if (lane < 46) {
         c.h(hXI + lane - 40) = a.x0[(size_t)b * 6 + (lane - 40)];
     }
+}
+
+// bound push (IPOPT bound_push = bound_frac = 1e-2): z moved inside the relaxed bounds l, u that it has (hl, hu)
+__device__ __forceinline__ double push_inside(double z, double l, double u, bool hl, bool hu) {
+    if (hl && hu) {
+        const double pl = fmin(1e-2 * fmax(1.0, fabs(l)), 1e-2 * (u - l));
+        const double pu = fmin(1e-2 * fmax(1.0, fabs(u)), 1e-2 * (u - l));
+        return fmin(fmax(z, l + pl), u - pu);
+    }
+    if (hl) return fmax(z, l + 1e-2 * fmax(1.0, fabs(l)));
+    if (hu) return fmin(z, u - 1e-2 * fmax(1.0, fabs(u)));
+    return z;
+}
+
+// ---------------- load one instance into LDS (coalesced flat copies) ----------------
+template <int BM>
+__device__ __forceinline__ void phase_load(const Ctx<BM>& c, const TrackArgs& a, int b) {
+    const int lane = c.lane, N = c.N, n = 8 * N + 6;
+    load_head(c, a, b);
     if (a.zg) {
         const double* zg = a.zg + (size_t)b * n;
         for (int t = lane; t < n; t += W) c.r(t % 8, t / 8) = zg[t];
@@ -1951,27 +1778,8 @@ __device__ __forceinline__ void phase_load(const Ctx<BM>& c, const TrackArgs& a,
 // instead of two.  Same values as phase_load + phase_init (an infeasible x_init keeps the unpushed copy).
 template <int BM>
 __device__ __forceinline__ void phase_load_init_reg(const Ctx<BM>& c, const TrackArgs& a, int b) {
-    const int lane = c.lane, N = c.N;
-    if (lane < 8) {
-        const int v = lane;
-        const double l = v < 6 ? a.xlb[v] : a.ulb[v - 6];
-        const double u = v < 6 ? a.xub[v] : a.uub[v - 6];
-        const bool hl = isfinite(l) && l > -1e19, hu = isfinite(u) && u < 1e19;
-        c.h(hLB + v) = hl ? l - 1e-8 * fmax(1.0, fabs(l)) : -INFINITY;
-        c.h(hUB + v) = hu ? u + 1e-8 * fmax(1.0, fabs(u)) : INFINITY;
-    }
-    const double* wq = a.wqwr ? a.wqwr + (size_t)b * 8 : nullptr;
-    if (lane < 36) {
-        const int i = lane / 6, j = lane % 6;
-        const double q = 0.5 * (a.Q[i * 6 + j] + a.Q[j * 6 + i]);
-        c.h(hQW + lane) = wq ? q * wq[i] * wq[j] : q;
-    } else if (lane < 40) {
-        const int e = lane - 36, i = e / 2, j = e % 2;
-        const double r = 0.5 * (a.R[i * 2 + j] + a.R[j * 2 + i]);
-        c.h(hRW + e) = wq ? r * wq[6 + i] * wq[6 + j] : r;
-    } else if (lane < 46) {
-        c.h(hXI + lane - 40) = a.x0[(size_t)b * 6 + (lane - 40)];
-    }
+    const int N = c.N;
+    load_head(c, a, b);
     // relaxed bounds (the head's values) and the infeasibility test of the kernel, evaluated per lane
     double lr[8], ur[8];
     bool infeas = false;
@@ -1993,16 +1801,7 @@ __device__ __forceinline__ void phase_load_init_reg(const Ctx<BM>& c, const Trac
             if (v >= 6 && k == N) continue;
             double z = c.rcv(v);
             if (!infeas) {
-                const double l = lr[v], u = ur[v];
-                if (c.hl(v) && c.hu(v)) {
-                    const double pl = fmin(1e-2 * fmax(1.0, fabs(l)), 1e-2 * (u - l));
-                    const double pu = fmin(1e-2 * fmax(1.0, fabs(u)), 1e-2 * (u - l));
-                    z = fmin(fmax(z, l + pl), u - pu);
-                } else if (c.hl(v)) {
-                    z = fmax(z, l + 1e-2 * fmax(1.0, fabs(l)));
-                } else if (c.hu(v)) {
-                    z = fmin(z, u - 1e-2 * fmax(1.0, fabs(u)));
-                }
+                z = push_inside(z, lr[v], ur[v], c.hl(v), c.hu(v));
                 c.r(rZL + v, k) = c.hl(v) ? 1.0 : 0.0;
                 c.r(rZU + v, k) = c.hu(v) ? 1.0 : 0.0;
             }
@@ -2024,18 +1823,7 @@ __device__ __forceinline__ void phase_init(const Ctx<BM>& c) {
 #pragma unroll
         for (int v = 0; v < 8; ++v) {
             if (v >= 6 && k == N) break;
-            double z = c.r(rX + v, k);
-            const double l = c.lb(v), u = c.ub(v);
-            if (c.hl(v) && c.hu(v)) {
-                const double pl = fmin(1e-2 * fmax(1.0, fabs(l)), 1e-2 * (u - l));
-                const double pu = fmin(1e-2 * fmax(1.0, fabs(u)), 1e-2 * (u - l));
-                z = fmin(fmax(z, l + pl), u - pu);
-            } else if (c.hl(v)) {
-                z = fmax(z, l + 1e-2 * fmax(1.0, fabs(l)));
-            } else if (c.hu(v)) {
-                z = fmin(z, u - 1e-2 * fmax(1.0, fabs(u)));
-            }
-            c.r(rX + v, k) = z;
+            c.r(rX + v, k) = push_inside(c.r(rX + v, k), c.lb(v), c.ub(v), c.hl(v), c.hu(v));
             c.r(rZL + v, k) = c.hl(v) ? 1.0 : 0.0;
             c.r(rZU + v, k) = c.hu(v) ? 1.0 : 0.0;
         }
@@ -2091,6 +1879,8 @@ __global__ __launch_bounds__(W) __attribute__((amdgpu_waves_per_eu(OCC))) void t
                                                   S * kGlobalRows * (int)sizeof(double), 0x00020000);
     c.regref = NS > 0 && NS < W;
     c.pair = Ctx<BM>::kPairSym && Ctx<BM>::kDiag && NS > 0 && NS < W / 2;
+    static_assert(Ctx<BM>::kLF || (Ctx<BM>::kPairSym && Ctx<BM>::kDiag && NS > 0 && NS < W / 2),
+                  "a two-wave build (kOccBit) runs lane pairs: its stage bodies have no other form (see Ctx::kLF)");
     c.rc0 = c.rc1 = c.rc2 = c.rc3 = c.rc4 = c.rc5 = c.rc6 = c.rc7 = 0.0;
     c.ts0 = c.tc0 = c.ts1 = c.tc1 = c.ts2 = c.tc2 = 0.0;
     c.t_alpha = 0.0;

@@ -12,6 +12,8 @@ from the reference, so that on the CPU oracle (one thread):
     0.25  30  96 x 0                5-9         -
     0.5   20  93 x 0, 3 x 4         up to 57    52
     0.5   30  94 x 0, 2 x 4         up to 52    25  (and one accepted second-order correction)
+    0.5   40  95 x 0, 1 x 4         up to 39    not counted  (no build that keeps the round trips: oracle test only)
+    0.5   50  93 x 0, 3 x 4         6-57        not counted  (18 instances take more than 9 iterations)
 """
 import numpy as np
 import pytest
@@ -60,19 +62,29 @@ def _assert_tiles_bitwise(big, small, reps, tag):
             assert np.array_equal(_bits(a[96 * r:96 * (r + 1)]), _bits(b)), (tag, name, r)
 
 
-@pytest.mark.parametrize("N", [20, 30])
+def _reps_past_three_per_cu():
+    """copies of the 96 that make the first multiple of 96 above three instances per CU (9, B = 864, on 256 CUs)"""
+    import torch
+    cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+    return 3 * cus // 96 + 1
+
+
+@pytest.mark.parametrize("N", [20, 30, 50])
 def test_hard_batch_is_bitwise_across_builds(N):
     """s = 0.5 tiled 22 times (B = 2112: the two-wave build, which keeps the LDS round trips) against the same 96
     solved alone (the one-wave build with the carried state): rejected line searches, the second-order correction
-    and the non-finite exits included."""
+    and the non-finite exits included.  N = 50: tiled past three instances per CU (the HBM-band build, which keeps
+    the LDS and HBM round trips) against the 96 alone (the all-LDS carried build) -- the same comparison for the
+    one-stage-per-lane slot mapping."""
     x0, xr, ur = hard_batch(N, 0.5)
     s = _gpu_solver(N)
+    reps = _reps_past_three_per_cu() if N == 50 else 22
     small = s.solve(x0, xr, ur)
-    big = s.solve(np.tile(x0, (22, 1)), np.tile(xr, (22, 1, 1)), np.tile(ur, (22, 1, 1)))
+    big = s.solve(np.tile(x0, (reps, 1)), np.tile(xr, (reps, 1, 1)), np.tile(ur, (reps, 1, 1)))
     st, it = small[2], small[3]
-    print(f"N={N} status counts {np.bincount(st, minlength=6).tolist()} iters max {int(it.max())}")
+    print(f"N={N} B={96 * reps} status counts {np.bincount(st, minlength=6).tolist()} iters max {int(it.max())}")
     assert it.max() > 9, "the batch no longer leaves the straight path"
-    _assert_tiles_bitwise(big, small, 22, N)
+    _assert_tiles_bitwise(big, small, reps, N)
 
 
 # instances on which the build before the carried state already disagreed with the oracle: (N, index) -> its numbers

@@ -1,9 +1,10 @@
 """Diagnostic: per-phase cycle shares of the tracking kernel (TT_STAMPS build, never shipped).
 
-    python tools/phase_stamps.py [B] [N]
+    [TTMPC_STAMPS_LIB=<another stamps build>] python tools/phase_stamps.py [B] [N]
 Reads s_memtime sums per phase per instance; prints mean cycles per instance and per IPM iteration.
 Shares only -- the stamped build's absolute time is not the real kernel's (MI355X guide §7)."""
 import ctypes as C
+import os
 import sys
 from pathlib import Path
 
@@ -21,7 +22,7 @@ PH = ["load", "linearize", "mu+barrier", "riccati", "forward", "step", "merit", 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
 N = int(sys.argv[2]) if len(sys.argv) > 2 else 20
 psi = 0.9 if N >= 40 else 0.3
-L = C.CDLL(str(REPO / "car-trailer-mpc_amd" / "ttmpc" / "libttmpc_stamps.so"))
+L = C.CDLL(os.environ.get("TTMPC_STAMPS_LIB") or str(REPO / "car-trailer-mpc_amd" / "ttmpc" / "libttmpc_stamps.so"))
 L.tt_create.argtypes = [C.POINTER(_lib.TTConfig)] + [C.POINTER(C.c_double)] * 7 + [C.c_int, C.POINTER(C.c_void_p)]
 L.ttx_solve_stamped.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_void_p]
 cfg = _lib.TTConfig()
